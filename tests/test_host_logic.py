@@ -384,3 +384,33 @@ def test_bench_child_leg_that_fails_becomes_an_error_entry_not_an_exception():
     assert out["search"]["error"] == r["error"] and out["c3"]["skipped"].startswith("the run's time budget")
     assert out["summary"]["legs_failed_or_skipped"] == ["search", "c3"] and out["config"]["workload"] == "w" * 150
     assert set(bench.LEGS) == set(bench.LINE_KEY) and "group" == list(bench.LEGS)[-1]     # (the never-run N > 1 path last)
+
+
+def test_bench_dump_outputs_keeps_its_budget_and_samples_the_same_positions(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: outputs smallest first, whole while they fit; what does not fit becomes <name>_sample.npy, the
+    elements at fixed seeded positions (the same in every run); floating point as float32, integers as float64."""
+    import importlib.util
+    import torch
+    ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(bench, "DUMP_BYTES", 500_000)
+    monkeypatch.setattr(bench, "DUMP_MIN_SAMPLE_BYTES", 40_000)
+    g = torch.Generator().manual_seed(3)
+    arrays = {"frames": torch.rand(4, 20_000, generator=g), "raster": torch.rand(4, 90_000, generator=g),
+              "sync_idx": torch.arange(1, 9, dtype=torch.int32).view(4, 2), "iir_state": np.arange(20_000, dtype=np.float32)}
+    pos = bench.dump_outputs(str(tmp_path / "a"), arrays)
+    assert pos["frames"] is None and pos["sync_idx"] is None and pos["iir_state"] is None and pos["raster"] is not None
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == ["frames.npy", "iir_state.npy", "raster_sample.npy", "sync_idx.npy"]
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) <= 500_000
+    si = np.load(tmp_path / "a" / "sync_idx.npy")
+    assert si.dtype == np.float64 and np.array_equal(si, np.arange(1, 9).reshape(4, 2))
+    fr = np.load(tmp_path / "a" / "frames.npy")
+    assert fr.dtype == np.float32 and np.array_equal(fr, arrays["frames"].numpy())
+    rs = np.load(tmp_path / "a" / "raster_sample.npy")
+    p = pos["raster"]
+    assert rs.dtype == np.float32 and len(rs) == len(p) > 10_000 and np.all(np.diff(p) > 0)
+    assert np.array_equal(rs, arrays["raster"].reshape(-1).numpy()[p])
+    assert np.array_equal(bench.dump_outputs(str(tmp_path / "b"), arrays)["raster"], p)

@@ -64,7 +64,7 @@ def test_bench_multi_rank_code_path_on_one_gpu():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", TSDR_BENCH_SHARE_ONE_GPU="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(os.path.dirname(HERE), "bench.py"), "--gpus", "2", "--steps", "4",
-           "--warmup", "1", "--repeats", "2", "--search-steps", "2", "--no-cpu", "--no-ingest", "--no-extra"]
+           "--warmup", "1", "--repeats", "2", "--search-steps", "2", "--no-cpu", "--no-ingest", "--no-extra", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, f"bench --gpus 2 failed:\n{r.stdout[-3000:]}\n{r.stderr[-3000:]}"
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -87,7 +87,7 @@ def test_bench_gpus_n_launched_bare_starts_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env["TSDR_BENCH_SHARE_ONE_GPU"] = "1"
     cmd = [sys.executable, os.path.join(os.path.dirname(HERE), "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1",
-           "--repeats", "2", "--search-steps", "2", "--no-cpu", "--no-ingest", "--no-extra"]
+           "--repeats", "2", "--search-steps", "2", "--no-cpu", "--no-ingest", "--no-extra", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, f"bare bench --gpus 2 failed:\n{r.stdout[-3000:]}\n{r.stderr[-3000:]}"
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -5,5 +5,5 @@ cd /tmp
 R=$GRAFT_REPO_ROOT
 for i in 1 2 3; do
 for v in 20000 0; do
-  echo "TSDR_SYNC_GUARD_PPB=$v: $(env TSDR_SYNC_GUARD_PPB=$v python3 $R/bench.py --quick --repeats 7 $@ | python3 -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['ms_per_step'], d['timing']['ms_per_step_min'], 'fused', d['fused']['ms_per_step'], d['roofline']['kernels_ms_per_step'])")"
+  echo "TSDR_SYNC_GUARD_PPB=$v: $(env TSDR_SYNC_GUARD_PPB=$v python3 $R/bench.py --full --quick --repeats 7 $@ | python3 -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['ms_per_step'], d['timing']['ms_per_step_min'], 'fused', d['fused']['ms_per_step'], d['roofline']['kernels_ms_per_step'])")"
 done; done

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Development aid (GPU box): bench.py --quick alternately on several library builds, the order rotated every round; per build the
+# Development aid (GPU box): bench.py --full --quick alternately on several library builds, the order rotated every round; per build the
 # sorted per-launch times of the dominant kernel.   ROUNDS=5 BENCH_ARGS="..." tools/ab_rotate.sh cur ab/x.so ...
 R=${GRAFT_REPO_ROOT:-.}
 libs=("$@"); n=${#libs[@]}
@@ -7,7 +7,7 @@ for round in $(seq 0 $((${ROUNDS:-3}))); do
   for k in $(seq 0 $((n-1))); do
     lib=${libs[$(((k+round)%n))]}
     if [ "$lib" = cur ]; then unset TSDR_HIP_LIB; else export TSDR_HIP_LIB=$R/$lib; fi
-    python3 $R/bench.py --quick $BENCH_ARGS 2>/dev/null | python3 -c "
+    python3 $R/bench.py --full --quick $BENCH_ARGS 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); r=d['roofline']
 print('$lib', d['ms_per_step'], round(r['avg_launch_ms']*1e3,1), r['kernel'])"

@@ -6,17 +6,17 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out
 mkdir -p $O
-python3 $R/bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
-python3 $R/bench.py --quick --pipeline on > $O/${TAG}_bench_c2_pipeline.json 2>/dev/null
+python3 $R/bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
+python3 $R/bench.py --full --quick --pipeline on > $O/${TAG}_bench_c2_pipeline.json 2>/dev/null
 # kernel traces of the pipelined loop in the arrangement the library measured fastest (do the launches overlap?)
 $R/tools/prof_pipeline.sh $TAG > /dev/null 2>&1
 $R/tools/calib_fetch.sh $TAG > /dev/null 2>&1
 rm -rf $O/${TAG}_stats $O/${TAG}_pmc_*
 # (the legs that run launches of two streams side by side -- `pipeline`, `two_streams` -- are left out of the profiled command:
 # their stretched launches of the same kernel symbols would be averaged into the per-kernel durations the roofline is checked against)
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_stats -o run -- python3 $R/bench.py --no-cpu --no-ingest --no-pipeline-leg --no-two-streams > $O/${TAG}_bench_under_rocprof.json 2>/dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_stats -o run -- python3 $R/bench.py --full --no-cpu --no-ingest --no-pipeline-leg --no-two-streams > $O/${TAG}_bench_under_rocprof.json 2>/dev/null
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/${TAG}_pmc_$c -o run -- python3 $R/bench.py --quick --steps 5 --warmup 2 --repeats 1 > /dev/null 2>&1
+  rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/${TAG}_pmc_$c -o run -- python3 $R/bench.py --full --quick --steps 5 --warmup 2 --repeats 1 > /dev/null 2>&1
 done
 python3 $R/tools/make_traffic.py $O/${TAG}_pmc_FETCH_SIZE $O/${TAG}_pmc_WRITE_SIZE $TAG C2 > $O/${TAG}_traffic.json
 # GetSpectrum / resampler legs: one short profiled run per leg and counter (cold-cache cycling as in the bench)
@@ -50,5 +50,5 @@ done; done
 } > $O/${TAG}_queue_probe.txt 2>&1
 cp $R/profiles/traffic.json $O/${TAG}_traffic_full.json   # (the box's copy: C2 frame kernels + search + spectra legs of this tag)
 # the bench line once more, now that this tag's traffic file is in place (its `traffic` fields are read from it)
-python3 $R/bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
+python3 $R/bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
 ls $O | grep $TAG

@@ -121,7 +121,7 @@ def main():
     except Exception:
         doc = {}
     doc["_note"] = ("HBM-side bytes per launch from rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE (separate passes, --kernel-trace "
-                    "only) on `python3 bench.py --quick --steps 5 --warmup 2` (MI355X, ROCm 7.2); built by tools/make_traffic.py from "
+                    "only) on `python3 bench.py --full --quick --steps 5 --warmup 2` (MI355X, ROCm 7.2); built by tools/make_traffic.py from "
                     f"the passes tagged {tag}.  Counter unit KB, median over a kernel's launches.  gfx950 correction per "
                     "MI355X_MICROARCH.md (HBM section): FETCH_SIZE counts coalesced reads at one half, so fetch bytes = "
                     "FETCH_SIZE*1024*2; WRITE_SIZE taken as is.  Infinity-Cache hits are included in FETCH_SIZE.")

@@ -1,4 +1,4 @@
-"""print the interesting parts of a bench.py JSON line (stdin or file)"""
+"""print the interesting parts of a `bench.py --full` JSON line (stdin or file)"""
 import json, sys
 src = open(sys.argv[1]) if len(sys.argv) > 1 else sys.stdin
 d = json.loads([l for l in src if l.startswith("{")][-1])
