@@ -114,6 +114,34 @@ _SIGS = {
     "tsdr_sync_beta": (C.c_int, [vp, C.c_int, vp]),
     "tsdr_fill_beta": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp]),
     "tsdr_circshift_neg": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    # Float64 / ComplexF64 element types of the per-function API
+    "tsdr_am_demod_f64": (C.c_int, [vp, vp, c_sz, vp]),
+    "tsdr_am_demod_f64_d": (C.c_int, [vp, vp, c_sz, vp]),
+    "tsdr_invert_am_f64": (C.c_int, [vp, vp, c_sz, vp]),
+    "tsdr_invert_am_f64_d": (C.c_int, [vp, vp, c_sz, vp]),
+    "tsdr_fm_demod_f64": (C.c_int, [vp, vp, c_sz, vp]),
+    "tsdr_fm_demod_f64_d": (C.c_int, [vp, vp, c_sz, vp]),
+    "tsdr_abs2_f64": (C.c_int, [vp, vp, c_sz, vp]),
+    "tsdr_abs2_f64_d": (C.c_int, [vp, vp, c_sz, vp]),
+    "tsdr_resize1d_f64": (C.c_int, [vp, vp, c_sz, c_sz, vp]),
+    "tsdr_resize1d_f64_d": (C.c_int, [vp, vp, c_sz, c_sz, vp]),
+    "tsdr_sig_to_image_f64": (C.c_int, [vp, vp, c_sz, C.c_int, C.c_int, vp]),
+    "tsdr_sig_to_image_f64_d": (C.c_int, [vp, vp, c_sz, C.c_int, C.c_int, vp]),
+    "tsdr_resize2d_f64": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "tsdr_resize2d_f64_d": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "tsdr_downgrade_f64": (C.c_int, [vp, vp, C.c_int, C.c_int, vp]),
+    "tsdr_downgrade_f64_d": (C.c_int, [vp, vp, C.c_int, C.c_int, vp]),
+    "tsdr_naive_resample_f64": (C.c_int, [vp, vp, c_sz, C.c_int, vp]),
+    "tsdr_naive_resample_f64_d": (C.c_int, [vp, vp, c_sz, C.c_int, vp]),
+    "tsdr_sync_create_f64": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(vp)]),
+    "tsdr_vsync_f64": (C.c_int, [vp, vp, c_i, c_i]),
+    "tsdr_vsync_f64_d": (C.c_int, [vp, vp, vp]),
+    "tsdr_sync_beta_f64": (C.c_int, [vp, C.c_int, vp]),
+    "tsdr_fill_beta_f64": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp]),
+    "tsdr_autocorr_f64": (C.c_int, [vp, vp, c_sz, C.c_double, C.c_double, C.c_double, C.c_int, vp, c_szp]),
+    "tsdr_autocorr_f64_d": (C.c_int, [vp, vp, c_sz, C.c_double, C.c_double, C.c_double, C.c_int, vp, c_szp]),
+    "tsdr_spectrum_f64": (C.c_int, [vp, vp, C.c_int, c_sz, C.c_int, vp]),
+    "tsdr_spectrum_f64_d": (C.c_int, [vp, vp, C.c_int, c_sz, C.c_int, vp]),
     # frame loop
     "tsdr_frames": (C.c_int, [vp, vp, vp, c_sz, c_sz, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, vp, vp, c_i]),
     "tsdr_frames_d": (C.c_int, [vp, vp, vp, c_sz, c_sz, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, vp, vp, c_i]),

@@ -41,6 +41,32 @@ def _f32(sig):
     return np.ascontiguousarray(sig, dtype=np.float32)
 
 
+def _is64(dtype):
+    """the `dtype=` keyword of the per-function API: None (today's Float32 path, input converted to f32) or np.float64
+    (the `_f64` entry points; Float64 / ComplexF64 input only)"""
+    if dtype is None:
+        return False
+    if np.dtype(dtype) == np.float64:
+        return True
+    raise AssertionError(f"dtype must be None or numpy.float64 (got {dtype}; MethodError in the reference)")
+
+
+def _need(a, dtype, what):
+    """Float64 entry points take exactly their element type: no silent conversion either way (the MethodError analogue)"""
+    if not isinstance(a, np.ndarray) or a.dtype != dtype:
+        raise AssertionError(f"{what}: expected a {np.dtype(dtype).name} array, got "
+                             f"{getattr(a, 'dtype', type(a))} (MethodError in the reference)")
+    return a
+
+
+def _c128(sig, what):
+    return np.ascontiguousarray(_need(sig, np.complex128, what))
+
+
+def _f64(sig, what):
+    return np.ascontiguousarray(_need(sig, np.float64, what))
+
+
 class Context:
     """One tsdr_ctx (HIP stream + workspaces).  One per caller thread, as in the reference's
     two-task layout."""
@@ -180,54 +206,98 @@ class Context:
         return out
 
     # -- Demodulation.jl ----------------------------------------------------------------
-    def amDemod(self, sig):
+    def amDemod(self, sig, *, dtype=None):
+        if _is64(dtype):
+            z = _c128(sig, "amDemod")
+            out = np.empty(z.shape, np.float64)
+            self.call("tsdr_am_demod_f64", _ptr(z), z.size, _ptr(out))
+            return out
         z = _c64(sig)
         out = np.empty(z.shape, np.float32)
         self.call("tsdr_am_demod", _ptr(z), z.size, _ptr(out))
         return out
 
-    def invert_amDemod(self, sig):
+    def invert_amDemod(self, sig, *, dtype=None):
+        if _is64(dtype):
+            z = _c128(sig, "invert_amDemod")
+            out = np.empty(z.shape, np.float64)
+            self.call("tsdr_invert_am_f64", _ptr(z), z.size, _ptr(out))
+            return out
         z = _c64(sig)
         out = np.empty(z.shape, np.float32)
         self.call("tsdr_invert_am", _ptr(z), z.size, _ptr(out))
         return out
 
-    def fmDemod(self, sig):
+    def fmDemod(self, sig, *, dtype=None):
+        if _is64(dtype):
+            z = _c128(sig, "fmDemod")
+            out = np.empty(z.shape, np.float64)
+            self.call("tsdr_fm_demod_f64", _ptr(z), z.size, _ptr(out))
+            return out
         z = _c64(sig)
         out = np.empty(z.shape, np.float32)
         self.call("tsdr_fm_demod", _ptr(z), z.size, _ptr(out))
         return out
 
-    def abs2(self, sig):
+    def abs2(self, sig, *, dtype=None):
+        if _is64(dtype):
+            z = _c128(sig, "abs2")
+            out = np.empty(z.shape, np.float64)
+            self.call("tsdr_abs2_f64", _ptr(z), z.size, _ptr(out))
+            return out
         z = _c64(sig)
         out = np.empty(z.shape, np.float32)
         self.call("tsdr_abs2", _ptr(z), z.size, _ptr(out))
         return out
 
     # -- Resampler.jl -------------------------------------------------------------------
-    def imresize1d(self, sig, n_out):
+    def imresize1d(self, sig, n_out, *, dtype=None):
+        if _is64(dtype):
+            x = _f64(sig, "imresize")
+            out = np.empty(int(n_out), np.float64)
+            self.call("tsdr_resize1d_f64", _ptr(x), x.size, int(n_out), _ptr(out))
+            return out
         x = _f32(sig)
         out = np.empty(int(n_out), np.float32)
         self.call("tsdr_resize1d", _ptr(x), x.size, int(n_out), _ptr(out))
         return out
 
-    def sig_to_image(self, sig, y_t, x_t):
+    def sig_to_image(self, sig, y_t, x_t, *, dtype=None):
+        if _is64(dtype):
+            x = _f64(sig, "sig_to_image")
+            img = np.empty((int(y_t), int(x_t)), np.float64, order="F")
+            self.call("tsdr_sig_to_image_f64", _ptr(x), x.size, int(y_t), int(x_t), _ptr(img))
+            return img
         x = _f32(sig)
         img = np.empty((int(y_t), int(x_t)), np.float32, order="F")
         self.call("tsdr_sig_to_image", _ptr(x), x.size, int(y_t), int(x_t), _ptr(img))
         return img
 
-    def imresize2d(self, image, size):
+    def imresize2d(self, image, size, *, dtype=None):
+        if _is64(dtype):
+            a = np.asfortranarray(_need(image, np.float64, "imresize"))
+            h, w = int(size[0]), int(size[1])
+            out = np.empty((h, w), np.float64, order="F")
+            self.call("tsdr_resize2d_f64", _ptr(a), a.shape[0], a.shape[1], h, w, _ptr(out))
+            return out
         a = np.asfortranarray(image, dtype=np.float32)
         h, w = int(size[0]), int(size[1])
         out = np.empty((h, w), np.float32, order="F")
         self.call("tsdr_resize2d", _ptr(a), a.shape[0], a.shape[1], h, w, _ptr(out))
         return out
 
-    def downgradeImage(self, image):
-        return self.imresize2d(image, (RENDER_H, RENDER_W))
+    def downgradeImage(self, image, *, dtype=None):
+        return self.imresize2d(image, (RENDER_H, RENDER_W), dtype=dtype)
 
-    def naiveResampler(self, sigOut, sigId, upCoeff):
+    def naiveResampler(self, sigOut, sigId, upCoeff, *, dtype=None):
+        if _is64(dtype):
+            x = _f64(sigId, "naiveResampler")
+            if not (isinstance(sigOut, np.ndarray) and sigOut.dtype == np.float64 and sigOut.flags.c_contiguous):
+                raise AssertionError("sigOut must be a contiguous float64 array")
+            if sigOut.size < x.size * int(upCoeff):
+                raise IndexError("sigOut too short (BoundsError in the reference)")
+            self.call("tsdr_naive_resample_f64", _ptr(x), x.size, int(upCoeff), _ptr(sigOut))
+            return
         x = _f32(sigId)
         if not (isinstance(sigOut, np.ndarray) and sigOut.dtype == np.float32 and sigOut.flags.c_contiguous):
             raise AssertionError("sigOut must be a contiguous float32 array")
@@ -242,14 +312,15 @@ class Context:
         return Resampler(self, int(bufferSize), int(upCoeff))
 
     # -- Autocorrelations.jl --------------------------------------------------------------
-    def calculate_autocorrelation(self, x, Fs, minDelay, maxDelay, scale="log"):
-        xv = _f32(x)
+    def calculate_autocorrelation(self, x, Fs, minDelay, maxDelay, scale="log", *, dtype=None):
+        f64 = _is64(dtype)
+        xv = _f64(x, "calculate_autocorrelation") if f64 else _f32(x)
         index_min = 1 + int(np.round(minDelay * Fs))
         index_max = int(np.round(maxDelay * Fs))
         cnt = max(index_max - index_min + 1, 0)
-        out = np.empty(max(cnt, 1), np.float32)
+        out = np.empty(max(cnt, 1), np.float64 if f64 else np.float32)
         n_out = C.c_size_t(0)
-        self.call("tsdr_autocorr", _ptr(xv), xv.size, float(Fs), float(minDelay), float(maxDelay),
+        self.call("tsdr_autocorr_f64" if f64 else "tsdr_autocorr", _ptr(xv), xv.size, float(Fs), float(minDelay), float(maxDelay),
                   1 if scale == "log" else 0, _ptr(out), C.byref(n_out))
         lags = np.arange(0, index_max - index_min + 1, dtype=np.float64) * (1.0 / Fs)
         return out[: n_out.value], lags
@@ -294,13 +365,19 @@ class Context:
             return a.astype(np.complex64, copy=False), 1
         return a.astype(np.float32, copy=False), 0
 
-    def getSpectrum(self, fs, sig, N=None, lin=False):
-        a, cplx = self._sig(sig)
+    def getSpectrum(self, fs, sig, N=None, lin=False, *, dtype=None):
+        f64 = _is64(dtype)
+        if f64:
+            if not (isinstance(sig, np.ndarray) and sig.dtype in (np.float64, np.complex128)):
+                raise AssertionError(f"getSpectrum: expected a float64 / complex128 array, got {getattr(sig, 'dtype', type(sig))}")
+            a, cplx = np.ascontiguousarray(sig), int(np.iscomplexobj(sig))
+        else:
+            a, cplx = self._sig(sig)
         N = a.size if N is None else int(N)
         if N > a.size:
             raise IndexError("N exceeds the signal length (BoundsError in the reference)")
-        y = np.empty(N, np.float32)
-        self.call("tsdr_spectrum", _ptr(a), cplx, N, int(lin), _ptr(y))
+        y = np.empty(N, np.float64 if f64 else np.float32)
+        self.call("tsdr_spectrum_f64" if f64 else "tsdr_spectrum", _ptr(a), cplx, N, int(lin), _ptr(y))
         freq = (np.arange(N) / N - 0.5) * fs
         return freq, y
 
@@ -336,17 +413,18 @@ class Context:
         return out
 
     # -- FrameSynchronisation.jl ------------------------------------------------------------
-    def SyncXY(self, image):
+    def SyncXY(self, image, *, dtype=None):
         a = np.asarray(image)
-        return SyncXY(self, a.shape[0], a.shape[1])
+        return SyncXY(self, a.shape[0], a.shape[1], dtype=np.float64 if _is64(dtype) else np.float32)
 
     def vsync(self, image, sync):
         return sync.vsync(image)
 
-    def fill_beta(self, cv, n, w_min, w_max):
-        x = _f32(cv)
-        beta = np.empty((w_max - w_min + 1, n), np.float32, order="F")
-        self.call("tsdr_fill_beta", _ptr(x), int(n), int(w_min), int(w_max), _ptr(beta))
+    def fill_beta(self, cv, n, w_min, w_max, *, dtype=None):
+        f64 = _is64(dtype)
+        x = _f64(cv, "fill_beta!") if f64 else _f32(cv)
+        beta = np.empty((w_max - w_min + 1, n), np.float64 if f64 else np.float32, order="F")
+        self.call("tsdr_fill_beta_f64" if f64 else "tsdr_fill_beta", _ptr(x), int(n), int(w_min), int(w_max), _ptr(beta))
         return beta
 
     def circshift_neg(self, image, s_y, s_x):
@@ -593,13 +671,18 @@ class StagingRing:
 
 
 class SyncXY:
-    """SyncXY{Float32} state (FrameSynchronisation.jl:25-48) living on the device."""
+    """SyncXY{Float32} state (FrameSynchronisation.jl:25-48) living on the device; dtype=np.float64: SyncXY{Float64}
+    (tsdr_sync_create_f64), whose vsync takes Float64 images and whose beta fields are Float64."""
 
-    def __init__(self, ctx, y_t, x_t):
+    def __init__(self, ctx, y_t, x_t, dtype=np.float32):
         self.ctx = ctx
         self.y_t, self.x_t = int(y_t), int(x_t)
+        if np.dtype(dtype) not in (np.float32, np.float64):
+            raise AssertionError(f"SyncXY{{{dtype}}}: only Float32 and Float64 states exist (MethodError in the reference)")
+        self.dtype = np.dtype(dtype)
+        self.f64 = self.dtype == np.float64
         h = C.c_void_p(0)
-        ctx.call("tsdr_sync_create", self.y_t, self.x_t, C.byref(h))
+        ctx.call("tsdr_sync_create_f64" if self.f64 else "tsdr_sync_create", self.y_t, self.x_t, C.byref(h))
         self.h = h.value
         b = (C.c_int * 4)()
         check(ctx.h, ctx.lib.tsdr_sync_bounds(self.h, b), "tsdr_sync_bounds")
@@ -609,11 +692,15 @@ class SyncXY:
         check(self.ctx.h, self.ctx.lib.tsdr_sync_reset(self.h), "tsdr_sync_reset")
 
     def vsync(self, image):
-        a = np.asfortranarray(image, dtype=np.float32)
+        if self.f64:
+            a = np.asfortranarray(_need(image, np.float64, "vsync(::Matrix, ::SyncXY{Float64})"))
+        else:
+            a = np.asfortranarray(image, dtype=np.float32)
         if a.shape != (self.y_t, self.x_t):
             raise AssertionError("image size does not match the SyncXY state")
         sy, sx = C.c_int(0), C.c_int(0)
-        check(self.ctx.h, self.ctx.lib.tsdr_vsync(self.h, _ptr(a), C.byref(sy), C.byref(sx)), "tsdr_vsync")
+        fn = "tsdr_vsync_f64" if self.f64 else "tsdr_vsync"
+        check(self.ctx.h, getattr(self.ctx.lib, fn)(self.h, _ptr(a), C.byref(sy), C.byref(sx)), fn)
         return sy.value, sx.value
 
     def beta(self, which):
@@ -622,8 +709,9 @@ class SyncXY:
             shape, w = (1 + self.wmax_x - self.wmin_x, self.x_t), 0
         else:
             shape, w = (1 + self.wmax_y - self.wmin_y, self.y_t), 1
-        out = np.empty(shape, np.float32, order="F")
-        check(self.ctx.h, self.ctx.lib.tsdr_sync_beta(self.h, w, _ptr(out)), "tsdr_sync_beta")
+        out = np.empty(shape, self.dtype, order="F")
+        fn = "tsdr_sync_beta_f64" if self.f64 else "tsdr_sync_beta"
+        check(self.ctx.h, getattr(self.ctx.lib, fn)(self.h, w, _ptr(out)), fn)
         return out
 
     def close(self):
@@ -693,17 +781,20 @@ def default_context():
 
 
 # module-level functions with the reference's names, bound to the default context
-def amDemod(sig): return default_context().amDemod(sig)
-def invert_amDemod(sig): return default_context().invert_amDemod(sig)
-def fmDemod(sig): return default_context().fmDemod(sig)
-def sig_to_image(sig, y_t, x_t): return default_context().sig_to_image(sig, y_t, x_t)
-def downgradeImage(image): return default_context().downgradeImage(image)
-def naiveResampler(sigOut, sigId, upCoeff): return default_context().naiveResampler(sigOut, sigId, upCoeff)
+def amDemod(sig, *, dtype=None): return default_context().amDemod(sig, dtype=dtype)
+def invert_amDemod(sig, *, dtype=None): return default_context().invert_amDemod(sig, dtype=dtype)
+def fmDemod(sig, *, dtype=None): return default_context().fmDemod(sig, dtype=dtype)
+def abs2(sig, *, dtype=None): return default_context().abs2(sig, dtype=dtype)
+def imresize1d(sig, n_out, *, dtype=None): return default_context().imresize1d(sig, n_out, dtype=dtype)
+def imresize2d(image, size, *, dtype=None): return default_context().imresize2d(image, size, dtype=dtype)
+def sig_to_image(sig, y_t, x_t, *, dtype=None): return default_context().sig_to_image(sig, y_t, x_t, dtype=dtype)
+def downgradeImage(image, *, dtype=None): return default_context().downgradeImage(image, dtype=dtype)
+def naiveResampler(sigOut, sigId, upCoeff, *, dtype=None): return default_context().naiveResampler(sigOut, sigId, upCoeff, dtype=dtype)
 def init_resampler(T, bufferSize, upCoeff): return default_context().init_resampler(T, bufferSize, upCoeff)
-def calculate_autocorrelation(x, Fs, minDelay, maxDelay, scale="log"):
-    return default_context().calculate_autocorrelation(x, Fs, minDelay, maxDelay, scale)
+def calculate_autocorrelation(x, Fs, minDelay, maxDelay, scale="log", *, dtype=None):
+    return default_context().calculate_autocorrelation(x, Fs, minDelay, maxDelay, scale, dtype=dtype)
 def zoom_autocorr(G, Fs, rate_min=20, rate_max=100): return default_context().zoom_autocorr(G, Fs, rate_min, rate_max)
-def getSpectrum(fs, sig, N=None): return default_context().getSpectrum(fs, sig, N)
+def getSpectrum(fs, sig, N=None, *, dtype=None): return default_context().getSpectrum(fs, sig, N, dtype=dtype)
 def getWelch(fe, sig, sizeFFT=1024): return default_context().getWelch(fe, sig, sizeFFT)
 def getWaterfall(fe, sig, sizeFFT=1024): return default_context().getWaterfall(fe, sig, sizeFFT)
 def vsync(image, sync): return sync.vsync(image)

@@ -29,6 +29,9 @@ enum Slot {
   WS_FFT_D,
   WS_MISC,
   WS_GUARD,       // sync guard: flags + per-workgroup top-2 column maxima (guard.h)
+  WS_F64_A,       // Float64 per-function entry points (*_f64): transform / staging buffers of their own, so that an f64
+  WS_F64_B,       // call never moves a workspace the f32 paths hold
+  WS_F64_C,
   WS_COUNT
 };
 

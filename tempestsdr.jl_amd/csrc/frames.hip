@@ -36,6 +36,7 @@ int sync_guard_d(tsdr_sync *s, const float *iq, size_t S, int y_t, int x_t, int 
 int sync_workspace(tsdr_sync *s, int frames, int slot, int nslots, const ProjLayout *pl_in, float **proj,
                    unsigned long long **keys);
 int sync_use_lane(tsdr_sync *s, int lane);
+bool sync_is_f64(const tsdr_sync *s);
 int shift_iir_d(tsdr_ctx *ctx, tsdr_sync *s, const float *img, size_t img_stride, int h, int w, int frames,
                 const unsigned long long *keys, int do_align, float alpha, float *state, float *frames_out,
                 int *sync_idx);
@@ -45,7 +46,13 @@ using namespace tsdr;
 
 extern "C" {
 
+// the frame loop is Float32 only: a SyncXY{Float64} state is refused whether or not it is used
+static int sync_f32_check(tsdr_ctx *ctx, const tsdr_sync *sync) {
+  return sync_is_f64(sync) ? set_err(ctx, TSDR_EINVAL, "the frame loop takes a SyncXY{Float32} state (got SyncXY{Float64})") : (int)TSDR_OK;
+}
+
 static int frames_check(tsdr_ctx *ctx, tsdr_sync *sync, int do_align) {
+  if (int rc = sync_f32_check(ctx, sync)) return rc;
   if (!do_align) return TSDR_OK;
   if (!sync) return set_err(ctx, TSDR_EINVAL, "do_align needs a SyncXY state");
   int b[4];
@@ -251,6 +258,7 @@ int tsdr_frames_d(tsdr_ctx *ctx, tsdr_sync *sync, const float *iq, size_t nEch, 
                   int do_align, float *imageOut_state, float *frames_out, float *raster_out, int *sync_idx,
                   int *n_frames) {
   if (!ctx || !imageOut_state || S == 0 || y_t <= 0 || x_t <= 0) return TSDR_EINVAL;
+  if (int rc = sync_f32_check(ctx, sync)) return rc;
   const size_t nb = nEch / S;
   if (nb > (size_t)1 << 20) return set_err(ctx, TSDR_EINVAL, "too many frames in one buffer");
   if (ctx->pipe_n) {  // buffers submitted through the pipeline come first (SyncXY and imageOut state are sequential)
@@ -669,6 +677,7 @@ int tsdr_frames_flush(tsdr_ctx *ctx) {
 int tsdr_frames(tsdr_ctx *ctx, tsdr_sync *sync, const float *iq, size_t nEch, size_t S, int y_t, int x_t, float alpha,
                 int do_align, float *imageOut_state, float *frames_out, float *raster_out, int *sync_idx, int *n_frames) {
   if (!ctx || !imageOut_state || S == 0 || y_t <= 0 || x_t <= 0 || (nEch && !iq)) return TSDR_EINVAL;
+  if (int rc = sync_f32_check(ctx, sync)) return rc;
   const size_t nb = nEch / S, npx = (size_t)TSDR_RENDER_H * TSDR_RENDER_W, P = (size_t)y_t * x_t;
   float *d_iq = (float *)ctx->scratch(WS_IN, nEch * 8);
   float *d_state = (float *)ctx->scratch(WS_AUX, npx * 4);

@@ -39,18 +39,7 @@
 #include "down_fused.h"
 #include "guard.h"
 #include "sync_layout.h"
-
-struct tsdr_sync {
-  tsdr_ctx *ctx;
-  int y_t, x_t;
-  int wmin_y, wmax_y, wmin_x, wmax_x;
-  float h[5];
-  float *beta_x = nullptr;  // device, (1+wmax_x-wmin_x) x x_t   (the current set: one of bset[])
-  float *beta_y = nullptr;  // device, (1+wmax_y-wmin_y) x y_t
-  float *bset[4][2] = {};   // [pipeline lane][x / y]: sync_use_lane
-  int *pending = nullptr;   // device: [cur] = s_y the next vsync call will return (argmax of beta_y); double-buffered
-  int cur = 0;
-};
+#include "sync_state.h"
 
 namespace tsdr {
 
@@ -954,6 +943,8 @@ int shift_iir_d(tsdr_ctx *ctx, tsdr_sync *s, const float *img, size_t img_stride
 // Pipelined frame loop, symmetric mode (frames.hip): the beta matrices k_beta / k_guard leave for the LAST frame of a buffer go
 // to a set of their own per lane, since the statistics of two buffers may run side by side; the state's current matrices
 // are those of the lane submitted last.
+bool sync_is_f64(const tsdr_sync *s) { return s && s->f64; }
+
 int sync_use_lane(tsdr_sync *s, int lane) {
   tsdr_ctx *ctx = s->ctx;
   lane &= 3;
@@ -1015,8 +1006,13 @@ int tsdr_sync_reset(tsdr_sync *s) {
     if (rc) return rc;
   }
   const size_t nbx = (size_t)(1 + s->wmax_x - s->wmin_x) * s->x_t, nby = (size_t)(1 + s->wmax_y - s->wmin_y) * s->y_t;
-  TSDR_HIP(ctx, hipMemsetAsync(s->beta_x, 0, nbx * 4, ctx->stream));
-  TSDR_HIP(ctx, hipMemsetAsync(s->beta_y, 0, nby * 4, ctx->stream));
+  if (s->f64) {
+    TSDR_HIP(ctx, hipMemsetAsync(s->beta64_x, 0, nbx * 8, ctx->stream));
+    TSDR_HIP(ctx, hipMemsetAsync(s->beta64_y, 0, nby * 8, ctx->stream));
+  } else {
+    TSDR_HIP(ctx, hipMemsetAsync(s->beta_x, 0, nbx * 4, ctx->stream));
+    TSDR_HIP(ctx, hipMemsetAsync(s->beta_y, 0, nby * 4, ctx->stream));
+  }
   const int one[4] = {1, 1, 0, 0};  // findmax of an all-zero beta_y is index (1,1)
   s->cur = 0;
   TSDR_HIP(ctx, hipMemcpyAsync(s->pending, one, 16, hipMemcpyHostToDevice, ctx->stream));
@@ -1032,6 +1028,7 @@ void tsdr_sync_free(tsdr_sync *s) {
   }
   for (auto &b : s->bset) for (float *p : b) if (p) (void)hipFree(p);
   if (s->pending) (void)hipFree(s->pending);
+  for (void *p : {(void *)s->beta64_x, (void *)s->beta64_y, (void *)s->blk64}) if (p) (void)hipFree(p);
   delete s;
 }
 
@@ -1044,6 +1041,7 @@ int tsdr_sync_bounds(const tsdr_sync *s, int b[4]) {
 int tsdr_vsync_d(tsdr_sync *s, const float *img, int *s_yx_dev) {
   if (!s || !img) return TSDR_EINVAL;
   tsdr_ctx *ctx = s->ctx;
+  if (s->f64) return set_err(ctx, TSDR_EINVAL, "tsdr_vsync_d: SyncXY{Float64} state (use tsdr_vsync_f64_d)");
   {
     int rc = pipe_drain(ctx);
     if (rc) return rc;
@@ -1063,6 +1061,7 @@ int tsdr_vsync_d(tsdr_sync *s, const float *img, int *s_yx_dev) {
 int tsdr_vsync(tsdr_sync *s, const float *img, int *s_y, int *s_x) {
   if (!s || !img || !s_y || !s_x) return TSDR_EINVAL;
   tsdr_ctx *ctx = s->ctx;
+  if (s->f64) return set_err(ctx, TSDR_EINVAL, "tsdr_vsync: SyncXY{Float64} state (use tsdr_vsync_f64)");
   const size_t bytes = (size_t)s->y_t * s->x_t * 4;
   float *d = (float *)ctx->scratch(WS_IN, bytes);
   int *didx = (int *)ctx->scratch(WS_OUT, 16);
@@ -1080,6 +1079,7 @@ int tsdr_vsync(tsdr_sync *s, const float *img, int *s_y, int *s_x) {
 int tsdr_sync_beta(tsdr_sync *s, int which, float *beta_host) {
   if (!s || !beta_host || (which != 0 && which != 1)) return TSDR_EINVAL;
   tsdr_ctx *ctx = s->ctx;
+  if (s->f64) return set_err(ctx, TSDR_EINVAL, "tsdr_sync_beta: SyncXY{Float64} state (use tsdr_sync_beta_f64)");
   const size_t n = which == 0 ? (size_t)(1 + s->wmax_x - s->wmin_x) * s->x_t : (size_t)(1 + s->wmax_y - s->wmin_y) * s->y_t;
   {  // submitted buffers fill the beta sets on the pipeline's internal streams: they come first
     int rc = pipe_drain(ctx);

@@ -23,6 +23,7 @@ export hip_frames!, hip_frames_submit!, hip_frames_submit_sc16!, hip_frames_flus
 export hip_extract_configuration, sync_guard_stats, sync_guard_auto, wait_stats   # fused GUI.jl:67-81 search; counters of the FAST loop's sync guard
 export hip_set_precision, hip_set_option                              # TSDR_EXACT / TSDR_FAST and the library's options, per task context
 export HipGroup, hip_group                                            # one process, several GPUs (RCCL inside the library): `devices = ...`
+export hip_abs2, hip_imresize, hip_sync_beta, hip_fill_beta                 # Float64 / ComplexF64 helpers (abs2, imresize, beta fields, fill_beta!)
 
 const LIB = get(ENV, "TEMPEST_HIP_LIB", joinpath(@__DIR__, "..", "libtempest_hip.so"))
 const RENDERING_SIZE = (600, 800)   # GUI.jl:10
@@ -82,6 +83,29 @@ function fmDemod(sig::Array{ComplexF32})                      # Demodulation.jl:
     return out
 end
 
+# ComplexF64 (a `readComplexBinary(file, :double)` capture, DatBinaryFiles.jl:53-64): the `_f64` entry points, Float64 out
+function amDemod(sig::Array{ComplexF64})
+    out = similar(sig, Float64); c = ctx()
+    check(c, ccall((:tsdr_am_demod_f64, LIB), Cint, (Ptr{Cvoid}, Ptr{ComplexF64}, Csize_t, Ptr{Float64}), c.h, sig, length(sig), out), "amDemod")
+    return out
+end
+function invert_amDemod(sig::Array{ComplexF64})
+    out = similar(sig, Float64); c = ctx()
+    check(c, ccall((:tsdr_invert_am_f64, LIB), Cint, (Ptr{Cvoid}, Ptr{ComplexF64}, Csize_t, Ptr{Float64}), c.h, sig, length(sig), out), "invert_amDemod")
+    return out
+end
+function fmDemod(sig::Array{ComplexF64})
+    out = similar(sig, Float64); c = ctx()
+    check(c, ccall((:tsdr_fm_demod_f64, LIB), Cint, (Ptr{Cvoid}, Ptr{ComplexF64}, Csize_t, Ptr{Float64}), c.h, sig, length(sig), out), "fmDemod")
+    return out
+end
+"`abs2.(sig)` on the device (GUI.jl:70); Float64 for ComplexF64 input"
+function hip_abs2(sig::Array{ComplexF64})
+    out = similar(sig, Float64); c = ctx()
+    check(c, ccall((:tsdr_abs2_f64, LIB), Cint, (Ptr{Cvoid}, Ptr{ComplexF64}, Csize_t, Ptr{Float64}), c.h, sig, length(sig), out), "abs2")
+    return out
+end
+
 # ---- Resampler.jl -----------------------------------------------------------------------
 function sig_to_image(sig::AbstractVector{Float32}, y_t, x_t)   # Resampler.jl:117-122
     s = _dense(sig)
@@ -102,6 +126,41 @@ function naiveResampler(sigOut::Vector{Float32}, sigId::Vector{Float32}, upCoeff
     check(c, ccall((:tsdr_naive_resample, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}, Csize_t, Cint, Ptr{Float32}),
                    c.h, sigId, length(sigId), upCoeff, sigOut), "naiveResampler")
     return nothing
+end
+# Float64 (imresize keeps the element type it is given)
+function sig_to_image(sig::AbstractVector{Float64}, y_t, x_t)
+    s = _dense(sig)
+    img = Matrix{Float64}(undef, Int(y_t), Int(x_t)); c = ctx()
+    check(c, ccall((:tsdr_sig_to_image_f64, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Csize_t, Cint, Cint, Ptr{Float64}),
+                   c.h, s, length(s), y_t, x_t, img), "sig_to_image")
+    return img
+end
+function downgradeImage(image::AbstractMatrix{Float64})
+    a = _dense(image); out = Matrix{Float64}(undef, RENDERING_SIZE...); c = ctx()
+    check(c, ccall((:tsdr_downgrade_f64, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Cint, Cint, Ptr{Float64}),
+                   c.h, a, size(a, 1), size(a, 2), out), "downgradeImage")
+    return out
+end
+function naiveResampler(sigOut::Vector{Float64}, sigId::Vector{Float64}, upCoeff)
+    length(sigOut) >= upCoeff * length(sigId) || throw(BoundsError(sigOut, upCoeff * length(sigId)))
+    c = ctx()
+    check(c, ccall((:tsdr_naive_resample_f64, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Csize_t, Cint, Ptr{Float64}),
+                   c.h, sigId, length(sigId), upCoeff, sigOut), "naiveResampler")
+    return nothing
+end
+"`imresize(sig, n_out)` on a Float64 vector (the 1-D core of sig_to_image, Resampler.jl:119)"
+function hip_imresize(sig::AbstractVector{Float64}, n_out::Integer)
+    s = _dense(sig); out = Vector{Float64}(undef, n_out); c = ctx()
+    check(c, ccall((:tsdr_resize1d_f64, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Csize_t, Csize_t, Ptr{Float64}),
+                   c.h, s, length(s), n_out, out), "imresize")
+    return out
+end
+"`imresize(image, (h_out, w_out))` on a Float64 matrix (Resampler.jl:125)"
+function hip_imresize(image::AbstractMatrix{Float64}, sz::Tuple{Integer,Integer})
+    a = _dense(image); out = Matrix{Float64}(undef, sz[1], sz[2]); c = ctx()
+    check(c, ccall((:tsdr_resize2d_f64, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Cint, Cint, Cint, Cint, Ptr{Float64}),
+                   c.h, a, size(a, 1), size(a, 2), sz[1], sz[2], out), "imresize")
+    return out
 end
 function init_resampler(T::Type, bufferSize::Int, upCoeff::Int)  # Resampler.jl:26-62
     T == Float32 || throw(AssertionError("the HIP path implements Float32 resamplers"))
@@ -124,8 +183,9 @@ init_resampler(x::Vector{T}, upCoeff) where T = init_resampler(T, length(x), upC
 
 # ---- Autocorrelations.jl ------------------------------------------------------------------
 # Element types.  The reference's functions are generic in T; its own callers (GUI.jl, production/) only ever pass
-# Float32 / ComplexF32, and those are the methods this shim defines.  Anything else is a MethodError -- never a silent
-# conversion to Float32, which would compute in less precision than the reference would have (INTEGRATION.md, section 4).
+# Float32 / ComplexF32; the offline flow of production/investigate_data.jl also runs on a :double capture, in Float64.  Those
+# are the methods this shim defines.  Anything else is a MethodError -- never a silent conversion, which would compute in
+# another precision than the reference would have (INTEGRATION.md, section 4).
 function calculate_autocorrelation(x::AbstractVector{Float32}, Fs, minDelay, maxDelay, scale = :log)   # Autocorrelations.jl:23-37
     xv = _dense(x)
     indexMin = 1 + round(minDelay * Fs) |> Int
@@ -133,6 +193,17 @@ function calculate_autocorrelation(x::AbstractVector{Float32}, Fs, minDelay, max
     out = Vector{Float32}(undef, max(indexMax - indexMin + 1, 1)); n = Ref{Csize_t}(0); c = ctx()
     check(c, ccall((:tsdr_autocorr, LIB), Cint,
                    (Ptr{Cvoid}, Ptr{Float32}, Csize_t, Cdouble, Cdouble, Cdouble, Cint, Ptr{Float32}, Ptr{Csize_t}),
+                   c.h, xv, length(xv), Fs, minDelay, maxDelay, scale == :log ? 1 : 0, out, n), "calculate_autocorrelation")
+    lags = (0:(indexMax - indexMin)) * 1 / Fs
+    return resize!(out, n[]), lags
+end
+function calculate_autocorrelation(x::AbstractVector{Float64}, Fs, minDelay, maxDelay, scale = :log)
+    xv = _dense(x)
+    indexMin = 1 + round(minDelay * Fs) |> Int
+    indexMax = round(maxDelay * Fs) |> Int
+    out = Vector{Float64}(undef, max(indexMax - indexMin + 1, 1)); n = Ref{Csize_t}(0); c = ctx()
+    check(c, ccall((:tsdr_autocorr_f64, LIB), Cint,
+                   (Ptr{Cvoid}, Ptr{Float64}, Csize_t, Cdouble, Cdouble, Cdouble, Cint, Ptr{Float64}, Ptr{Csize_t}),
                    c.h, xv, length(xv), Fs, minDelay, maxDelay, scale == :log ? 1 : 0, out, n), "calculate_autocorrelation")
     lags = (0:(indexMax - indexMin)) * 1 / Fs
     return resize!(out, n[]), lags
@@ -149,6 +220,8 @@ end
 # ---- GetSpectrum.jl -------------------------------------------------------------------------
 _raw(sig::AbstractVector{ComplexF32}) = (_dense(sig), 1)
 _raw(sig::AbstractVector{Float32}) = (_dense(sig), 0)
+_raw(sig::AbstractVector{ComplexF64}) = (_dense(sig), 1)
+_raw(sig::AbstractVector{Float64}) = (_dense(sig), 0)
 function getSpectrum(fs, sig; N = nothing)                                   # GetSpectrum.jl:21-30
     isnothing(N) && (N = length(sig))
     N <= length(sig) || throw(BoundsError(sig, N))
@@ -156,15 +229,23 @@ function getSpectrum(fs, sig; N = nothing)                                   # G
     check(c, ccall((:tsdr_spectrum, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Csize_t, Cint, Ptr{Float32}), c.h, a, cplx, N, 0, y), "getSpectrum")
     return (collect(((0:N-1) ./ N .- 0.5) * fs), y)
 end
+function getSpectrum(fs, sig::AbstractVector{<:Union{Float64,ComplexF64}}; N = nothing)
+    isnothing(N) && (N = length(sig))
+    N <= length(sig) || throw(BoundsError(sig, N))
+    a, cplx = _raw(sig); y = Vector{Float64}(undef, N); c = ctx()
+    check(c, ccall((:tsdr_spectrum_f64, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Csize_t, Cint, Ptr{Float64}), c.h, a, cplx, N, 0, y), "getSpectrum")
+    return (collect(((0:N-1) ./ N .- 0.5) * fs), y)
+end
 getSpectrum(sig) = getSpectrum(1, sig)
+_raw32(sig::AbstractVector{<:Union{Float32,ComplexF32}}) = _raw(sig)   # getWelch / getWaterfall stay Float32 / ComplexF32
 function getWelch(fe, sig; sizeFFT = 1024)                                   # GetSpectrum.jl:36-52
-    a, cplx = _raw(sig); y = Vector{Float32}(undef, sizeFFT); c = ctx()
+    a, cplx = _raw32(sig); y = Vector{Float32}(undef, sizeFFT); c = ctx()
     check(c, ccall((:tsdr_welch, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Csize_t, Csize_t, Cint, Ptr{Float32}),
                    c.h, a, cplx, length(a), sizeFFT, 0, y), "getWelch")
     return (collect(((0:sizeFFT-1) ./ sizeFFT .- 0.5) * fe), y)
 end
 function getWaterfall(fe, sig; sizeFFT = 1024)                               # GetSpectrum.jl:54-66
-    a, cplx = _raw(sig); nbSeg = length(a) ÷ sizeFFT
+    a, cplx = _raw32(sig); nbSeg = length(a) ÷ sizeFFT
     m = Matrix{Float64}(undef, sizeFFT, nbSeg); c = ctx()
     check(c, ccall((:tsdr_waterfall, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Csize_t, Csize_t, Ptr{Float64}),
                    c.h, a, cplx, length(a), sizeFFT, m), "getWaterfall")
@@ -179,9 +260,13 @@ mutable struct SyncXY{T}                                                      # 
     y_t::Int
     x_t::Int
     function SyncXY(image::Matrix{T}) where T
-        T == Float32 || throw(MethodError(SyncXY, (image,)))
+        T == Float32 || T == Float64 || throw(MethodError(SyncXY, (image,)))
         c = ctx(); r = Ref{Ptr{Cvoid}}(C_NULL)
-        check(c, ccall((:tsdr_sync_create, LIB), Cint, (Ptr{Cvoid}, Cint, Cint, Ptr{Ptr{Cvoid}}), c.h, size(image, 1), size(image, 2), r), "SyncXY")
+        if T == Float64          # SyncXY{Float64}: beta fields in f64 (tsdr_sync_create_f64)
+            check(c, ccall((:tsdr_sync_create_f64, LIB), Cint, (Ptr{Cvoid}, Cint, Cint, Ptr{Ptr{Cvoid}}), c.h, size(image, 1), size(image, 2), r), "SyncXY")
+        else
+            check(c, ccall((:tsdr_sync_create, LIB), Cint, (Ptr{Cvoid}, Cint, Cint, Ptr{Ptr{Cvoid}}), c.h, size(image, 1), size(image, 2), r), "SyncXY")
+        end
         s = new{T}(r[], c, size(image, 1), size(image, 2))
         finalizer(s) do x   # tsdr_sync_free touches the context's stream: skip it when the context went first
             x.c.h != C_NULL && ccall((:tsdr_sync_free, LIB), Cvoid, (Ptr{Cvoid},), x.h)
@@ -189,7 +274,28 @@ mutable struct SyncXY{T}                                                      # 
         return s
     end
 end
-function vsync(image::AbstractMatrix{T}, sync::SyncXY{T}) where T               # FrameSynchronisation.jl:56-79
+function vsync(image::AbstractMatrix{Float64}, sync::SyncXY{Float64})
+    a = _dense(image); sy = Ref{Cint}(0); sx = Ref{Cint}(0)
+    size(a) == (sync.y_t, sync.x_t) || throw(DimensionMismatch("image does not match the SyncXY state"))
+    check(sync.c, ccall((:tsdr_vsync_f64, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Cint}, Ptr{Cint}), sync.h, a, sy, sx), "vsync")
+    return (Int(sy[]), Int(sx[]))
+end
+"the beta_x (`:x`) / beta_y (`:y`) field of a SyncXY{Float64}, (w_max - w_min + 1) x n"
+function hip_sync_beta(sync::SyncXY{Float64}, which::Symbol)
+    # w_min / w_max as SyncXY derives them (FrameSynchronisation.jl:36-41)
+    shape = which == :x ? (floor(Int, sync.x_t / 4) - ceil(Int, 5 / 100 * sync.x_t) + 1, sync.x_t) :
+                          (floor(Int, sync.y_t / 4) - ceil(Int, 1 / 100 * sync.y_t) + 1, sync.y_t)
+    out = Matrix{Float64}(undef, shape...)
+    check(sync.c, ccall((:tsdr_sync_beta_f64, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}), sync.h, which == :x ? 0 : 1, out), "sync_beta")
+    return out
+end
+"fill_beta!(β, c_v, Sync(w_min, w_max, n)) (FrameSynchronisation.jl:94-112) on Float64 projections -> β"
+function hip_fill_beta(cv::AbstractVector{Float64}, n::Integer, w_min::Integer, w_max::Integer)
+    x = _dense(cv); β = Matrix{Float64}(undef, w_max - w_min + 1, n); c = ctx()
+    check(c, ccall((:tsdr_fill_beta_f64, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Cint, Cint, Cint, Ptr{Float64}), c.h, x, n, w_min, w_max, β), "fill_beta!")
+    return β
+end
+function vsync(image::AbstractMatrix{Float32}, sync::SyncXY{Float32})             # FrameSynchronisation.jl:56-79
     a = _dense(image); sy = Ref{Cint}(0); sx = Ref{Cint}(0)
     size(a) == (sync.y_t, sync.x_t) || throw(DimensionMismatch("image does not match the SyncXY state"))
     check(sync.c, ccall((:tsdr_vsync, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Cint}, Ptr{Cint}), sync.h, a, sy, sx), "vsync")

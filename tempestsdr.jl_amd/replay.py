@@ -23,13 +23,18 @@ from . import video_configurations as vc
 from .dat_files import readComplexBinary
 
 
-def replay(backend, sigRx, Fs, offset=420_000, line_method="gui"):
+def replay(backend, sigRx, Fs, offset=420_000, line_method="gui", dtype=np.complex64):
     """-> dict with every intermediate the script plots or prints.  line_method "script": the script's own 500-lag
-    estimate (investigate_data.jl:69-82); "gui": the GUI's (the lags after the frame peak, GUI.jl:491-506)."""
+    estimate (investigate_data.jl:69-82); "gui": the GUI's (the lags after the frame peak, GUI.jl:491-506).
+    dtype np.complex64 (default): the capture is processed as ComplexF32; np.complex128: as ComplexF64, Float64 from
+    amDemod to the aligned image (the `dtype=np.float64` methods of the backend), what a :double capture does in the script."""
     out = {}
-    sigId = backend.amDemod(np.ascontiguousarray(sigRx, np.complex64))                    # :37
-    out["spectrum"] = backend.getSpectrum(Fs, sigId[:80_000])                              # :44 (freqAx, dB)
-    G, _ = backend.calculate_autocorrelation(sigId, Fs, 0, 1 / 10)                         # :52
+    if np.dtype(dtype) not in (np.complex64, np.complex128):
+        raise AssertionError(f"replay: dtype must be complex64 or complex128 (got {dtype})")
+    kw = {"dtype": np.float64} if np.dtype(dtype) == np.complex128 else {}
+    sigId = backend.amDemod(np.ascontiguousarray(sigRx, dtype), **kw)                     # :37
+    out["spectrum"] = backend.getSpectrum(Fs, sigId[:80_000], **kw)                        # :44 (freqAx, dB)
+    G, _ = backend.calculate_autocorrelation(sigId, Fs, 0, 1 / 10, **kw)                   # :52
     rates_large, G_large = backend.zoom_autocorr(G, Fs, rate_min=50, rate_max=90)          # :55
     pos = int(np.argmax(G_large))                                                          # :60 findmax: first maximum
     fv = float(np.round(1.0 / (1.0 / rates_large[pos]), 2))                               # :61-62
@@ -42,16 +47,16 @@ def replay(backend, sigRx, Fs, offset=420_000, line_method="gui"):
     d = int(np.round(Fs / final.refresh))                                                  # toImage :161
     if offset + 2 * d > sigId.size:
         raise IndexError("capture too short for the image at this offset (BoundsError in the reference)")
-    image = backend.sig_to_image(sigId[offset: offset + d], final.height, final.width)     # :179 toImage == sig_to_image
-    sync = backend.SyncXY(image)                                                           # :196
+    image = backend.sig_to_image(sigId[offset: offset + d], final.height, final.width, **kw)   # :179 toImage == sig_to_image
+    sync = backend.SyncXY(image, **kw)                                                     # :196
     tup = backend.vsync(image, sync)                                                       # :197  (s_y, s_x)
     tau = tup[1] * final.width + tup[0]                                                    # :200
     idx = int(np.floor(tau / (final.width * final.height) / fv * Fs))                      # :201
-    aligned = backend.sig_to_image(sigId[offset + idx: offset + idx + d], final.height, final.width)   # :206
+    aligned = backend.sig_to_image(sigId[offset + idx: offset + idx + d], final.height, final.width, **kw)   # :206
     out.update(fv=fv, fv_unrounded=float(rates_large[pos]), lag=m, y_t=float(y_t), name=name, mode=final, sync=tuple(int(v) for v in tup),
                tau=int(tau), sample_offset=idx, image=image, aligned=aligned, G=G)
     return out
 
 
-def replay_file(backend, path, Fs, fmt="single", **kw):
-    return replay(backend, readComplexBinary(path, fmt), Fs, **kw)
+def replay_file(backend, path, Fs, fmt="single", dtype=np.complex64, **kw):
+    return replay(backend, readComplexBinary(path, fmt), Fs, dtype=dtype, **kw)
