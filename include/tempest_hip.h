@@ -320,7 +320,7 @@ int tsdr_circshift_neg(tsdr_ctx *ctx, const float *img, int h, int w, int s_y, i
  *   autocorr_f64 / spectrum_f64: complex f64 FFT (Stockham, Bluestein for prime factors > 13), abs2 and 10log10 in f64.
  * A SyncXY{Float64} (tsdr_sync_create_f64) works with tsdr_sync_reset / _bounds / _free; every f32 entry point that takes a
  * tsdr_sync (tsdr_vsync*, tsdr_sync_beta, tsdr_frames*) refuses it with TSDR_EINVAL, and tsdr_vsync_f64* / tsdr_sync_beta_f64
- * refuse an f32 state likewise.  The frame loop, ring, groups, getWelch / getWaterfall and init_resampler stay Float32. */
+ * refuse an f32 state likewise.  Only the frame loop, the ring and the groups (tsdr_group_welch included) stay Float32. */
 int tsdr_am_demod_f64(tsdr_ctx *ctx, const double *iq, size_t n, double *out);
 int tsdr_am_demod_f64_d(tsdr_ctx *ctx, const double *iq, size_t n, double *out);
 int tsdr_invert_am_f64(tsdr_ctx *ctx, const double *iq, size_t n, double *out);
@@ -353,6 +353,20 @@ int tsdr_autocorr_f64_d(tsdr_ctx *ctx, const double *x, size_t len, double Fs, d
 /* arguments as tsdr_spectrum (is_complex: interleaved ComplexF64), y Float64 */
 int tsdr_spectrum_f64(tsdr_ctx *ctx, const double *sig, int is_complex, size_t N, int lin, double *y);
 int tsdr_spectrum_f64_d(tsdr_ctx *ctx, const double *sig, int is_complex, size_t N, int lin, double *y);
+/* getWelch / getWaterfall (GetSpectrum.jl:36-66) in f64: arguments as tsdr_welch / tsdr_waterfall (is_complex: interleaved
+ * ComplexF64, 16-byte aligned for the _d forms), y / sMatrix Float64.  sizeFFT == 0 is TSDR_EINVAL; nbSeg = len / sizeFFT == 0
+ * gives zeros (-Inf dB) / nothing.  Segment transforms: 2^a 3^b 5^c <= 4096 points in LDS, the rest in chunks (LDS-blocked
+ * passes, Bluestein for prime factors > 5); abs2 = re*re + im*im without FMA, the Welch sum in f64 in a fixed order. */
+int tsdr_welch_f64(tsdr_ctx *ctx, const double *sig, int is_complex, size_t len, size_t sizeFFT, int lin, double *y);
+int tsdr_welch_f64_d(tsdr_ctx *ctx, const double *sig, int is_complex, size_t len, size_t sizeFFT, int lin, double *y);
+int tsdr_waterfall_f64(tsdr_ctx *ctx, const double *sig, int is_complex, size_t len, size_t sizeFFT, double *sMatrix);
+int tsdr_waterfall_f64_d(tsdr_ctx *ctx, const double *sig, int is_complex, size_t len, size_t sizeFFT, double *sMatrix);
+/* init_resampler(Float64, bufferSize, upCoeff): the same H as tsdr_resampler_init; resampler!(out, in) with containerFFT in
+ * ComplexF64: stuff, fft, * H, ifft (1/N), 2 upCoeff real(.), in double.  tsdr_resampler_run[_d] refuses an f64 resampler and
+ * tsdr_resampler_run_f64[_d] an f32 one (TSDR_EINVAL); _lpf / _lpf64 / _free take both kinds. */
+int tsdr_resampler_init_f64(tsdr_ctx *ctx, size_t bufferSize, int upCoeff, tsdr_resampler **out);
+int tsdr_resampler_run_f64(tsdr_resampler *r, const double *in, size_t n_in, double *out);
+int tsdr_resampler_run_f64_d(tsdr_resampler *r, const double *in, size_t n_in, double *out);
 
 /* ---- steady-state frame loop ------------------------------------------------------ */
 /* coreProcessing's per-buffer body, GUI.jl:163-178 (minus sleep/channel):

@@ -142,6 +142,13 @@ _SIGS = {
     "tsdr_autocorr_f64_d": (C.c_int, [vp, vp, c_sz, C.c_double, C.c_double, C.c_double, C.c_int, vp, c_szp]),
     "tsdr_spectrum_f64": (C.c_int, [vp, vp, C.c_int, c_sz, C.c_int, vp]),
     "tsdr_spectrum_f64_d": (C.c_int, [vp, vp, C.c_int, c_sz, C.c_int, vp]),
+    "tsdr_welch_f64": (C.c_int, [vp, vp, C.c_int, c_sz, c_sz, C.c_int, vp]),
+    "tsdr_welch_f64_d": (C.c_int, [vp, vp, C.c_int, c_sz, c_sz, C.c_int, vp]),
+    "tsdr_waterfall_f64": (C.c_int, [vp, vp, C.c_int, c_sz, c_sz, vp]),
+    "tsdr_waterfall_f64_d": (C.c_int, [vp, vp, C.c_int, c_sz, c_sz, vp]),
+    "tsdr_resampler_init_f64": (C.c_int, [vp, c_sz, C.c_int, C.POINTER(vp)]),
+    "tsdr_resampler_run_f64": (C.c_int, [vp, vp, c_sz, vp]),
+    "tsdr_resampler_run_f64_d": (C.c_int, [vp, vp, c_sz, vp]),
     # frame loop
     "tsdr_frames": (C.c_int, [vp, vp, vp, c_sz, c_sz, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, vp, vp, c_i]),
     "tsdr_frames_d": (C.c_int, [vp, vp, vp, c_sz, c_sz, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, vp, vp, c_i]),

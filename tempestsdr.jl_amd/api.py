@@ -306,10 +306,10 @@ class Context:
         self.call("tsdr_naive_resample", _ptr(x), x.size, int(upCoeff), _ptr(sigOut))
 
     def init_resampler(self, T, bufferSize, upCoeff):
-        """init_resampler(T,bufferSize,upCoeff) -> resampler!(out,in)  (Resampler.jl:26-62)"""
-        if np.dtype(T) != np.float32:
-            raise AssertionError("only Float32 resamplers are implemented on the GPU path")
-        return Resampler(self, int(bufferSize), int(upCoeff))
+        """init_resampler(T,bufferSize,upCoeff) -> resampler!(out,in)  (Resampler.jl:26-62); T is Float32 or Float64"""
+        if np.dtype(T) not in (np.float32, np.float64):
+            raise AssertionError("only Float32 and Float64 resamplers are implemented on the GPU path")
+        return Resampler(self, int(bufferSize), int(upCoeff), dtype=np.dtype(T))
 
     # -- Autocorrelations.jl --------------------------------------------------------------
     def calculate_autocorrelation(self, x, Fs, minDelay, maxDelay, scale="log", *, dtype=None):
@@ -381,18 +381,26 @@ class Context:
         freq = (np.arange(N) / N - 0.5) * fs
         return freq, y
 
-    def getWelch(self, fe, sig, sizeFFT=1024, lin=False):
-        a, cplx = self._sig(sig)
-        y = np.empty(int(sizeFFT), np.float32)
-        self.call("tsdr_welch", _ptr(a), cplx, a.size, int(sizeFFT), int(lin), _ptr(y))
+    def _sig64(self, sig, what):
+        """Float64 / ComplexF64 input of the `dtype=np.float64` spectra, as it is (no conversion)"""
+        if not (isinstance(sig, np.ndarray) and sig.dtype in (np.float64, np.complex128)):
+            raise AssertionError(f"{what}: expected a float64 / complex128 array, got {getattr(sig, 'dtype', type(sig))}")
+        return np.ascontiguousarray(sig), int(np.iscomplexobj(sig))
+
+    def getWelch(self, fe, sig, sizeFFT=1024, lin=False, *, dtype=None):
+        f64 = _is64(dtype)
+        a, cplx = self._sig64(sig, "getWelch") if f64 else self._sig(sig)
+        y = np.empty(int(sizeFFT), np.float64 if f64 else np.float32)
+        self.call("tsdr_welch_f64" if f64 else "tsdr_welch", _ptr(a), cplx, a.size, int(sizeFFT), int(lin), _ptr(y))
         freq = (np.arange(sizeFFT) / sizeFFT - 0.5) * fe
         return freq, y
 
-    def getWaterfall(self, fe, sig, sizeFFT=1024):
-        a, cplx = self._sig(sig)
+    def getWaterfall(self, fe, sig, sizeFFT=1024, *, dtype=None):
+        f64 = _is64(dtype)
+        a, cplx = self._sig64(sig, "getWaterfall") if f64 else self._sig(sig)
         nb = a.size // int(sizeFFT)
         m = np.empty((int(sizeFFT), nb), np.float64, order="F")
-        self.call("tsdr_waterfall", _ptr(a), cplx, a.size, int(sizeFFT), _ptr(m))
+        self.call("tsdr_waterfall_f64" if f64 else "tsdr_waterfall", _ptr(a), cplx, a.size, int(sizeFFT), _ptr(m))
         f_ax = (np.arange(sizeFFT) / sizeFFT - 0.5) * fe
         t_ax = np.arange(nb) * (sizeFFT / fe)
         return t_ax, f_ax, m
@@ -727,25 +735,34 @@ class SyncXY:
 
 
 class Resampler:
-    """The closure init_resampler returns (Resampler.jl:26-62): call it as r(out, inp)."""
+    """The closure init_resampler returns (Resampler.jl:26-62): call it as r(out, inp).  dtype=np.float64: the Float64 closure
+    (tsdr_resampler_init_f64), whose buffers are float64."""
 
-    def __init__(self, ctx, bufferSize, upCoeff):
+    def __init__(self, ctx, bufferSize, upCoeff, dtype=np.float32):
         self.ctx, self.bufferSize, self.upCoeff = ctx, bufferSize, upCoeff
+        self.dtype = np.dtype(dtype)
+        self.f64 = self.dtype == np.float64
         h = C.c_void_p(0)
-        ctx.call("tsdr_resampler_init", bufferSize, upCoeff, C.byref(h))
+        ctx.call("tsdr_resampler_init_f64" if self.f64 else "tsdr_resampler_init", bufferSize, upCoeff, C.byref(h))
         self.h = h.value
 
     def __call__(self, out, inp):
         if not (isinstance(out, np.ndarray) and isinstance(inp, np.ndarray)):
             raise AssertionError("numpy arrays expected")
-        if out.dtype != np.float32 or inp.dtype != np.float32:
+        if self.f64:
+            if out.dtype != np.float64 or inp.dtype != np.float64:  # Resampler.jl:44
+                raise AssertionError(f"Type of input ({inp.dtype}) should match type used during init (Float64)")
+        elif out.dtype != np.float32 or inp.dtype != np.float32:
             raise AssertionError("Type of input should match type used during init (Float32)")  # Resampler.jl:44
         if inp.size != self.bufferSize:
             raise AssertionError(f"Size of input {inp.size} should match size used during init {self.bufferSize}")  # :47
         if out.size < self.bufferSize * self.upCoeff:
             raise IndexError("out too short")
+        if not out.flags.c_contiguous:
+            raise AssertionError("out must be contiguous")
         x = np.ascontiguousarray(inp)
-        check(self.ctx.h, self.ctx.lib.tsdr_resampler_run(self.h, _ptr(x), x.size, _ptr(out)), "tsdr_resampler_run")
+        fn = "tsdr_resampler_run_f64" if self.f64 else "tsdr_resampler_run"
+        check(self.ctx.h, getattr(self.ctx.lib, fn)(self.h, _ptr(x), x.size, _ptr(out)), fn)
 
     def lpf(self):
         H = np.empty(self.bufferSize * self.upCoeff, np.complex64)
@@ -795,6 +812,6 @@ def calculate_autocorrelation(x, Fs, minDelay, maxDelay, scale="log", *, dtype=N
     return default_context().calculate_autocorrelation(x, Fs, minDelay, maxDelay, scale, dtype=dtype)
 def zoom_autocorr(G, Fs, rate_min=20, rate_max=100): return default_context().zoom_autocorr(G, Fs, rate_min, rate_max)
 def getSpectrum(fs, sig, N=None, *, dtype=None): return default_context().getSpectrum(fs, sig, N, dtype=dtype)
-def getWelch(fe, sig, sizeFFT=1024): return default_context().getWelch(fe, sig, sizeFFT)
-def getWaterfall(fe, sig, sizeFFT=1024): return default_context().getWaterfall(fe, sig, sizeFFT)
+def getWelch(fe, sig, sizeFFT=1024, *, dtype=None): return default_context().getWelch(fe, sig, sizeFFT, dtype=dtype)
+def getWaterfall(fe, sig, sizeFFT=1024, *, dtype=None): return default_context().getWaterfall(fe, sig, sizeFFT, dtype=dtype)
 def vsync(image, sync): return sync.vsync(image)

@@ -119,6 +119,10 @@ struct tsdr_ctx {
   std::map<int, tsdr::TwTable> tw;
   std::map<unsigned, float2 *> twg;  // mixed-radix FFT: W_{R*Rn}^(col*k) tables of the last strided pass, key R << 16 | Rn
   std::map<size_t, tsdr::BluesteinPlan> blu;
+  // Float64 segment / resampler transforms (spectra64.hip): W_n^e in f64, built once per length n -- e < n for n <= 4096, else
+  // two levels (W_n^j, j < 4096, then W_n^(4096 h)); Bluestein chirp + transformed wrapped conj chirp per length
+  std::map<size_t, double2 *> tw64;
+  std::map<size_t, double2 *> blu64;
   // tsdr_argmax_d: two device key slots (each launch clears the other one) and a pinned host word for the readback
   unsigned long long *amax_keys = nullptr, *amax_host = nullptr, *amax_host_dev = nullptr;
   int amax_slot = 0;

@@ -244,6 +244,8 @@ void tsdr_destroy(tsdr_ctx *ctx) {
   for (auto &kv : ctx->tw) { (void)hipFree(kv.second.lo); (void)hipFree(kv.second.hi); }
   for (auto &kv : ctx->twg) (void)hipFree(kv.second);
   for (auto &kv : ctx->blu) { (void)hipFree(kv.second.chirp); (void)hipFree(kv.second.bfft); }
+  for (auto &kv : ctx->tw64) (void)hipFree(kv.second);
+  for (auto &kv : ctx->blu64) (void)hipFree(kv.second);
   if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
 }

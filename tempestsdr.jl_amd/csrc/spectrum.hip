@@ -6,16 +6,7 @@
 #include <cstring>
 
 #include "fft_dev.h"
-
-struct tsdr_resampler {
-  tsdr_ctx *ctx;
-  size_t bufferSize, sizeFFT;
-  int up;
-  double2 *H = nullptr;    // initLPF's H: ComplexF64 as in the reference (the Float64 window promotes it, Resampler.jl:93-97)
-  double2 *Hs = nullptr;   // (H[k] + conj H[N-k]) / 2 for k <= N/2: the filter of the real part (half-size route), or null
-  float2 *work = nullptr;  // containerFFT / inFFT / outFFT, device
-  double2 *tw = nullptr;   // half-size route: {cos, sin}(2 pi e / N) for e < 1024, then for e = 1024 h (h <= N / 2048 + 1)
-};
+#include "resampler_state.h"
 
 namespace tsdr {
 
@@ -653,17 +644,23 @@ static inline double lpf_phase(size_t k, const LpfPhase &st) {
   return a + b;
 }
 
-int tsdr_resampler_init(tsdr_ctx *ctx, size_t bufferSize, int upCoeff, tsdr_resampler **out) {
+}  // extern "C"
+namespace tsdr {
+// init_resampler(T, bufferSize, upCoeff) for T = Float32 (f64 false) or Float64: the same H either way (initLPF builds it in f64
+// for both); the containerFFT buffers of the kind asked for
+int resampler_init_kind(tsdr_ctx *ctx, size_t bufferSize, int upCoeff, bool f64, tsdr_resampler **out) {
   if (!ctx || !out) return TSDR_EINVAL;
   *out = nullptr;
   if (bufferSize == 0 || upCoeff < 1) return set_err(ctx, TSDR_EINVAL, "init_resampler: bufferSize and upCoeff must be positive");
   const size_t N = bufferSize * (size_t)upCoeff;
   if (N >= (size_t(1) << 30)) return set_err(ctx, TSDR_EINVAL, "init_resampler: sizeFFT too large");
   tsdr_resampler *r = new tsdr_resampler();
-  r->ctx = ctx; r->bufferSize = bufferSize; r->up = upCoeff; r->sizeFFT = N;
+  r->ctx = ctx; r->bufferSize = bufferSize; r->up = upCoeff; r->sizeFFT = N; r->f64 = f64;
   double2 *scratch = nullptr;
-  const bool half = (bufferSize % 2 == 0) && bufferSize >= 4;
-  if (hipMalloc((void **)&r->H, N * sizeof(double2)) != hipSuccess || hipMalloc((void **)&r->work, N * sizeof(float2)) != hipSuccess ||
+  const bool half = !f64 && (bufferSize % 2 == 0) && bufferSize >= 4;
+  if (hipMalloc((void **)&r->H, N * sizeof(double2)) != hipSuccess ||
+      (!f64 && hipMalloc((void **)&r->work, N * sizeof(float2)) != hipSuccess) ||
+      (f64 && (hipMalloc((void **)&r->A64, N * sizeof(double2)) != hipSuccess || hipMalloc((void **)&r->B64, N * sizeof(double2)) != hipSuccess)) ||
       hipMalloc((void **)&scratch, N * sizeof(double2)) != hipSuccess ||
       (half && hipMalloc((void **)&r->Hs, (N / 2 + 1) * sizeof(double2)) != hipSuccess)) {
     (void)hipFree(scratch);
@@ -716,10 +713,17 @@ int tsdr_resampler_init(tsdr_ctx *ctx, size_t bufferSize, int upCoeff, tsdr_resa
   *out = r;
   return TSDR_OK;
 }
+}  // namespace tsdr
+extern "C" {
+
+int tsdr_resampler_init(tsdr_ctx *ctx, size_t bufferSize, int upCoeff, tsdr_resampler **out) {
+  return resampler_init_kind(ctx, bufferSize, upCoeff, false, out);
+}
 
 int tsdr_resampler_run_d(tsdr_resampler *r, const float *in, size_t n_in, float *out) {
   if (!r || !in || !out) return TSDR_EINVAL;
   tsdr_ctx *ctx = r->ctx;
+  if (r->f64) return set_err(ctx, TSDR_EINVAL, "resampler!: a Float64 resampler takes Float64 buffers (tsdr_resampler_run_f64)");
   if (n_in != r->bufferSize) return set_err(ctx, TSDR_EINVAL, "Size of input %zu should match size used during init %zu", n_in, r->bufferSize);
   const size_t N = r->sizeFFT;
   if (N == 4096) {  // one workgroup, one launch
@@ -774,6 +778,7 @@ int tsdr_resampler_run_d(tsdr_resampler *r, const float *in, size_t n_in, float 
 
 int tsdr_resampler_run(tsdr_resampler *r, const float *in, size_t n_in, float *out) {
   if (!r) return TSDR_EINVAL;
+  if (r->f64) return set_err(r->ctx, TSDR_EINVAL, "resampler!: a Float64 resampler takes Float64 buffers (tsdr_resampler_run_f64)");
   if (n_in != r->bufferSize) return set_err(r->ctx, TSDR_EINVAL, "Size of input %zu should match size used during init %zu", n_in, r->bufferSize);
   return host_map(r->ctx, in, n_in * 4, out, r->sizeFFT * 4,
                   [&](void *i, void *o) { return tsdr_resampler_run_d(r, (const float *)i, n_in, (float *)o); });
@@ -782,7 +787,8 @@ int tsdr_resampler_run(tsdr_resampler *r, const float *in, size_t n_in, float *o
 int tsdr_resampler_lpf(tsdr_resampler *r, float *H_host) {
   if (!r || !H_host) return TSDR_EINVAL;
   tsdr_ctx *ctx = r->ctx;
-  float2 *tmp = (float2 *)ctx->scratch(WS_FFT_A, r->sizeFFT * sizeof(float2));
+  // (a Float64 resampler narrows in its own buffer: no f64 object moves a workspace of the f32 paths)
+  float2 *tmp = r->f64 ? (float2 *)r->A64 : (float2 *)ctx->scratch(WS_FFT_A, r->sizeFFT * sizeof(float2));
   if (!tmp) return TSDR_ENOMEM;
   TSDR_LAUNCH(ctx, "lpf_c32", k_c64_to_c32, dim3(stream_grid(ctx, r->sizeFFT)), dim3(256), 0, (const double2 *)r->H, r->sizeFFT, tmp);
   TSDR_HIP(ctx, hipMemcpyAsync(H_host, tmp, r->sizeFFT * sizeof(float2), hipMemcpyDeviceToHost, ctx->stream));
@@ -824,6 +830,8 @@ void tsdr_resampler_free(tsdr_resampler *r) {
   if (r->Hs) (void)hipFree(r->Hs);
   if (r->work) (void)hipFree(r->work);
   if (r->tw) (void)hipFree(r->tw);
+  if (r->A64) (void)hipFree(r->A64);
+  if (r->B64) (void)hipFree(r->B64);
   delete r;
 }
 

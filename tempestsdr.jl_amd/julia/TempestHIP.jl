@@ -163,7 +163,8 @@ function hip_imresize(image::AbstractMatrix{Float64}, sz::Tuple{Integer,Integer}
     return out
 end
 function init_resampler(T::Type, bufferSize::Int, upCoeff::Int)  # Resampler.jl:26-62
-    T == Float32 || throw(AssertionError("the HIP path implements Float32 resamplers"))
+    T == Float32 || T == Float64 || throw(AssertionError("the HIP path implements Float32 and Float64 resamplers"))
+    T == Float64 && return _init_resampler64(bufferSize, upCoeff)
     c = ctx(); r = Ref{Ptr{Cvoid}}(C_NULL)
     check(c, ccall((:tsdr_resampler_init, LIB), Cint, (Ptr{Cvoid}, Csize_t, Cint, Ptr{Ptr{Cvoid}}), c.h, bufferSize, upCoeff, r), "init_resampler")
     h = r[]
@@ -176,6 +177,24 @@ function init_resampler(T::Type, bufferSize::Int, upCoeff::Int)  # Resampler.jl:
         @assert T == T2 "Type of input ($T2) should match type used during init ($T)"             # :44
         @assert length(in) == bufferSize "Size of input $(length(in)) should match size used during init $bufferSize"   # :47
         check(c, ccall((:tsdr_resampler_run, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}, Csize_t, Ptr{Float32}), h, in, length(in), out), "resampler!")
+    end
+    return resampler!
+end
+# init_resampler(Float64, ...): the same H; containerFFT in ComplexF64 (tsdr_resampler_init_f64 / tsdr_resampler_run_f64)
+function _init_resampler64(bufferSize::Int, upCoeff::Int)
+    T = Float64
+    c = ctx(); r = Ref{Ptr{Cvoid}}(C_NULL)
+    check(c, ccall((:tsdr_resampler_init_f64, LIB), Cint, (Ptr{Cvoid}, Csize_t, Cint, Ptr{Ptr{Cvoid}}), c.h, bufferSize, upCoeff, r), "init_resampler")
+    h = r[]
+    keep = Ref(c)
+    finalizer(keep) do k
+        k[].h != C_NULL && ccall((:tsdr_resampler_free, LIB), Cvoid, (Ptr{Cvoid},), h)
+    end
+    function resampler!(out::AbstractVector{T2}, in::AbstractVector{T2}) where T2
+        keep[] === c || error("unreachable")
+        @assert T == T2 "Type of input ($T2) should match type used during init ($T)"             # :44
+        @assert length(in) == bufferSize "Size of input $(length(in)) should match size used during init $bufferSize"   # :47
+        check(c, ccall((:tsdr_resampler_run_f64, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Csize_t, Ptr{Float64}), h, in, length(in), out), "resampler!")
     end
     return resampler!
 end
@@ -237,7 +256,7 @@ function getSpectrum(fs, sig::AbstractVector{<:Union{Float64,ComplexF64}}; N = n
     return (collect(((0:N-1) ./ N .- 0.5) * fs), y)
 end
 getSpectrum(sig) = getSpectrum(1, sig)
-_raw32(sig::AbstractVector{<:Union{Float32,ComplexF32}}) = _raw(sig)   # getWelch / getWaterfall stay Float32 / ComplexF32
+_raw32(sig::AbstractVector{<:Union{Float32,ComplexF32}}) = _raw(sig)   # the Float32 / ComplexF32 getWelch / getWaterfall; Float64 below
 function getWelch(fe, sig; sizeFFT = 1024)                                   # GetSpectrum.jl:36-52
     a, cplx = _raw32(sig); y = Vector{Float32}(undef, sizeFFT); c = ctx()
     check(c, ccall((:tsdr_welch, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Csize_t, Csize_t, Cint, Ptr{Float32}),
@@ -248,6 +267,20 @@ function getWaterfall(fe, sig; sizeFFT = 1024)                               # G
     a, cplx = _raw32(sig); nbSeg = length(a) ÷ sizeFFT
     m = Matrix{Float64}(undef, sizeFFT, nbSeg); c = ctx()
     check(c, ccall((:tsdr_waterfall, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Csize_t, Csize_t, Ptr{Float64}),
+                   c.h, a, cplx, length(a), sizeFFT, m), "getWaterfall")
+    return ((0:nbSeg-1) * (sizeFFT / fe), collect(((0:sizeFFT-1) ./ sizeFFT .- 0.5) .* fe), m)
+end
+# Float64 / ComplexF64 (a :double capture): the `_f64` entry points, Float64 out
+function getWelch(fe, sig::AbstractVector{<:Union{Float64,ComplexF64}}; sizeFFT = 1024)
+    a, cplx = _raw(sig); y = Vector{Float64}(undef, sizeFFT); c = ctx()
+    check(c, ccall((:tsdr_welch_f64, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Csize_t, Csize_t, Cint, Ptr{Float64}),
+                   c.h, a, cplx, length(a), sizeFFT, 0, y), "getWelch")
+    return (collect(((0:sizeFFT-1) ./ sizeFFT .- 0.5) * fe), y)
+end
+function getWaterfall(fe, sig::AbstractVector{<:Union{Float64,ComplexF64}}; sizeFFT = 1024)
+    a, cplx = _raw(sig); nbSeg = length(a) ÷ sizeFFT
+    m = Matrix{Float64}(undef, sizeFFT, nbSeg); c = ctx()
+    check(c, ccall((:tsdr_waterfall_f64, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Csize_t, Csize_t, Ptr{Float64}),
                    c.h, a, cplx, length(a), sizeFFT, m), "getWaterfall")
     return ((0:nbSeg-1) * (sizeFFT / fe), collect(((0:sizeFFT-1) ./ sizeFFT .- 0.5) .* fe), m)
 end

@@ -106,6 +106,32 @@ for cplx in (0, 1):
     row("spectrum_d", f"N=80000 {'complex' if cplx else 'real'}", timed(lambda: chk(L.tsdr_spectrum_f64_d(h, q64, cplx, N, 0, y64))),
         timed(lambda: chk(L.tsdr_spectrum_d(h, q32, cplx, N, 0, y32))))
 
+# getWelch / getWaterfall on a C2 capture (1e7 ComplexF64 samples: 160 MB read), the resampler at test_resampler.jl's size and
+# at 1e6 x 4.  Bytes are the algorithmic ones: the input once, the output once.
+n = 10_000_000
+for N in (1024, 1000):
+    y64, y32 = V(ctx.dev_alloc(8 * N)), V(ctx.dev_alloc(4 * N))
+    t64 = timed(lambda: chk(L.tsdr_welch_f64_d(h, z64, 1, n, N, 0, y64)))
+    t32 = timed(lambda: chk(L.tsdr_welch_d(h, z32, 1, n, N, 0, y32)))
+    row("welch_d", f"1e7 complex, sizeFFT {N}", t64, t32, f"f64 {16 * n / (t64 * 1e-6) / 1e12:.2f} TB/s")
+nw = 3_000_000
+for N in (1024, 1000):
+    m64 = V(ctx.dev_alloc(8 * nw))
+    t64 = timed(lambda: chk(L.tsdr_waterfall_f64_d(h, z64, 1, nw, N, m64)))
+    t32 = timed(lambda: chk(L.tsdr_waterfall_d(h, z32, 1, nw, N, m64)))
+    row("waterfall_d", f"3e6 complex, sizeFFT {N}", t64, t32, f"f64 {(16 + 8) * nw / (t64 * 1e-6) / 1e12:.2f} TB/s")
+for bs, up in [(1024, 4), (1_000_000, 4), (1000, 4), (999, 3)]:
+    r64, r32 = C.c_void_p(0), C.c_void_p(0)
+    chk(L.tsdr_resampler_init_f64(h, bs, up, C.byref(r64)))
+    chk(L.tsdr_resampler_init(h, bs, up, C.byref(r32)))
+    i64, i32 = dev(rng.standard_normal(bs)), dev(rng.standard_normal(bs).astype(np.float32))
+    o64, o32 = V(ctx.dev_alloc(8 * bs * up)), V(ctx.dev_alloc(4 * bs * up))
+    t64 = timed(lambda: chk(L.tsdr_resampler_run_f64_d(r64, i64, bs, o64)))
+    t32 = timed(lambda: chk(L.tsdr_resampler_run_d(r32, i32, bs, o32)))
+    row("resampler_run_d", f"({bs}, {up})", t64, t32)
+    L.tsdr_resampler_free(r64)
+    L.tsdr_resampler_free(r32)
+
 info = ctx.device_info()
 print(json.dumps({"device": info["name"], "reps": args.reps, "rows": rows}))
 if args.json:
