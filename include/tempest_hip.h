@@ -243,6 +243,23 @@ int tsdr_autocorr_iq_d(tsdr_ctx *ctx, const float *iq, size_t len, double Fs, do
  * over them).  *idx is 0-based inside the window, first maximum, NaN maximal; blocking like tsdr_argmax_d. */
 int tsdr_autocorr_search_d(tsdr_ctx *ctx, const float *x, int is_iq, size_t len, double Fs, double minDelay, double maxDelay,
                            int log_scale, float *out, size_t *n_out, size_t win_lo, size_t win_cnt, size_t *idx, float *val);
+/* IQ sample formats of the generic entry points (tsdr_frames_iq_d, tsdr_frames_submit_iq_d, tsdr_autocorr_search_iq_d).
+ * One conversion rule, the same in every kernel that reads IQ, with ONE rounding per component (the product):
+ *   TSDR_IQ_CF32  float re, float im (8 bytes)      the value itself; `scale` is ignored
+ *   TSDR_IQ_SC16  int16 I, int16 Q   (4 bytes)      ComplexF32(f32(I) * scale, f32(Q) * scale)
+ *   TSDR_IQ_SC8   int8 I, int8 Q     (2 bytes)      ComplexF32(f32(I) * scale, f32(Q) * scale)        HackRF, UHD "sc8"
+ *   TSDR_IQ_UC8   uint8 I, uint8 Q   (2 bytes)      ComplexF32((f32(I) - 127.5f) * scale, (f32(Q) - 127.5f) * scale)   RTL-SDR
+ * The uc8 offset is fixed at 127.5 (not an option); the subtraction is exact in f32.  A buffer expanded on the host with
+ * (q.astype(float32) - offset) * float32(scale) and the raw buffer give identical bits everywhere. */
+enum { TSDR_IQ_CF32 = 0, TSDR_IQ_SC16 = 1, TSDR_IQ_SC8 = 2, TSDR_IQ_UC8 = 3 };
+/* tsdr_autocorr_search_d(is_iq = 1) reading `len` IQ samples of format iq_fmt on the device as they are stored: the first
+ * pass's loader converts (rule above) and forms abs2; the transform is the one ComplexF32 input takes for the same n, and
+ * the lag vector, idx and val equal those of the expanded samples bit for bit.  Integer formats need a 16-byte aligned iq
+ * (what tsdr_ring_take_d and hipMalloc hand out), TSDR_IQ_CF32 behaves as tsdr_autocorr_search_d; an unknown format or a
+ * misaligned buffer is TSDR_EINVAL. */
+int tsdr_autocorr_search_iq_d(tsdr_ctx *ctx, const void *iq, int iq_fmt, float scale, size_t len, double Fs, double minDelay,
+                              double maxDelay, int log_scale, float *out, size_t *n_out, size_t win_lo, size_t win_cnt, size_t *idx,
+                              float *val);
 /* multi-GPU building block: partial circular autocorrelation
  *   part[k] = sum_{m in [m0, m0+cnt)} x[m] * x[(m+k) mod n],  k = 0..n_lags-1
  * of the length-n sequence x (device, real f32; is_iq!=0: x = abs2 of complex IQ).
@@ -426,6 +443,18 @@ int tsdr_frames_sc16_d(tsdr_ctx *ctx, tsdr_sync *sync, const int16_t *iq, float 
 int tsdr_frames_submit_sc16_d(tsdr_ctx *ctx, tsdr_sync *sync, const int16_t *iq, float scale, size_t nEch, size_t S, int y_t,
                               int x_t, float alpha, int do_align, float *imageOut_state, float *frames_out, float *raster_out,
                               int *sync_idx, int *n_frames);
+/* The same for any format (TSDR_IQ_*, above): iq = nEch samples of that format on the device, converted in the kernels'
+ * loaders and never expanded in HBM (8-bit: a quarter of ComplexF32's bytes; tsdr_ring fmt 4 / 6).  TSDR_IQ_CF32 is
+ * tsdr_frames_d / tsdr_frames_submit_d (scale ignored), TSDR_IQ_SC16 the _sc16_d calls.  iq needs the alignment of one
+ * sample only (2 bytes for the 8-bit formats, so a call may start at any sample of a larger buffer).  An unknown format or
+ * a base not aligned to one sample is TSDR_EINVAL.  Results are those of the ComplexF32 entry points on the converted
+ * samples, bit for bit. */
+int tsdr_frames_iq_d(tsdr_ctx *ctx, tsdr_sync *sync, const void *iq, int iq_fmt, float scale, size_t nEch, size_t S, int y_t, int x_t,
+                     float alpha, int do_align, float *imageOut_state, float *frames_out, float *raster_out, int *sync_idx,
+                     int *n_frames);
+int tsdr_frames_submit_iq_d(tsdr_ctx *ctx, tsdr_sync *sync, const void *iq, int iq_fmt, float scale, size_t nEch, size_t S, int y_t,
+                            int x_t, float alpha, int do_align, float *imageOut_state, float *frames_out, float *raster_out,
+                            int *sync_idx, int *n_frames);
 /* what the pipeline measured on this context (host-side, no synchronisation): *trials_left = candidate arrangements still to
  * be timed for the current configuration (0: settled, or nothing is measured); *chosen = index of the arrangement in use
  * (-1 while measuring); ms_per_buffer[c] = mean interval between the tails of successive buffers under candidate c (0: not
@@ -442,7 +471,10 @@ int tsdr_frames_pipeline_info(tsdr_ctx *ctx, int *trials_left, int *chosen, floa
  * fmt 0: ComplexF32 slots (what recv! returns); fmt 1: interleaved int16 I/Q as SDR hardware delivers it (half
  * the PCIe bytes), expanded on the device to ComplexF32 * scale; fmt 2: int16 slots that STAY int16 on the device --
  * tsdr_ring_take_d then hands out nEch int16 pairs (cast the pointer) for tsdr_frames_sc16_d / _submit_sc16_d with the
- * same scale, and nothing expands them.  Counters as print_summary (:333-341). */
+ * same scale, and nothing expands them.  8-bit I/Q (a quarter of the PCIe bytes, 2 bytes per sample; conversion rule at
+ * TSDR_IQ_*): fmt 3: int8 pairs ("sc8") expanded on the device to ComplexF32 with the same product as fmt 1; fmt 4: int8
+ * pairs that stay as they are, for tsdr_frames_iq_d / _submit_iq_d / tsdr_autocorr_search_iq_d(TSDR_IQ_SC8); fmt 5: uint8
+ * pairs ("uc8") expanded; fmt 6: uint8 pairs raw (TSDR_IQ_UC8).  Counters as print_summary (:333-341). */
 typedef struct tsdr_ring tsdr_ring;
 int tsdr_ring_create(tsdr_ctx *ctx, size_t nEch, int depth, int fmt, float scale, tsdr_ring **out);
 void tsdr_ring_free(tsdr_ring *r);

@@ -90,6 +90,8 @@ _SIGS = {
     "tsdr_autocorr_iq_d": (C.c_int, [vp, vp, c_sz, C.c_double, C.c_double, C.c_double, C.c_int, vp, c_szp]),
     "tsdr_autocorr_search_d": (C.c_int, [vp, vp, C.c_int, c_sz, C.c_double, C.c_double, C.c_double, C.c_int, vp, c_szp, c_sz, c_sz,
                                          c_szp, c_f]),
+    "tsdr_autocorr_search_iq_d": (C.c_int, [vp, vp, C.c_int, C.c_float, c_sz, C.c_double, C.c_double, C.c_double, C.c_int, vp, c_szp,
+                                            c_sz, c_sz, c_szp, c_f]),
     "tsdr_autocorr_partial_d": (C.c_int, [vp, vp, C.c_int, c_sz, c_sz, c_sz, c_sz, vp]),
     "tsdr_autocorr_finish_d": (C.c_int, [vp, vp, c_sz, c_sz, C.c_int, vp]),
     "tsdr_zoom_bounds": (C.c_int, [c_sz, C.c_double, C.c_double, C.c_double, c_szp, c_szp]),
@@ -156,6 +158,8 @@ _SIGS = {
     "tsdr_frames_flush": (C.c_int, [vp]),
     "tsdr_frames_sc16_d": (C.c_int, [vp, vp, vp, C.c_float, c_sz, c_sz, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, vp, vp, c_i]),
     "tsdr_frames_submit_sc16_d": (C.c_int, [vp, vp, vp, C.c_float, c_sz, c_sz, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, vp, vp, c_i]),
+    "tsdr_frames_iq_d": (C.c_int, [vp, vp, vp, C.c_int, C.c_float, c_sz, c_sz, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, vp, vp, c_i]),
+    "tsdr_frames_submit_iq_d": (C.c_int, [vp, vp, vp, C.c_int, C.c_float, c_sz, c_sz, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, vp, vp, c_i]),
     "tsdr_frames_pipeline_info": (C.c_int, [vp, c_i, c_i, c_f, C.c_int, C.c_char_p, c_sz]),
     "tsdr_ring_create": (C.c_int, [vp, c_sz, C.c_int, C.c_int, C.c_float, C.POINTER(vp)]),
     "tsdr_ring_free": (None, [vp]),

@@ -325,29 +325,61 @@ class Context:
         lags = np.arange(0, index_max - index_min + 1, dtype=np.float64) * (1.0 / Fs)
         return out[: n_out.value], lags
 
-    def autocorr_search(self, sig, Fs, minDelay, maxDelay, rate_min=50, rate_max=90, scale="log"):
+    def autocorr_search(self, sig, Fs, minDelay, maxDelay, rate_min=50, rate_max=90, scale="log", *, iq_fmt=None, iq_scale=1.0,
+                        n_samples=None):
         """calculate_autocorrelation + zoom_autocorr + findmax as ONE library call (tsdr_autocorr_search_d; GUI.jl:73-81).
         sig: real power samples, or complex IQ whose abs2 is formed on the fly (GUI.jl:70).
+        iq_fmt "sc16" / "sc8" / "uc8" (keyword only): sig is integer IQ as the hardware stores it -- an int16 / int8 / uint8
+        array of 2*n interleaved components (strict about the dtype), or the integer address of such a buffer on the device
+        (16-byte aligned, e.g. from StagingRing.take_d) with n_samples = n; every sample is converted with iq_scale by the first
+        pass's loader (tsdr_autocorr_search_iq_d).
         -> (G, pos, val): the lag vector, the 0-based findmax position inside the zoom window, its value."""
-        a = np.ascontiguousarray(sig)
-        is_iq = int(np.iscomplexobj(a))
-        a = a.astype(np.complex64 if is_iq else np.float32, copy=False)
+        d_in, own, code = None, True, 0
+        if iq_fmt is None:
+            a = np.ascontiguousarray(sig)
+            is_iq = int(np.iscomplexobj(a))
+            a = a.astype(np.complex64 if is_iq else np.float32, copy=False)
+            n = a.size
+        else:
+            code = iq_fmt_code(iq_fmt)
+            if code == 0:
+                raise AssertionError("iq_fmt is for integer IQ (sc16, sc8, uc8); ComplexF32 goes in as a complex array")
+            if isinstance(sig, (int, np.integer)) and not isinstance(sig, bool):
+                if n_samples is None or int(n_samples) <= 0:
+                    raise AssertionError("a device address needs n_samples")
+                d_in, own, n = int(sig), False, int(n_samples)
+            else:
+                want = {1: np.int16, 2: np.int8, 3: np.uint8}[code]
+                if not isinstance(sig, np.ndarray) or sig.dtype != want or sig.size % 2:
+                    raise AssertionError(f"iq_fmt {iq_fmt!r} takes an {np.dtype(want).name} array of 2*n interleaved components")
+                a = np.ascontiguousarray(sig)
+                n = a.size // 2
         index_min = 1 + int(np.round(minDelay * Fs))
         index_max = int(np.round(maxDelay * Fs))
         cnt = max(index_max - index_min + 1, 0)
         pmin, pmax = C.c_size_t(0), C.c_size_t(0)
         check(self.h, self.lib.tsdr_zoom_bounds(cnt, float(Fs), float(rate_min), float(rate_max), C.byref(pmin), C.byref(pmax)),
               "tsdr_zoom_bounds")
-        d_in, d_out = self.upload(a), self.dev_alloc(max(cnt, 1) * 4)
+        if d_in is None:
+            d_in = self.upload(a)
+        d_out = None
         try:
+            d_out = self.dev_alloc(max(cnt, 1) * 4)
             n_out, idx, val = C.c_size_t(0), C.c_size_t(0), C.c_float(0)
-            self.call("tsdr_autocorr_search_d", C.c_void_p(d_in), is_iq, a.size, float(Fs), float(minDelay), float(maxDelay),
-                      1 if scale == "log" else 0, C.c_void_p(d_out), C.byref(n_out), int(pmin.value - 1),
-                      int(pmax.value - pmin.value + 1), C.byref(idx), C.byref(val))
+            if iq_fmt is None:
+                self.call("tsdr_autocorr_search_d", C.c_void_p(d_in), is_iq, n, float(Fs), float(minDelay), float(maxDelay),
+                          1 if scale == "log" else 0, C.c_void_p(d_out), C.byref(n_out), int(pmin.value - 1),
+                          int(pmax.value - pmin.value + 1), C.byref(idx), C.byref(val))
+            else:
+                self.call("tsdr_autocorr_search_iq_d", C.c_void_p(d_in), code, C.c_float(iq_scale), n, float(Fs), float(minDelay),
+                          float(maxDelay), 1 if scale == "log" else 0, C.c_void_p(d_out), C.byref(n_out), int(pmin.value - 1),
+                          int(pmax.value - pmin.value + 1), C.byref(idx), C.byref(val))
             G = self.download(d_out, (n_out.value,), np.float32)
         finally:
-            self.dev_free(d_in)
-            self.dev_free(d_out)
+            if own:
+                self.dev_free(d_in)
+            if d_out is not None:
+                self.dev_free(d_out)
         return G, int(idx.value), float(val.value)
 
     def zoom_autocorr(self, G, Fs, rate_min=20, rate_max=100):
@@ -487,6 +519,47 @@ def frames_submit_d(ctx, sync, iq, nEch, S, y_t, x_t, alpha, do_align, state, fr
     return n.value
 
 
+# IQ sample formats of the generic entry points (TSDR_IQ_* of tempest_hip.h): code, numpy dtype of the stored components,
+# the offset subtracted before the one product by scale (uc8: 127.5, fixed)
+IQ_FORMATS = {"cf32": (0, np.float32, 0.0), "sc16": (1, np.int16, 0.0), "sc8": (2, np.int8, 0.0), "uc8": (3, np.uint8, 127.5)}
+
+
+def iq_fmt_code(fmt):
+    """"cf32" / "sc16" / "sc8" / "uc8" (or the TSDR_IQ_* integer) -> TSDR_IQ_* code; AssertionError for anything else"""
+    if isinstance(fmt, str) and fmt in IQ_FORMATS:
+        return IQ_FORMATS[fmt][0]
+    if isinstance(fmt, (int, np.integer)) and not isinstance(fmt, bool) and 0 <= int(fmt) <= 3:
+        return int(fmt)
+    raise AssertionError(f"unknown IQ format {fmt!r} (cf32, sc16, sc8, uc8)")
+
+
+def expand_iq(q, fmt, scale):
+    """The conversion rule of the integer IQ formats on the host: interleaved components (2*n values of the format's dtype) ->
+    complex64[n], every component (f32(code) - offset) * f32(scale) with the product as the one rounding.  What every loader
+    of the library forms from the raw buffer, bit for bit."""
+    name = fmt if isinstance(fmt, str) else {v[0]: k for k, v in IQ_FORMATS.items()}[iq_fmt_code(fmt)]
+    _, dt, off = IQ_FORMATS[name]
+    a = np.ascontiguousarray(q)
+    if a.dtype != dt or a.size % 2:
+        raise AssertionError(f"{name} IQ is an even number of {np.dtype(dt).name} values, got {a.dtype} x {a.size}")
+    if name == "cf32":
+        return a.view(np.complex64)
+    v = (a.astype(np.float32) - np.float32(off)) * np.float32(scale)
+    return v.view(np.complex64)
+
+
+def frames_iq_d(ctx, sync, iq, fmt, scale, nEch, S, y_t, x_t, alpha, do_align, state, frames_out=None, raster_out=None, sync_idx=None,
+                submit=False):
+    """frames_d / frames_submit_d on a device buffer of nEch samples of format `fmt` ("cf32", "sc16", "sc8", "uc8"): integer
+    samples are converted in the kernels' loaders (tsdr_frames_iq_d / tsdr_frames_submit_iq_d); the buffer is never expanded."""
+    code = iq_fmt_code(fmt)
+    n = C.c_int(0)
+    ctx.call("tsdr_frames_submit_iq_d" if submit else "tsdr_frames_iq_d", C.c_void_p(sync.h if sync is not None else 0), _ptr(iq),
+             code, C.c_float(scale), int(nEch), int(S), int(y_t), int(x_t), C.c_float(alpha), int(bool(do_align)), _ptr(state),
+             _ptr(frames_out), _ptr(raster_out), _ptr(sync_idx), C.byref(n))
+    return n.value
+
+
 def frames_sc16_d(ctx, sync, iq, scale, nEch, S, y_t, x_t, alpha, do_align, state, frames_out=None, raster_out=None, sync_idx=None,
                   submit=False):
     """frames_d / frames_submit_d on a device buffer of nEch interleaved int16 (re, im) pairs: every sample is
@@ -618,30 +691,48 @@ class StagingRing:
     """Pinned-host staging ring: the consumer side of AtomicCircularBuffer / recv!(buffer, csdr)
     (AtomicAbstractSDRs.jl:64-190, 320-322) with the buffer landing on the device.
     fmt "cf32": ComplexF32 slots; "sc16": interleaved int16 I/Q, expanded on the device to ComplexF32 * scale; "sc16raw": int16
-    slots that stay int16 on the device (take_d hands out int16 pairs for frames_sc16_d with the same scale)."""
+    slots that stay int16 on the device (take_d hands out int16 pairs for frames_sc16_d with the same scale).  8-bit I/Q, two
+    bytes per sample: "sc8" (int8 pairs) / "uc8" (uint8 pairs around 127.5) expanded on the device, "sc8raw" / "uc8raw" handed
+    out as stored, for frames_iq_d and autocorr_search(iq_fmt=...) with the same scale."""
+    FORMATS = {"cf32": 0, "sc16": 1, "sc16raw": 2, "sc8": 3, "sc8raw": 4, "uc8": 5, "uc8raw": 6}
+    SLOT_DTYPES = {"cf32": (np.float32, np.complex64), "sc16": (np.int16,), "sc16raw": (np.int16,), "sc8": (np.int8,),
+                   "sc8raw": (np.int8,), "uc8": (np.uint8,), "uc8raw": (np.uint8,)}
 
     def __init__(self, ctx, nEch, depth=16, fmt="cf32", scale=1.0):
+        if fmt not in self.FORMATS:
+            raise AssertionError(f"unknown ring format {fmt!r} ({', '.join(self.FORMATS)})")
         self.ctx, self.nEch, self.depth, self.fmt = ctx, int(nEch), int(depth), fmt
+        self.scale = float(scale)
+        self.sample_bytes = 8 if fmt == "cf32" else 4 if fmt in ("sc16", "sc16raw") else 2
+        self.h = None
         h = C.c_void_p(0)
-        ctx.call("tsdr_ring_create", self.nEch, self.depth, {"cf32": 0, "sc16": 1, "sc16raw": 2}[fmt], C.c_float(scale), C.byref(h))
+        ctx.call("tsdr_ring_create", self.nEch, self.depth, self.FORMATS[fmt], C.c_float(scale), C.byref(h))
         self.h = h.value
+
+    @property
+    def iq_fmt(self):
+        """format of the buffers take_d hands out: "cf32" for every expanding ring, else "sc16" / "sc8" / "uc8" """
+        return self.fmt[:-3] if self.fmt.endswith("raw") else "cf32"
 
     def _chk(self, rc, what):
         check(self.ctx.h, rc, what)
 
     def put(self, buf):
-        """circ_put!: copy one buffer (complex64[nEch] or int16[2*nEch]) into the ring; never waits for the consumer."""
+        """circ_put!: copy one buffer (complex64[nEch], or int16 / int8 / uint8 [2*nEch] for the integer formats) into the
+        ring; never waits for the consumer."""
         a = np.ascontiguousarray(buf)
-        want = self.nEch * (8 if self.fmt == "cf32" else 4)
+        want = self.nEch * self.sample_bytes
         if a.nbytes != want:
             raise AssertionError(f"ring slot is {want} bytes, got {a.nbytes}")
+        if self.sample_bytes == 2 and a.dtype not in self.SLOT_DTYPES[self.fmt]:   # (int8 and uint8 differ in meaning only)
+            raise AssertionError(f"a {self.fmt} ring takes {np.dtype(self.SLOT_DTYPES[self.fmt][0]).name} components, got {a.dtype}")
         self._chk(self.ctx.lib.tsdr_ring_put(self.h, _ptr(a)), "tsdr_ring_put")
 
     def write_view(self):
         """Zero-copy producer: a numpy view of the pinned slot to fill; publish it with commit()."""
         p = self.ctx.lib.tsdr_ring_write_ptr(self.h)
         n = self.nEch * 2
-        ctype = C.c_float if self.fmt == "cf32" else C.c_int16
+        ctype = {8: C.c_float, 4: C.c_int16}.get(self.sample_bytes, C.c_uint8 if self.fmt.startswith("uc8") else C.c_int8)
         return np.ctypeslib.as_array(C.cast(p, C.POINTER(ctype)), shape=(n,))
 
     def commit(self):

@@ -26,21 +26,33 @@ int get_tw(tsdr_ctx *ctx, int logN, TwTable **out);
 
 __device__ inline float2 cmulf(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
 
-__device__ inline float ld_power(const float *x, int is_iq, size_t i) {
-  if (is_iq) {
+// is_iq: 0 = x is real f32; 1 + TSDR_IQ_* = x is IQ of that format (1: ComplexF32, 2: sc16, 3: sc8, 4: uc8), whose abs2 is the
+// sample -- integer storage converted as the frame loaders do (common.h: ld_iq, one product by `scale`)
+__device__ inline float ld_power(const float *x, int is_iq, size_t i, float scale) {
+  if (is_iq == 1) {
     float2 z = reinterpret_cast<const float2 *>(x)[i];
+    return abs2_c(z.x, z.y);
+  }
+  if (is_iq) {
+    float2 z;
+    if (is_iq == 2) z = cvt_sc16(reinterpret_cast<const short2 *>(x)[i], scale);
+    else if (is_iq == 3) z = cvt_sc8(reinterpret_cast<const unsigned short *>(x)[i], scale);
+    else z = cvt_uc8(reinterpret_cast<const unsigned short *>(x)[i], scale);
     return abs2_c(z.x, z.y);
   }
   return x[i];
 }
+inline int iq_src_mode(int is_iq) {   // the first pass's loader for that input
+  return is_iq == 0 ? SRC_REAL : is_iq == 1 ? SRC_IQPOW : is_iq == 2 ? SRC_IQPOW_SC16 : is_iq == 3 ? SRC_IQPOW_SC8 : SRC_IQPOW_UC8;
+}
 
 // z[j] = x[2j] + i x[2j+1], zero beyond n; Mc complex outputs
 __global__ __launch_bounds__(256) void k_ac_pack(const float *__restrict__ x, int is_iq, size_t n, size_t Mc,
-                                                 float2 *__restrict__ z) {
+                                                 float2 *__restrict__ z, float scale) {
   for (size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x; j < Mc; j += (size_t)gridDim.x * blockDim.x) {
     const size_t i0 = 2 * j;
-    float a = i0 < n ? ld_power(x, is_iq, i0) : 0.f;
-    float b = i0 + 1 < n ? ld_power(x, is_iq, i0 + 1) : 0.f;
+    float a = i0 < n ? ld_power(x, is_iq, i0, scale) : 0.f;
+    float b = i0 + 1 < n ? ld_power(x, is_iq, i0 + 1, scale) : 0.f;
     z[j] = make_float2(a, b);
   }
 }
@@ -95,13 +107,13 @@ __global__ __launch_bounds__(256) void k_ac_finish(const float *__restrict__ cor
 // ---- partial (sharded) correlation --------------------------------------------------------
 // z[j] = u[j] + i v[j]; u = x[m0 .. m0+cnt), v = x[(m0+j) mod n], j < cnt+n_lags-1; zero padded to M
 __global__ __launch_bounds__(256) void k_pc_pack(const float *__restrict__ x, int is_iq, size_t n, size_t m0,
-                                                 size_t cnt, size_t vlen, size_t M, float2 *__restrict__ z) {
+                                                 size_t cnt, size_t vlen, size_t M, float2 *__restrict__ z, float scale) {
   for (size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x; j < M; j += (size_t)gridDim.x * blockDim.x) {
     float u = 0.f, v = 0.f;
     if (j < vlen) {
       size_t idx = m0 + j;
       if (idx >= n) idx %= n;
-      v = ld_power(x, is_iq, idx);
+      v = ld_power(x, is_iq, idx, scale);
       if (j < cnt) u = v;
     }
     z[j] = make_float2(u, v);
@@ -198,7 +210,7 @@ struct AmaxReq {
 
 // shared core: x (real f32, or IQ whose abs2 is taken on the fly), first n samples
 static int autocorr_core(tsdr_ctx *ctx, const float *x, int is_iq, size_t n, size_t k0, size_t cnt, int log_scale,
-                         float *out, AmaxReq *amax = nullptr) {
+                         float *out, AmaxReq *amax = nullptr, float iq_scale = 1.0f) {
   // n = 2*Mc with Mc = 2^a 3^b 5^c (the usual case: decimal sample rates, or a power of two): the circular
   // correlation of length n is transformed natively -- no zero padding, no fold, half the bytes (or less) of the
   // padded route below, which remains for every other n.
@@ -206,6 +218,7 @@ static int autocorr_core(tsdr_ctx *ctx, const float *x, int is_iq, size_t n, siz
   const bool mixed_on = ctx->opt_ac_mixed != 0;
   if ((n & 1) == 0 && n > 1024 && (half_pow2 || (mixed_on && fft_mixed_ok(n / 2))) &&
       (!is_iq || (reinterpret_cast<uintptr_t>(x) & 15u) == 0)) {
+    const int src_mode = iq_src_mode(is_iq);
     const size_t Mc = n / 2;
     float2 *z = (float2 *)ctx->scratch(WS_FFT_A, Mc * sizeof(float2));
     float2 *Z = (float2 *)ctx->scratch(WS_FFT_C, Mc * sizeof(float2));
@@ -226,15 +239,15 @@ static int autocorr_core(tsdr_ctx *ctx, const float *x, int is_iq, size_t n, siz
       // one launch carries the last forward pass, the power spectrum and the first inverse pass when the split allows
       if (ctx->opt_ac_fuse_mid) {
         bool done = false;
-        int rc = fft_mixed_autocorr(ctx, reinterpret_cast<const float2 *>(x), is_iq ? SRC_IQPOW : SRC_REAL, n, Mc, Z, z,
-                                    (float)(0.5 / (double)Mc), (k0 + cnt + 1) / 2, &epi, &done);
+        int rc = fft_mixed_autocorr(ctx, reinterpret_cast<const float2 *>(x), src_mode, n, Mc, Z, z,
+                                    (float)(0.5 / (double)Mc), (k0 + cnt + 1) / 2, &epi, &done, iq_scale);
         if (rc || done) return rc;
       }
-      int rc = fft_mixed(ctx, reinterpret_cast<const float2 *>(x), Z, Mc, 1, -1, 1.0f, is_iq ? SRC_IQPOW : SRC_REAL, n, 0);
+      int rc = fft_mixed(ctx, reinterpret_cast<const float2 *>(x), Z, Mc, 1, -1, 1.0f, src_mode, n, 0, nullptr, nullptr, iq_scale);
       if (rc) return rc;
       return fft_mixed(ctx, Z, z, Mc, 1, +1, (float)(0.5 / (double)Mc), SRC_POWER, Mc, (k0 + cnt + 1) / 2, &epi);
     }
-    int rc = fft_pow2(ctx, reinterpret_cast<const float2 *>(x), Z, ilog2(Mc), 1, -1, 1.0f, is_iq ? SRC_IQPOW : SRC_REAL, n, 0);
+    int rc = fft_pow2(ctx, reinterpret_cast<const float2 *>(x), Z, ilog2(Mc), 1, -1, 1.0f, src_mode, n, 0, nullptr, nullptr, iq_scale);
     if (rc) return rc;
     TSDR_LAUNCH(ctx, "ac_power", k_ac_power, dim3(stream_grid(ctx, Mc / 2 + 1)), dim3(256), 0, Z, Mc, (const float2 *)nullptr,
                 (const float2 *)nullptr, 0, 4.0 / (double)Mc);
@@ -257,9 +270,9 @@ static int autocorr_core(tsdr_ctx *ctx, const float *x, int is_iq, size_t n, siz
   // the fly when asked -- and never reads the zero padding; no separate pack pass, no 33 MB round trip
   const bool aligned = !is_iq || (reinterpret_cast<uintptr_t>(x) & 15u) == 0;  // the IQ loader reads float4 pairs
   if (logM - 1 > 8 && aligned) {
-    rc = fft_pow2(ctx, reinterpret_cast<const float2 *>(x), Z, logM - 1, 1, -1, 1.0f, is_iq ? SRC_IQPOW : SRC_REAL, n, 0);
+    rc = fft_pow2(ctx, reinterpret_cast<const float2 *>(x), Z, logM - 1, 1, -1, 1.0f, iq_src_mode(is_iq), n, 0, nullptr, nullptr, iq_scale);
   } else {
-    TSDR_LAUNCH(ctx, "ac_pack", k_ac_pack, dim3(stream_grid(ctx, Mc)), dim3(256), 0, x, is_iq, n, Mc, z);
+    TSDR_LAUNCH(ctx, "ac_pack", k_ac_pack, dim3(stream_grid(ctx, Mc)), dim3(256), 0, x, is_iq, n, Mc, z, iq_scale);
     rc = fft_pow2(ctx, z, Z, logM - 1, 1, -1, 1.0f, SRC_C2C, 0, 0);
   }
   if (rc) return rc;
@@ -342,7 +355,7 @@ int tsdr_autocorr_partial_d(tsdr_ctx *ctx, const float *x, int is_iq, size_t n, 
   float2 *z = (float2 *)ctx->scratch(WS_FFT_A, M * sizeof(float2));
   float2 *Z = (float2 *)ctx->scratch(WS_FFT_C, M * sizeof(float2));
   if (!z || !Z) return TSDR_ENOMEM;
-  TSDR_LAUNCH(ctx, "pc_pack", k_pc_pack, dim3(stream_grid(ctx, M)), dim3(256), 0, x, is_iq, n, m0, cnt, vlen, M, z);
+  TSDR_LAUNCH(ctx, "pc_pack", k_pc_pack, dim3(stream_grid(ctx, M)), dim3(256), 0, x, is_iq ? 1 : 0, n, m0, cnt, vlen, M, z, 1.0f);
   int rc = fft_pow2(ctx, z, Z, logM, 1, -1, 1.0f, SRC_C2C, 0, 0);
   if (rc) return rc;
   TSDR_LAUNCH(ctx, "pc_cross", k_pc_cross, dim3(stream_grid(ctx, M / 2 + 1)), dim3(256), 0, Z, M);
@@ -447,8 +460,10 @@ int tsdr_argmax_d(tsdr_ctx *ctx, const float *v, size_t n, size_t *idx, float *v
   return amax_wait(ctx, r.seq, idx, val);
 }
 
-int tsdr_autocorr_search_d(tsdr_ctx *ctx, const float *x, int is_iq, size_t len, double Fs, double minDelay, double maxDelay,
-                           int log_scale, float *out, size_t *n_out, size_t win_lo, size_t win_cnt, size_t *idx, float *val) {
+// is_iq as ld_power takes it (0, or 1 + TSDR_IQ_*)
+static int autocorr_search_any_d(tsdr_ctx *ctx, const float *x, int is_iq, float iq_scale, size_t len, double Fs, double minDelay,
+                                 double maxDelay, int log_scale, float *out, size_t *n_out, size_t win_lo, size_t win_cnt, size_t *idx,
+                                 float *val) {
   if (!ctx || !x || !out || !idx) return TSDR_EINVAL;
   size_t n, k0, cnt;
   int rc = autocorr_args(ctx, len, Fs, minDelay, maxDelay, &n, &k0, &cnt);
@@ -462,7 +477,7 @@ int tsdr_autocorr_search_d(tsdr_ctx *ctx, const float *x, int is_iq, size_t len,
   r.lo = win_lo;
   r.cnt = win_cnt;
   ctx->amax_dirty = true;   // until the publish launch (or the route without an epilogue) is known to have been enqueued
-  rc = autocorr_core(ctx, x, is_iq, n, k0, cnt, log_scale, out, &r);
+  rc = autocorr_core(ctx, x, is_iq, n, k0, cnt, log_scale, out, &r, iq_scale);
   if (rc) return rc;
   if (!r.fused) {  // routes whose last pass has no epilogue: the separate kernel
     ctx->amax_dirty = false;
@@ -473,6 +488,23 @@ int tsdr_autocorr_search_d(tsdr_ctx *ctx, const float *x, int is_iq, size_t len,
     ctx->amax_dirty = false;
   }
   return amax_wait(ctx, r.seq, idx, val);
+}
+
+int tsdr_autocorr_search_d(tsdr_ctx *ctx, const float *x, int is_iq, size_t len, double Fs, double minDelay, double maxDelay,
+                           int log_scale, float *out, size_t *n_out, size_t win_lo, size_t win_cnt, size_t *idx, float *val) {
+  return autocorr_search_any_d(ctx, x, is_iq ? 1 : 0, 1.0f, len, Fs, minDelay, maxDelay, log_scale, out, n_out, win_lo, win_cnt, idx, val);
+}
+
+int tsdr_autocorr_search_iq_d(tsdr_ctx *ctx, const void *iq, int iq_fmt, float scale, size_t len, double Fs, double minDelay,
+                              double maxDelay, int log_scale, float *out, size_t *n_out, size_t win_lo, size_t win_cnt, size_t *idx,
+                              float *val) {
+  if (!ctx) return TSDR_EINVAL;
+  if (iq_fmt < TSDR_IQ_CF32 || iq_fmt > TSDR_IQ_UC8) return set_err(ctx, TSDR_EINVAL, "autocorr_search_iq: unknown IQ format %d", iq_fmt);
+  // the first pass loads two samples at a time; one rule for every format: the base a ring slot or hipMalloc hands out
+  if (iq_fmt != TSDR_IQ_CF32 && (reinterpret_cast<uintptr_t>(iq) & 15u)) return set_err(ctx, TSDR_EINVAL, "autocorr_search_iq: integer IQ needs a 16-byte aligned buffer");
+  if (iq_fmt == TSDR_IQ_CF32 && (reinterpret_cast<uintptr_t>(iq) & 7u)) return set_err(ctx, TSDR_EINVAL, "autocorr_search_iq: the buffer is not aligned to one sample");
+  return autocorr_search_any_d(ctx, reinterpret_cast<const float *>(iq), 1 + iq_fmt, iq_fmt == TSDR_IQ_CF32 ? 1.0f : scale, len, Fs, minDelay,
+                               maxDelay, log_scale, out, n_out, win_lo, win_cnt, idx, val);
 }
 
 }  // extern "C"

@@ -42,8 +42,14 @@ struct ProfRec {
 
 // How the frame kernels' loaders read one IQ sample: interleaved ComplexF32 (the reference's recv! buffers), or interleaved
 // int16 pairs as SDR hardware delivers them, turned into ComplexF32(re, im) * scale in the loader itself (tsdr_frames_sc16*:
-// int16 slots are never expanded in HBM -- half the IQ bytes the image kernel reads)
-struct IqFmt { int sc16 = 0; float scale = 1.0f; };
+// int16 slots are never expanded in HBM -- half the IQ bytes the image kernel reads), or 8-bit pairs (tsdr_frames_iq_d):
+// int8 (sc8), or uint8 around the fixed offset 127.5 (uc8: the subtraction is exact in f32, so the product by scale is
+// the only rounding of either format) -- a quarter of the bytes.  kind = TSDR_IQ_* of tempest_hip.h.
+enum { IQK_CF32 = 0, IQK_SC16 = 1, IQK_SC8 = 2, IQK_UC8 = 3 };
+struct IqFmt {
+  int kind = IQK_CF32; float scale = 1.0f;
+  __host__ __device__ bool sc16() const { return kind == IQK_SC16; }
+};
 
 struct TwTable {   // two-level table of W_N^e = exp(-2*pi*i*e/N), N = 2^logN
   int logN = 0, h = 0;
@@ -67,7 +73,7 @@ struct tsdr_ctx {
   std::string err;
   int cu_count = 0;
   int precision = TSDR_FAST;  // tsdr_precision
-  tsdr::IqFmt iq_fmt;         // set for the duration of a tsdr_frames_sc16* call
+  tsdr::IqFmt iq_fmt;         // set for the duration of a tsdr_frames_sc16* / tsdr_frames_iq_d call
   // development switches (tsdr_set_option; environment variables of the same upper-case names are read ONCE, in tsdr_create)
   int opt_ac_mixed = 1;     // autocorrelation of n = 2*(2^a3^b5^c) samples: native mixed-radix route (0: zero-padded power of two)
   int opt_fft_no_mix2 = 0;  // 1: every mixed-radix factor through the generic LDS-stage kernel
@@ -141,15 +147,15 @@ struct tsdr_ctx {
   // frames apart), the tile plan of (S, y_t, x_t, raster or not, precision) for the projection sums, the SyncXY object's block
   // counts for the guard records.  A change of any of them runs the pipeline empty first.
   struct PipeKey {
-    size_t nb = 0, S = 0; int y_t = 0, x_t = 0, raster = -1, prec = -1, align = -1, sc16 = 0; const void *sync = nullptr;
+    size_t nb = 0, S = 0; int y_t = 0, x_t = 0, raster = -1, prec = -1, align = -1, iq_kind = 0; const void *sync = nullptr;
     bool operator==(const PipeKey &o) const {
-      return nb == o.nb && S == o.S && y_t == o.y_t && x_t == o.x_t && raster == o.raster && prec == o.prec && align == o.align && sc16 == o.sc16 && sync == o.sync;
+      return nb == o.nb && S == o.S && y_t == o.y_t && x_t == o.x_t && raster == o.raster && prec == o.prec && align == o.align && iq_kind == o.iq_kind && sync == o.sync;
     }
     // the same loop at a slightly different geometry (GUI.jl:492-506: the interactive y_t / x_t corrections move one line at a
     // time): same frames per buffer, raster or not, precision, alignment, input format; S and the raster size within 10 %.
     // What was measured for one holds for the other (the launches have the same shapes and durations within a few percent).
     bool near(const PipeKey &o) const {
-      if (!(nb == o.nb && raster == o.raster && prec == o.prec && align == o.align && sc16 == o.sc16)) return false;
+      if (!(nb == o.nb && raster == o.raster && prec == o.prec && align == o.align && iq_kind == o.iq_kind)) return false;
       const double s = (double)S / (double)(o.S ? o.S : 1), p = ((double)y_t * x_t) / ((double)o.y_t * o.x_t > 0 ? (double)o.y_t * o.x_t : 1.0);
       return s > 0.9 && s < 1.1 && p > 0.9 && p < 1.1;
     }
@@ -307,17 +313,32 @@ __device__ inline float abs_c(float re, float im) {
   if (isinf(re) || isinf(im)) r = INFINITY;
   return r;
 }
-// one IQ sample of a frame's buffer (k in samples); sc16: the same product the ring's expansion kernel forms
+// one IQ sample of a frame's buffer (k in samples) from integer storage: the same product the ring's expansion kernels form.
+// An 8-bit sample is one 2-byte load (a frame of an 8-bit buffer starts at byte 2*f*S: nothing wider is aligned).
+constexpr float kUc8Offset = 127.5f;   // uc8: value = (f32(code) - 127.5) * scale; the subtraction is exact, the product the one rounding
+__device__ inline float2 cvt_sc16(short2 v, float scale) { return make_float2(__fmul_rn((float)v.x, scale), __fmul_rn((float)v.y, scale)); }
+__device__ inline float2 cvt_sc8(unsigned v, float scale) {   // v: the two bytes, I in the low one
+  return make_float2(__fmul_rn((float)(signed char)(v & 0xFFu), scale), __fmul_rn((float)(signed char)((v >> 8) & 0xFFu), scale));
+}
+__device__ inline float2 cvt_uc8(unsigned v, float scale) {
+  return make_float2(__fmul_rn(__fsub_rn((float)(v & 0xFFu), kUc8Offset), scale),
+                     __fmul_rn(__fsub_rn((float)((v >> 8) & 0xFFu), kUc8Offset), scale));
+}
 __device__ inline float2 ld_iq(const float *__restrict__ src, unsigned k, const IqFmt &f) {
-  if (f.sc16) {
-    const short2 v = reinterpret_cast<const short2 *>(src)[k];
-    return make_float2(__fmul_rn((float)v.x, f.scale), __fmul_rn((float)v.y, f.scale));
+  if (f.kind == IQK_SC16) return cvt_sc16(reinterpret_cast<const short2 *>(src)[k], f.scale);
+  if (f.kind >= IQK_SC8) {   // one load and one instruction stream for both 8-bit formats (sc8: f32(code) - 0 is f32(code))
+    const unsigned v = reinterpret_cast<const unsigned short *>(src)[k];
+    const bool uc = f.kind == IQK_UC8;
+    const int i = uc ? (int)(v & 0xFFu) : (int)(signed char)(v & 0xFFu), q = uc ? (int)(v >> 8) : (int)(signed char)(v >> 8);
+    const float off = uc ? kUc8Offset : 0.f;
+    return make_float2(__fmul_rn(__fsub_rn((float)i, off), f.scale), __fmul_rn(__fsub_rn((float)q, off), f.scale));
   }
   return reinterpret_cast<const float2 *>(src)[k];
 }
-// The same with the format fixed at compile time (IQF_CF32 / IQF_SC16: the FAST image kernels, whose register allocation and
-// instruction stream must not pay for the other format) or read from the launch's parameters (IQF_RT: every other reader)
-enum { IQF_CF32 = 0, IQF_SC16 = 1, IQF_RT = 2 };
+// The same with the format fixed at compile time (IQF_CF32 / IQF_SC16 / IQF_SC8 / IQF_UC8: the FAST image kernels, whose
+// register allocation and instruction stream must not pay for the other formats) or read from the launch's parameters
+// (IQF_RT: every other reader)
+enum { IQF_CF32 = 0, IQF_SC16 = 1, IQF_RT = 2, IQF_SC8 = 3, IQF_UC8 = 4 };
 template <int IQF>
 __device__ inline float2 ld_iq_as(const float *__restrict__ src, unsigned k, const IqFmt &f) {
   if (IQF == IQF_CF32) return reinterpret_cast<const float2 *>(src)[k];
@@ -325,12 +346,21 @@ __device__ inline float2 ld_iq_as(const float *__restrict__ src, unsigned k, con
     const short2 v = reinterpret_cast<const short2 *>(src)[k];
     return make_float2(__fmul_rn((float)v.x, f.scale), __fmul_rn((float)v.y, f.scale));
   }
+  if (IQF == IQF_SC8) return cvt_sc8(reinterpret_cast<const unsigned short *>(src)[k], f.scale);
+  if (IQF == IQF_UC8) return cvt_uc8(reinterpret_cast<const unsigned short *>(src)[k], f.scale);
   return ld_iq(src, k, f);
 }
+// bytes per IQ sample in a buffer of that format (frame strides are counted in samples; an 8-bit sample is half a float, so
+// a frame's base is offset in bytes)
+__host__ __device__ inline size_t iq_bytes(const IqFmt &f) { return f.kind == IQK_CF32 ? 8 : f.kind == IQK_SC16 ? 4 : 2; }
 template <int IQF>
-__host__ __device__ inline size_t iq_floats_as(const IqFmt &f) { return IQF == IQF_CF32 ? 2 : IQF == IQF_SC16 ? 1 : (f.sc16 ? 1 : 2); }
-// floats per IQ sample in a buffer of that format (frame strides are counted in samples)
-__host__ __device__ inline size_t iq_floats(const IqFmt &f) { return f.sc16 ? 1 : 2; }
+__host__ __device__ inline size_t iq_bytes_as(const IqFmt &f) {
+  return IQF == IQF_CF32 ? 8 : IQF == IQF_SC16 ? 4 : (IQF == IQF_SC8 || IQF == IQF_UC8) ? 2 : iq_bytes(f);
+}
+// base of the frame that starts `samples` samples into an IQ buffer (8-bit formats: 2-byte aligned, no more)
+__host__ __device__ inline const float *iq_at(const float *in, size_t samples, size_t bytes_per_sample) {
+  return reinterpret_cast<const float *>(reinterpret_cast<const char *>(in) + samples * bytes_per_sample);
+}
 __device__ inline float abs2_c(float re, float im) { return __fadd_rn(__fmul_rn(re, re), __fmul_rn(im, im)); }
 #endif
 

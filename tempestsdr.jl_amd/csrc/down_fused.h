@@ -152,7 +152,7 @@ __device__ __forceinline__ void down_fused_body(const float *__restrict__ in, si
   int *kfirst = ckx + q.TC;                                                                           // [NL]
   const int tr = tile_idx / q.tiles_c, tc = tile_idx - tr * q.tiles_c;
   const int r0 = tr * 64, c0 = tc * q.TC;
-  const float *src = in + (size_t)f * in_stride * (CPLX ? iq_floats_as<IQF>(q.iqf) : 1);
+  const float *src = CPLX ? iq_at(in, (size_t)f * in_stride, iq_bytes_as<IQF>(q.iqf)) : in + (size_t)f * in_stride;
   const unsigned P = (unsigned)q.y_t * (unsigned)q.x_t;
   const RsAxis ax1 = rs_axis(q.S, P);
   const RsAxis ay = rs_axis((size_t)q.y_t, (size_t)q.h_out);

@@ -39,6 +39,7 @@ struct PassDesc {
   unsigned long long src_n;  // real samples behind SRC_REAL / SRC_IQPOW
   unsigned long long keep;   // last pass: complex outputs >= keep (per transform) are not stored
   const float2 *src_aux;     // SRC_MULH: the factor array
+  double src_w8;             // fft_load's f64 parameter: the scale of an integer IQ source (else 0)
   FftEpilogue epi;           // last pass: epilogue when epi.out != nullptr (fft_dev.h)
 };
 
@@ -116,7 +117,7 @@ __global__ __launch_bounds__(256) void k_fft_pass(const float2 *__restrict__ in,
       const int t = s & (T - 1), j0 = s >> logT;
 #pragma unroll
       for (int m = 0; m < RA; ++m)
-        v[q * RA + m] = s < n1 ? conj_if(fft_load(in, d.src_mode, d.src_n, base + (size_t)(j0 + RB * m) * d.B + t, 0.0, d.src_aux), smask)
+        v[q * RA + m] = s < n1 ? conj_if(fft_load(in, d.src_mode, d.src_n, base + (size_t)(j0 + RB * m) * d.B + t, d.src_w8, d.src_aux), smask)
                                : make_float2(0.f, 0.f);
     }
     // inter-pass twiddles of this thread's 16 outputs: independent of the data, so they are evaluated here,
@@ -341,7 +342,7 @@ int get_tw(tsdr_ctx *ctx, int logN, TwTable **out) {
 // in/out may alias.  Uses WS_FFT_B when more than one pass is needed: callers must not hand
 // WS_FFT_B buffers to this function.
 int fft_pow2(tsdr_ctx *ctx, const float2 *in, float2 *out, int logN, size_t batch, int dir, float scale, int src_mode,
-             size_t src_n, size_t keep, const FftEpilogue *epi, const float2 *src_aux) {
+             size_t src_n, size_t keep, const FftEpilogue *epi, const float2 *src_aux, float src_scale) {
   if (logN < 0 || logN > 31) return set_err(ctx, TSDR_EINVAL, "fft: unsupported power-of-two length 2^%d", logN);
   if (batch == 0) return TSDR_OK;
   int rc = ensure_tw_small(ctx);
@@ -363,6 +364,7 @@ int fft_pow2(tsdr_ctx *ctx, const float2 *in, float2 *out, int logN, size_t batc
   d.keep = keep ? keep : N;
   if ((src_mode != SRC_C2C || epi) && (batch != 1 || logN <= 8)) return set_err(ctx, TSDR_EINVAL, "fft: fused loader / epilogue needs one multi-pass transform");
   d.src_aux = src_aux;
+  d.src_w8 = src_is_int_iq(src_mode) ? (double)src_scale : 0.0;
   if (p == 1) {
     d.mode = FFT_ROWS;
     d.logR = logN;

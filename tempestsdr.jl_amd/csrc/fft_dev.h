@@ -148,6 +148,9 @@ __device__ inline float2 conj_if(float2 v, unsigned smask) {  // smask = 0x80000
 //   SRC_C2C   in[g]
 //   SRC_REAL  (x[2g], x[2g+1])            real f32 sequence of src_n samples packed two per complex, zero beyond
 //   SRC_IQPOW (|iq[2g]|^2, |iq[2g+1]|^2)  the same with x = abs2.(iq) formed on the fly (GUI.jl:70)
+//   SRC_IQPOW_SC16 / _SC8 / _UC8  the same from integer IQ storage (int16, int8, uint8 pairs): every sample is converted by
+//             common.h's cvt_* (the one product by `scale`, which arrives in the loader-parameter slot), then abs2_c.
+//             The two samples of g are one 8-byte (sc16) or 4-byte (8-bit) load: the base must be aligned to that.
 //   SRC_POWER Y[g] of the autocorrelation: `in` = Z, the length-src_n transform of a packed real
 //             sequence; Y is the packed spectrum whose inverse transform (times 1/2) is the real sequence with
 //             spectrum |X|^2 (see k_ac_power, which this loader replaces: one launch and a 2 x 8*Mc-byte round
@@ -157,8 +160,10 @@ __device__ inline float2 conj_if(float2 v, unsigned smask) {  // smask = 0x80000
 //   SRC_RE0   (x[g], 0): a real f32 sequence as complex input (getSpectrum of a real signal) -- k_r2c without its pass
 //   SRC_MULH  in[g] * aux[g], aux = ComplexF64 (double2 behind the float2 pointer): the resampler's frequency-domain filter
 //             applied while the inverse transform loads -- evaluated in f64 and rounded to ComplexF32 (Resampler.jl:51-53)
-enum { SRC_C2C = 0, SRC_REAL = 1, SRC_IQPOW = 2, SRC_POWER = 3, SRC_STUFF = 4, SRC_MULH = 5, SRC_RE0 = 6 };
+enum { SRC_C2C = 0, SRC_REAL = 1, SRC_IQPOW = 2, SRC_POWER = 3, SRC_STUFF = 4, SRC_MULH = 5, SRC_RE0 = 6, SRC_IQPOW_SC16 = 7, SRC_IQPOW_SC8 = 8, SRC_IQPOW_UC8 = 9 };
+inline bool src_is_int_iq(int src_mode) { return src_mode >= SRC_IQPOW_SC16 && src_mode <= SRC_IQPOW_UC8; }
 
+// inv_m8 is the loader's one f64 parameter: 8/M for SRC_POWER with M not a power of two, the f32 scale for integer IQ, else 0
 // tw_frac below (needed by the SRC_POWER loader when M = 2*Mc is not a power of two)
 __device__ inline float2 tw_frac(unsigned e, double inv_n8);
 
@@ -195,8 +200,21 @@ __device__ inline float2 fft_load(const float2 *__restrict__ in, int src_mode, u
     const float *x = reinterpret_cast<const float *>(in);
     return make_float2(x[i0], i0 + 1 < src_n ? x[i0 + 1] : 0.f);
   }
-  const float4 z = reinterpret_cast<const float4 *>(in)[g];  // iq[2g], iq[2g+1]
-  return make_float2(z.x * z.x + z.y * z.y, i0 + 1 < src_n ? z.z * z.z + z.w * z.w : 0.f);
+  if (src_mode == SRC_IQPOW) {
+    const float4 z = reinterpret_cast<const float4 *>(in)[g];  // iq[2g], iq[2g+1]
+    return make_float2(z.x * z.x + z.y * z.y, i0 + 1 < src_n ? z.z * z.z + z.w * z.w : 0.f);
+  }
+  const float sc = (float)inv_m8;
+  float2 a, b;
+  if (src_mode == SRC_IQPOW_SC16) {
+    const short4 v = reinterpret_cast<const short4 *>(in)[g];
+    a = cvt_sc16(make_short2(v.x, v.y), sc); b = cvt_sc16(make_short2(v.z, v.w), sc);
+  } else {
+    const unsigned v = reinterpret_cast<const unsigned *>(in)[g];
+    if (src_mode == SRC_IQPOW_SC8) { a = cvt_sc8(v & 0xFFFFu, sc); b = cvt_sc8(v >> 16, sc); }
+    else { a = cvt_uc8(v & 0xFFFFu, sc); b = cvt_uc8(v >> 16, sc); }
+  }
+  return make_float2(abs2_c(a.x, a.y), i0 + 1 < src_n ? abs2_c(b.x, b.y) : 0.f);
 }
 
 // exp(-2*pi*i*e/N) for any N: inv_n8 = 8/N in f64, 0 <= e < N.  The phase e/N is formed in f64 (relative error
@@ -290,11 +308,11 @@ __device__ inline void epi_argmax_finish(const FftEpilogue &e, unsigned long lon
 // pass; keep: complex outputs per transform the caller will look at (0 = all); epi: epilogue of the last pass.  Loaders
 // and epilogues need one transform (batch == 1) of more than one pass.
 int fft_pow2(tsdr_ctx *ctx, const float2 *in, float2 *out, int logN, size_t batch, int dir, float scale, int src_mode,
-             size_t src_n, size_t keep, const FftEpilogue *epi = nullptr, const float2 *src_aux = nullptr);
+             size_t src_n, size_t keep, const FftEpilogue *epi = nullptr, const float2 *src_aux = nullptr, float src_scale = 1.0f);
 int fft_mixed(tsdr_ctx *ctx, const float2 *in, float2 *out, size_t N, size_t batch, int dir, float scale, int src_mode,
-              size_t src_n, size_t keep, const FftEpilogue *epi = nullptr, const float2 *src_aux = nullptr);
+              size_t src_n, size_t keep, const FftEpilogue *epi = nullptr, const float2 *src_aux = nullptr, float src_scale = 1.0f);
 int fft_mixed_autocorr(tsdr_ctx *ctx, const float2 *x, int src_mode, size_t src_n, size_t Mc, float2 *Zbuf, float2 *zbuf,
-                       float scale, size_t keep, const FftEpilogue *epi, bool *done);
+                       float scale, size_t keep, const FftEpilogue *epi, bool *done, float src_scale = 1.0f);
 unsigned fft_rows_welch_parts(tsdr_ctx *ctx);
 int fft_rows_welch(tsdr_ctx *ctx, const float *sig, int is_complex, size_t N, size_t nbSeg, float *part, unsigned *nparts, bool *did);
 int fft_rows1024(tsdr_ctx *ctx, const float2 *in, float2 *out, size_t batch, int dir, float scale);   // spectrum.hip

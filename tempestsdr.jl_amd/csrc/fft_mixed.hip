@@ -1481,7 +1481,7 @@ static bool fft_big_ok(tsdr_ctx *ctx, size_t total_points) {
 //   their result in.
 static int fft_mixed_ex(tsdr_ctx *ctx, const float2 *in, float2 *out, size_t N, size_t batch, int dir, float scale, int src_mode,
                         size_t src_n, size_t keep, const FftEpilogue *epi, const float2 *src_aux, const MixPlan *force,
-                        int first_pass, float2 **work_out) {
+                        int first_pass, float2 **work_out, float src_scale = 1.0f) {
   MixPlan pl;
   if (force) pl = *force;
   else if (!fft_mixed_plan(N, &pl, fft_big_ok(ctx, N * batch)))
@@ -1495,7 +1495,7 @@ static int fft_mixed_ex(tsdr_ctx *ctx, const float2 *in, float2 *out, size_t N, 
   d.N = N;
   d.src_mode = SRC_C2C;
   d.keep = keep ? keep : N;
-  d.src_w8 = src_mode == SRC_POWER && !is_pow2(src_n) ? 4.0 / (double)src_n : 0.0;
+  d.src_w8 = src_mode == SRC_POWER && !is_pow2(src_n) ? 4.0 / (double)src_n : src_is_int_iq(src_mode) ? (double)src_scale : 0.0;
   d.src_aux = src_aux;
   if (epi && (batch != 1 || p == 1)) return set_err(ctx, TSDR_EINVAL, "fft: epilogue needs one multi-pass transform");
   auto set_radix = [&](int i) {
@@ -1725,8 +1725,8 @@ int fft_rows_waterfall(tsdr_ctx *ctx, const float *sig, int is_complex, size_t N
 }
 
 int fft_mixed(tsdr_ctx *ctx, const float2 *in, float2 *out, size_t N, size_t batch, int dir, float scale, int src_mode,
-              size_t src_n, size_t keep, const FftEpilogue *epi, const float2 *src_aux) {
-  return fft_mixed_ex(ctx, in, out, N, batch, dir, scale, src_mode, src_n, keep, epi, src_aux, nullptr, 0, nullptr);
+              size_t src_n, size_t keep, const FftEpilogue *epi, const float2 *src_aux, float src_scale) {
+  return fft_mixed_ex(ctx, in, out, N, batch, dir, scale, src_mode, src_n, keep, epi, src_aux, nullptr, 0, nullptr, src_scale);
 }
 
 // The circular autocorrelation of n = 2*Mc real samples (x, or abs2 of IQ formed while loading) as
@@ -1734,7 +1734,7 @@ int fft_mixed(tsdr_ctx *ctx, const float2 *in, float2 *out, size_t N, size_t bat
 // with the epilogue (abs2 / 10log10 of the wanted lags, optional findmax) on the last one.  *done = false (nothing
 // launched) when this length has no fused middle: the caller then runs the two transforms separately.
 int fft_mixed_autocorr(tsdr_ctx *ctx, const float2 *x, int src_mode, size_t src_n, size_t Mc, float2 *Zbuf, float2 *zbuf,
-                       float scale, size_t keep, const FftEpilogue *epi, bool *done) {
+                       float scale, size_t keep, const FftEpilogue *epi, bool *done, float src_scale) {
   *done = false;
   MixPlan F;
   if (ctx->opt_fft_no_mix2 || !fft_mixed_plan(Mc, &F, fft_big_ok(ctx, Mc)) || F.p < 2 || Mc >= (size_t(1) << 31)) return TSDR_OK;
@@ -1797,7 +1797,7 @@ int fft_mixed_autocorr(tsdr_ctx *ctx, const float2 *x, int src_mode, size_t src_
   m.tw_sets = sets <= 4 ? (int)sets : 0;
   m.w8 = 4.0 / (double)Mc;
   float2 *w = nullptr;
-  int rc = fft_mixed_ex(ctx, x, nullptr, Mc, 1, -1, 1.0f, src_mode, src_n, 0, nullptr, nullptr, &F, 0, &w);
+  int rc = fft_mixed_ex(ctx, x, nullptr, Mc, 1, -1, 1.0f, src_mode, src_n, 0, nullptr, nullptr, &F, 0, &w, src_scale);
   if (rc) return rc;
   if (me->RA == 0) {  // three-step kernel
     const size_t lds = me->lds3;

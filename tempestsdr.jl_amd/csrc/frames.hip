@@ -477,7 +477,7 @@ int tsdr_frames_submit_d(tsdr_ctx *ctx, tsdr_sync *sync, const float *iq, size_t
   if (rc) return rc;
   tsdr_ctx::PipeKey key;
   key.nb = nb; key.S = S; key.y_t = y_t; key.x_t = x_t; key.raster = raster_out ? 1 : 0; key.prec = ctx->precision;
-  key.align = do_align ? 1 : 0; key.sync = (const void *)sync; key.sc16 = ctx->iq_fmt.sc16;
+  key.align = do_align ? 1 : 0; key.sync = (const void *)sync; key.iq_kind = ctx->iq_fmt.kind;
   const int cand = pipe_pick(ctx, key);
   if (cand < 0) return cand;
   const PipeCand &pc = kCands[cand];
@@ -646,16 +646,25 @@ int tsdr_frames_pipeline_info(tsdr_ctx *ctx, int *trials_left, int *chosen, floa
 namespace {
 struct IqScope {
   tsdr_ctx *ctx;
-  IqScope(tsdr_ctx *c, float scale) : ctx(c) { c->iq_fmt.sc16 = 1; c->iq_fmt.scale = scale; }
+  IqScope(tsdr_ctx *c, int kind, float scale) : ctx(c) { c->iq_fmt.kind = kind; c->iq_fmt.scale = scale; }
   ~IqScope() { ctx->iq_fmt = tsdr::IqFmt{}; }
 };
+// tsdr_frames_iq_d / tsdr_frames_submit_iq_d: the format is one of TSDR_IQ_*, the base aligned to one sample
+int iq_args_check(tsdr_ctx *ctx, const void *iq, int iq_fmt) {
+  static_assert(TSDR_IQ_CF32 == tsdr::IQK_CF32 && TSDR_IQ_SC16 == tsdr::IQK_SC16 && TSDR_IQ_SC8 == tsdr::IQK_SC8 && TSDR_IQ_UC8 == tsdr::IQK_UC8,
+                "IqFmt::kind is the public format code");
+  if (iq_fmt < TSDR_IQ_CF32 || iq_fmt > TSDR_IQ_UC8) return tsdr::set_err(ctx, TSDR_EINVAL, "frames_iq: unknown IQ format %d", iq_fmt);
+  tsdr::IqFmt f; f.kind = iq_fmt;
+  if (reinterpret_cast<uintptr_t>(iq) % tsdr::iq_bytes(f)) return tsdr::set_err(ctx, TSDR_EINVAL, "frames_iq: the buffer is not aligned to one sample of its format");
+  return TSDR_OK;
+}
 }  // namespace
 
 int tsdr_frames_sc16_d(tsdr_ctx *ctx, tsdr_sync *sync, const int16_t *iq, float scale, size_t nEch, size_t S, int y_t, int x_t,
                        float alpha, int do_align, float *imageOut_state, float *frames_out, float *raster_out, int *sync_idx,
                        int *n_frames) {
   if (!ctx) return TSDR_EINVAL;
-  IqScope fmt(ctx, scale);
+  IqScope fmt(ctx, tsdr::IQK_SC16, scale);
   return tsdr_frames_d(ctx, sync, reinterpret_cast<const float *>(iq), nEch, S, y_t, x_t, alpha, do_align, imageOut_state, frames_out,
                        raster_out, sync_idx, n_frames);
 }
@@ -664,7 +673,29 @@ int tsdr_frames_submit_sc16_d(tsdr_ctx *ctx, tsdr_sync *sync, const int16_t *iq,
                               int x_t, float alpha, int do_align, float *imageOut_state, float *frames_out, float *raster_out,
                               int *sync_idx, int *n_frames) {
   if (!ctx) return TSDR_EINVAL;
-  IqScope fmt(ctx, scale);
+  IqScope fmt(ctx, tsdr::IQK_SC16, scale);
+  return tsdr_frames_submit_d(ctx, sync, reinterpret_cast<const float *>(iq), nEch, S, y_t, x_t, alpha, do_align, imageOut_state,
+                              frames_out, raster_out, sync_idx, n_frames);
+}
+
+// ---- any input format (TSDR_IQ_*): ComplexF32, int16 pairs, or the 8-bit pairs of HackRF / UHD sc8 (int8) and RTL-SDR
+// (uint8 around 127.5).  CF32 ignores the scale and is tsdr_frames_d; every other format converts in the loaders.
+int tsdr_frames_iq_d(tsdr_ctx *ctx, tsdr_sync *sync, const void *iq, int iq_fmt, float scale, size_t nEch, size_t S, int y_t, int x_t,
+                     float alpha, int do_align, float *imageOut_state, float *frames_out, float *raster_out, int *sync_idx,
+                     int *n_frames) {
+  if (!ctx) return TSDR_EINVAL;
+  if (int rc = iq_args_check(ctx, iq, iq_fmt)) return rc;
+  IqScope fmt(ctx, iq_fmt, iq_fmt == TSDR_IQ_CF32 ? 1.0f : scale);
+  return tsdr_frames_d(ctx, sync, reinterpret_cast<const float *>(iq), nEch, S, y_t, x_t, alpha, do_align, imageOut_state, frames_out,
+                       raster_out, sync_idx, n_frames);
+}
+
+int tsdr_frames_submit_iq_d(tsdr_ctx *ctx, tsdr_sync *sync, const void *iq, int iq_fmt, float scale, size_t nEch, size_t S, int y_t,
+                            int x_t, float alpha, int do_align, float *imageOut_state, float *frames_out, float *raster_out,
+                            int *sync_idx, int *n_frames) {
+  if (!ctx) return TSDR_EINVAL;
+  if (int rc = iq_args_check(ctx, iq, iq_fmt)) return rc;
+  IqScope fmt(ctx, iq_fmt, iq_fmt == TSDR_IQ_CF32 ? 1.0f : scale);
   return tsdr_frames_submit_d(ctx, sync, reinterpret_cast<const float *>(iq), nEch, S, y_t, x_t, alpha, do_align, imageOut_state,
                               frames_out, raster_out, sync_idx, n_frames);
 }

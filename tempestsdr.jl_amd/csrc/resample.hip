@@ -131,7 +131,7 @@ __global__ __launch_bounds__(256) void k_raster_tile(const float *__restrict__ i
   int tp = (int)u - f * q.tiles_p;
   if (tp < 0) { tp += q.tiles_p; --f; } else if (tp >= q.tiles_p) { tp -= q.tiles_p; ++f; }
   const int l0 = tl * q.own_l, p0 = tp * q.own_p;
-  const float *src = in + (size_t)f * in_stride * (CPLX ? iq_floats(q.iqf) : 1);
+  const float *src = CPLX ? iq_at(in, (size_t)f * in_stride, iq_bytes(q.iqf)) : in + (size_t)f * in_stride;
   const unsigned P = (unsigned)q.y_t * (unsigned)q.x_t;
   const RsAxis ax = q.ax;
   const bool same = (q.S == P);
@@ -585,8 +585,11 @@ __global__ __launch_bounds__(256 * VW, 8) void k_raster_fast(const float *__rest
   int f = (int)(((float)u + 0.5f) * q.inv_tiles_p);
   int tp = (int)u - f * q.tiles_p;
   if (tp < 0) { tp += q.tiles_p; --f; } else if (tp >= q.tiles_p) { tp -= q.tiles_p; ++f; }
+  // (f and tp are wave-uniform but come out of f32 arithmetic, i.e. vector registers; behind the run-time format switch of
+  // the loader the compiler no longer moves the frame's image base back to scalar registers for store_saddr: say so here)
+  if (CPLX && IQF == IQF_RT) { f = __builtin_amdgcn_readfirstlane(f); tp = __builtin_amdgcn_readfirstlane(tp); }
   const int l0 = tl * q.own_l, p0 = tp * q.own_p;
-  const float *src = in + (size_t)f * in_stride * (CPLX ? iq_floats_as<IQF>(q.iqf) : 1);
+  const float *src = CPLX ? iq_at(in, (size_t)f * in_stride, iq_bytes_as<IQF>(q.iqf)) : in + (size_t)f * in_stride;
   const int tid = threadIdx.x;
   const int wave_id = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   const int wave = wave_id & 3, wv = wave_id >> 2;  // horizontal segment, vertical position
@@ -924,7 +927,7 @@ __global__ __launch_bounds__(64 * (128 / PW), 4) void k_raster_fast4(   // (HIP:
   int tp = (int)u - f * q.tiles_p;
   if (tp < 0) { tp += q.tiles_p; --f; } else if (tp >= q.tiles_p) { tp -= q.tiles_p; ++f; }
   const int l0 = tl * q.own_l, p0 = tp * q.own_p;
-  const float *src = in + (size_t)f * in_stride * iq_floats_as<IQF>(q.iqf);
+  const float *src = iq_at(in, (size_t)f * in_stride, iq_bytes_as<IQF>(q.iqf));
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
 
@@ -1079,7 +1082,7 @@ template <bool CPLX>
 __global__ __launch_bounds__(256) void k_raster_direct(const float *__restrict__ in, size_t in_stride, unsigned S,
                                                        int y_t, int x_t, float *__restrict__ out, size_t out_stride, IqFmt iqf) {
   const int f = blockIdx.y;
-  const float *src = in + (size_t)f * in_stride * (CPLX ? iq_floats(iqf) : 1);
+  const float *src = CPLX ? iq_at(in, (size_t)f * in_stride, iq_bytes(iqf)) : in + (size_t)f * in_stride;
   const unsigned P = (unsigned)y_t * (unsigned)x_t;
   const RsAxis ax = rs_axis(S, P);
   const bool same = (S == P);
@@ -1250,7 +1253,8 @@ int raster_frames_d(tsdr_ctx *ctx, const float *in, int cplx, size_t in_stride, 
     // round 6: four lines per lane (k_raster_fast4) wherever the f32-sample walk with the in-walk image writes rasters from
     // 128-pixel tiles -- C2's route: a quarter fewer write requests for the same bytes (option "raster_v4", default on)
     const bool v4 = ctx->opt_raster_v4 > 0 && rec4_ok && dn && q.TP == 128 && out != nullptr && 2 * P < (size_t(1) << 24) && y_t >= 512 &&
-                    x_t <= 127 * 128 && ctx->opt_raster_split == 0;
+                    x_t <= 127 * 128 && ctx->opt_raster_split == 0 &&
+                    (q.iqf.kind == IQK_CF32 || q.iqf.kind == IQK_SC16);   // (k_raster_fast4 exists for those two formats only)
     int VW = v4 ? 1 : y_t >= 2 * 64 ? 2 : 1;
     const int lstep = dn ? 63 : 64, NL = v4 ? 256 : lstep * (VW - 1) + 64;
     q.own_l = v4 ? 255 : lstep * VW;
@@ -1308,12 +1312,12 @@ int raster_frames_d(tsdr_ctx *ctx, const float *in, int cplx, size_t in_stride, 
     const dim3 grid(8, (unsigned)q.tiles_l, (unsigned)upx);
     if (v4) {
       if (v4pw == 32) {
-        if (q.iqf.sc16) {
+        if (q.iqf.sc16()) {
           TSDR_LAUNCH(ctx, "raster_down_iq", (k_raster_fast4<IQF_SC16, 32>), grid, dim3(256), lds, in, in_stride, q, fa, fi, out, out_stride, down, down_stride);
         } else {
           TSDR_LAUNCH(ctx, "raster_down_iq", (k_raster_fast4<IQF_CF32, 32>), grid, dim3(256), lds, in, in_stride, q, fa, fi, out, out_stride, down, down_stride);
         }
-      } else if (q.iqf.sc16) {
+      } else if (q.iqf.sc16()) {
         TSDR_LAUNCH(ctx, "raster_down_iq", (k_raster_fast4<IQF_SC16, 16>), grid, dim3(512), lds, in, in_stride, q, fa, fi, out, out_stride, down, down_stride);
       } else {
         TSDR_LAUNCH(ctx, "raster_down_iq", (k_raster_fast4<IQF_CF32, 16>), grid, dim3(512), lds, in, in_stride, q, fa, fi, out, out_stride, down, down_stride);
@@ -1343,7 +1347,10 @@ int raster_frames_d(tsdr_ctx *ctx, const float *in, int cplx, size_t in_stride, 
   } while (0)
 #define FASTK2R(W32, PW, VWK)                                                                                         \
   do {                                                                                                                \
-    if (q.iqf.sc16) FASTK2RF(W32, PW, VWK, IQF_SC16); else FASTK2RF(W32, PW, VWK, IQF_CF32);                          \
+    if (q.iqf.kind == IQK_SC16) FASTK2RF(W32, PW, VWK, IQF_SC16);                                                     \
+    else if (q.iqf.kind == IQK_SC8) FASTK2RF(W32, PW, VWK, IQF_SC8);                                                  \
+    else if (q.iqf.kind == IQK_UC8) FASTK2RF(W32, PW, VWK, IQF_UC8);                                                  \
+    else FASTK2RF(W32, PW, VWK, IQF_CF32);                                                                            \
   } while (0)
 #define FASTK1(C, W32, D, PW, NAME)                                                                                   \
   do {                                                                                                                \
@@ -1527,8 +1534,14 @@ int down_frames_d(tsdr_ctx *ctx, const float *in, int cplx, size_t in_stride, si
   // (the FAST kernels exist once per input format -- ComplexF32 or int16 pairs -- the EXACT one reads either)
 #define DOWNKL(C, M, SUMS, LDN, NAME, LDS)                                                                                         \
   do {                                                                                                                             \
-    if (M != DM_EXACT && pl.q.iqf.sc16) {                                                                                          \
+    if (M != DM_EXACT && pl.q.iqf.kind == IQK_SC16) {                                                                              \
       TSDR_LAUNCH(ctx, NAME, (k_down_fused<C, M, SUMS, LDN, (M == DM_EXACT ? IQF_RT : IQF_SC16)>), grid, dim3(kDownNT), LDS, in,   \
+                  in_stride, pl.q, out, out_stride, lds_main);                                                                     \
+    } else if (M != DM_EXACT && pl.q.iqf.kind == IQK_SC8) {                                                                        \
+      TSDR_LAUNCH(ctx, NAME, (k_down_fused<C, M, SUMS, LDN, (M == DM_EXACT ? IQF_RT : IQF_SC8)>), grid, dim3(kDownNT), LDS, in,    \
+                  in_stride, pl.q, out, out_stride, lds_main);                                                                     \
+    } else if (M != DM_EXACT && pl.q.iqf.kind == IQK_UC8) {                                                                        \
+      TSDR_LAUNCH(ctx, NAME, (k_down_fused<C, M, SUMS, LDN, (M == DM_EXACT ? IQF_RT : IQF_UC8)>), grid, dim3(kDownNT), LDS, in,    \
                   in_stride, pl.q, out, out_stride, lds_main);                                                                     \
     } else {                                                                                                                       \
       TSDR_LAUNCH(ctx, NAME, (k_down_fused<C, M, SUMS, LDN>), grid, dim3(kDownNT), LDS, in, in_stride, pl.q, out, out_stride,     \
@@ -1568,7 +1581,7 @@ int down_frames_d(tsdr_ctx *ctx, const float *in, int cplx, size_t in_stride, si
   if (!ras) return TSDR_ENOMEM;
   ras += (size_t)(ctx->pipe_lane & 3) * P;
   for (int f = 0; f < frames; ++f) {
-    rc = raster_frames_d(ctx, in + (size_t)f * in_stride * (cplx ? iq_floats(ctx->iq_fmt) : 1), cplx, in_stride, S, y_t, x_t, 1, ras, P);
+    rc = raster_frames_d(ctx, cplx ? iq_at(in, (size_t)f * in_stride, iq_bytes(ctx->iq_fmt)) : in + (size_t)f * in_stride, cplx, in_stride, S, y_t, x_t, 1, ras, P);
     if (rc) return rc;
     rc = resize2d_d(ctx, ras, y_t, x_t, h_out, w_out, out + (size_t)f * out_stride);
     if (rc) return rc;
@@ -1622,7 +1635,7 @@ int raster_and_down_d(tsdr_ctx *ctx, const float *in, int cplx, size_t in_stride
   // FAST with a raster (option "raster_split"; A/B of round 4): the rasters by the store-aligned ("sheared") raster-only
   // kernel of raster_shear.hip, the images + projection sums by the raster-free kernel -- two launches, IQ read twice,
   // instead of the one walk that produces raster, image and sums with misaligned column stores
-  if (raster && ctx->precision == TSDR_FAST && cplx && ctx->opt_raster_split && !ctx->iq_fmt.sc16) {   // (the A/B kernel reads ComplexF32 only)
+  if (raster && ctx->precision == TSDR_FAST && cplx && ctx->opt_raster_split && ctx->iq_fmt.kind == IQK_CF32) {   // (the A/B kernel reads ComplexF32 only)
     const DownPlan dp = plan_down(S, y_t, x_t, h_out, w_out, false);
     const double spp = (double)S / ((double)y_t * (double)x_t);
     if (dp.fused && dp.q.TC >= 32 && spp <= 0.5 && !(y_t == h_out && x_t == w_out) && check_geom(ctx, S, y_t, x_t) == TSDR_OK && y_t >= 64 && x_t >= 128) {

@@ -10,7 +10,9 @@
 // on its own stream; the ring owns two device buffers and, when a buffer is handed out, already starts the DMA of
 // the next committed slot into the other one -- the H2D transfer of buffer k+1 runs under the kernels of buffer k.
 // Slots may hold ComplexF32 (what recv! returns in the reference) or interleaved int16 I/Q as SDR hardware
-// delivers it (half the PCIe bytes; expanded to ComplexF32 on the device with a caller-given scale).
+// delivers it (half the PCIe bytes; expanded to ComplexF32 on the device with a caller-given scale), or 8-bit I/Q --
+// int8 (HackRF, UHD sc8) or uint8 around 127.5 (RTL-SDR) -- at a quarter of the bytes.  The integer formats either
+// expand on the device or stay as they are for the loaders of tsdr_frames_iq_d / tsdr_autocorr_search_iq_d.
 #include <chrono>
 #include <condition_variable>
 #include <cstring>
@@ -22,12 +24,12 @@
 struct tsdr_ring {
   tsdr_ctx *ctx = nullptr;
   size_t nEch = 0;
-  int depth = 0, fmt = 0;          // fmt: 0 = ComplexF32, 1 = int16 I/Q
-  float scale = 1.0f;              // int16 -> float factor
+  int depth = 0, fmt = 0;          // fmt: 0 = ComplexF32, 1 / 2 = int16 I/Q expanded / raw, 3 / 4 = int8, 5 / 6 = uint8 (tempest_hip.h)
+  float scale = 1.0f;              // integer -> float factor
   size_t slot_bytes = 0;
   char *host = nullptr;            // depth pinned slots
   float *dev[2] = {nullptr, nullptr};
-  void *raw[2] = {nullptr, nullptr};  // int16 landing buffers (fmt 1)
+  void *raw[2] = {nullptr, nullptr};  // integer landing buffers (fmt 1, 3, 5)
   hipStream_t copy = nullptr;
   hipEvent_t ready[2] = {nullptr, nullptr};  // DMA (+ conversion) of dev[i] complete
   hipEvent_t freed = nullptr;                 // consumer's stream has passed the previous hand-out
@@ -61,13 +63,39 @@ __global__ __launch_bounds__(256) void k_sc16_to_cf32(const short2 *__restrict__
   }
 }
 
+// 8-bit pairs -> ComplexF32, the product of common.h's loaders (cvt_sc8 / cvt_uc8).  Two samples (one dword) per step; the
+// landing buffer is a hipMalloc block, so the dword loads and float4 stores are aligned.  An odd last sample goes alone.
+template <bool UC>
+__global__ __launch_bounds__(256) void k_iq8_to_cf32(const unsigned *__restrict__ in, size_t n, float scale, float4 *__restrict__ out) {
+  const size_t np = n / 2;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < np; i += (size_t)gridDim.x * blockDim.x) {
+    const unsigned v = in[i];
+    const float2 a = UC ? cvt_uc8(v & 0xFFFFu, scale) : cvt_sc8(v & 0xFFFFu, scale);
+    const float2 b = UC ? cvt_uc8(v >> 16, scale) : cvt_sc8(v >> 16, scale);
+    out[i] = make_float4(a.x, a.y, b.x, b.y);
+  }
+  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+    const unsigned v = reinterpret_cast<const unsigned short *>(in)[n - 1];
+    reinterpret_cast<float2 *>(out)[n - 1] = UC ? cvt_uc8(v, scale) : cvt_sc8(v, scale);
+  }
+}
+
+inline bool ring_fmt_raw(int fmt) { return fmt == 0 || fmt == 2 || fmt == 4 || fmt == 6; }   // the slot's bytes are what the consumer reads
+inline size_t ring_fmt_bytes(int fmt) { return fmt == 0 ? 8 : fmt <= 2 ? 4 : 2; }              // per sample
+
 // start the DMA of host slot `slot` into device buffer d (caller holds no lock; slot content is stable because the
 // producer only overwrites slots the consumer has not reserved -- see ring_take)
 static int ring_stage(tsdr_ring *r, int slot, int d) {
   tsdr_ctx *ctx = r->ctx;
   const char *src = r->host + (size_t)slot * r->slot_bytes;
-  if (r->fmt == 0 || r->fmt == 2) {   // (2: the int16 pairs stay int16 on the device -- tsdr_frames_sc16_d reads them as they are)
+  if (ring_fmt_raw(r->fmt)) {   // (2, 4, 6: the integer pairs stay as they are on the device -- the frame and search loaders read them)
     TSDR_HIP(ctx, hipMemcpyAsync(r->dev[d], src, r->slot_bytes, hipMemcpyHostToDevice, r->copy));
+  } else if (r->fmt == 3 || r->fmt == 5) {
+    TSDR_HIP(ctx, hipMemcpyAsync(r->raw[d], src, r->slot_bytes, hipMemcpyHostToDevice, r->copy));
+    const dim3 grid((unsigned)stream_grid(ctx, (r->nEch + 1) / 2));
+    if (r->fmt == 3) hipLaunchKernelGGL(k_iq8_to_cf32<false>, grid, dim3(256), 0, r->copy, (const unsigned *)r->raw[d], r->nEch, r->scale, (float4 *)r->dev[d]);
+    else hipLaunchKernelGGL(k_iq8_to_cf32<true>, grid, dim3(256), 0, r->copy, (const unsigned *)r->raw[d], r->nEch, r->scale, (float4 *)r->dev[d]);
+    TSDR_HIP(ctx, hipGetLastError());
   } else {
     TSDR_HIP(ctx, hipMemcpyAsync(r->raw[d], src, r->slot_bytes, hipMemcpyHostToDevice, r->copy));
     hipLaunchKernelGGL(k_sc16_to_cf32, dim3((unsigned)stream_grid(ctx, r->nEch)), dim3(256), 0, r->copy,
@@ -85,16 +113,16 @@ using namespace tsdr;
 extern "C" {
 
 int tsdr_ring_create(tsdr_ctx *ctx, size_t nEch, int depth, int fmt, float scale, tsdr_ring **out) {
-  if (!ctx || !out || nEch == 0 || depth < 2 || fmt < 0 || fmt > 2) return TSDR_EINVAL;
+  if (!ctx || !out || nEch == 0 || depth < 2 || fmt < 0 || fmt > 6) return TSDR_EINVAL;
   *out = nullptr;
   tsdr_ring *r = new tsdr_ring();
   r->ctx = ctx; r->nEch = nEch; r->depth = depth; r->fmt = fmt; r->scale = scale;
-  r->slot_bytes = nEch * (fmt == 0 ? 8 : 4);
+  r->slot_bytes = nEch * ring_fmt_bytes(fmt);
   r->slot_gen.assign((size_t)depth, 0ull);
   bool ok = hipHostMalloc((void **)&r->host, r->slot_bytes * depth, hipHostMallocDefault) == hipSuccess;
   for (int i = 0; i < 2 && ok; ++i) {
     ok = hipMalloc((void **)&r->dev[i], nEch * 8) == hipSuccess;
-    if (ok && fmt == 1) ok = hipMalloc(&r->raw[i], r->slot_bytes) == hipSuccess;
+    if (ok && !ring_fmt_raw(fmt)) ok = hipMalloc(&r->raw[i], (r->slot_bytes + 3) & ~(size_t)3) == hipSuccess;
     if (ok) ok = hipEventCreateWithFlags(&r->ready[i], hipEventDisableTiming) == hipSuccess;
   }
   if (ok) ok = hipEventCreateWithFlags(&r->freed, hipEventDisableTiming) == hipSuccess;

@@ -865,8 +865,8 @@ int sync_guard_d(tsdr_sync *s, const float *iq, size_t S, int y_t, int x_t, int 
     a.g.top2 = g.top2 + (size_t)f0 * (size_t)(g.nbx + g.nby);
     a.g.flags = g.flags + f0;
     a.frames = nf;
-    // (an sc16 buffer has one float's worth of bytes per sample)
-    a.iq = iq + (size_t)f0 * S * iq_floats(ctx->iq_fmt); a.in_stride = S; a.img = img + (size_t)f0 * img_stride; a.img_stride = img_stride;
+    // (frames are offset in bytes: an sc16 sample is one float's worth, an 8-bit one half of that)
+    a.iq = iq_at(iq, (size_t)f0 * S, iq_bytes(ctx->iq_fmt)); a.in_stride = S; a.img = img + (size_t)f0 * img_stride; a.img_stride = img_stride;
     a.tilesA = (int)(ceil_div((size_t)y, 64) * (size_t)a.dq.tiles_c);
     a.y_t = y; a.x_t = x;
     a.proj_stride = proj_floats(y, x, pl); a.ncp = pl.ncp; a.nrp = pl.nrp;

@@ -13,13 +13,16 @@ from . import api
 
 
 def stream_frames(ctx, ring, sync, n_buffers, nEch, S, y_t, x_t, alpha, state, frames_out, sync_idx, timeout_ms=10000,
-                  sc16_scale=None):
+                  sc16_scale=None, iq_fmt=None, iq_scale=1.0):
     """Consumer loop: take a device buffer from the ring, run the frame path on it, repeat.  Returns frames done.
-    sc16_scale: the ring hands out int16 pairs (fmt "sc16raw"), which the frame kernels convert in their loaders."""
+    sc16_scale: the ring hands out int16 pairs (fmt "sc16raw"), which the frame kernels convert in their loaders.
+    iq_fmt ("sc16", "sc8", "uc8") with iq_scale: the same for any raw ring ("sc16raw", "sc8raw", "uc8raw"), through frames_iq_d."""
     done = 0
     for _ in range(n_buffers):
         d_iq = ring.take_d(timeout_ms)
-        if sc16_scale is None:
+        if iq_fmt is not None:
+            done += api.frames_iq_d(ctx, sync, d_iq, iq_fmt, iq_scale, nEch, S, y_t, x_t, alpha, True, state, frames_out, None, sync_idx)
+        elif sc16_scale is None:
             done += api.frames_d(ctx, sync, d_iq, nEch, S, y_t, x_t, alpha, True, state, frames_out, None, sync_idx)
         else:
             done += api.frames_sc16_d(ctx, sync, d_iq, sc16_scale, nEch, S, y_t, x_t, alpha, True, state, frames_out, None, sync_idx)
@@ -37,6 +40,11 @@ def bench_ingest(ctx, tsdr, iq_host, S, y_t, x_t, seconds=1.0, depth=4, fmt="cf3
         peak = float(np.max(np.abs(iq_host.view(np.float32)))) or 1.0
         scale = peak / 2047.0
         src = np.round(iq_host.view(np.float32) / scale).astype(np.int16)
+    elif fmt in ("sc8", "sc8raw", "uc8", "uc8raw"):   # full-scale 8-bit codes: int8, or uint8 around 127.5
+        peak = float(np.max(np.abs(iq_host.view(np.float32)))) or 1.0
+        scale = peak / 127.0
+        q = iq_host.view(np.float32) / scale
+        src = np.round(q).astype(np.int8) if fmt.startswith("sc8") else np.clip(np.round(q + 127.5), 0, 255).astype(np.uint8)
     else:
         src = iq_host.view(np.float32)
     ring = tsdr.StagingRing(ctx, nEch, depth, fmt=fmt, scale=scale)
@@ -69,7 +77,8 @@ def bench_ingest(ctx, tsdr, iq_host, S, y_t, x_t, seconds=1.0, depth=4, fmt="cf3
     t0 = time.perf_counter()
     while time.perf_counter() - t0 < seconds:
         n_done += stream_frames(ctx, ring, sync, 4, nEch, S, y_t, x_t, np.float32(0.1), state, frames_out, sync_idx,
-                                sc16_scale=scale if fmt == "sc16raw" else None)
+                                sc16_scale=scale if fmt == "sc16raw" else None,
+                                iq_fmt=fmt[:-3] if fmt in ("sc8raw", "uc8raw") else None, iq_scale=scale)
     ctx.synchronize()
     dt = time.perf_counter() - t0
     stop.set()
@@ -77,7 +86,7 @@ def bench_ingest(ctx, tsdr, iq_host, S, y_t, x_t, seconds=1.0, depth=4, fmt="cf3
     th.join()
     st = ring.stats()
     ring.close()
-    bytes_per_buf = nEch * (8 if fmt == "cf32" else 4)
+    bytes_per_buf = nEch * (8 if fmt == "cf32" else 4 if fmt in ("sc16", "sc16raw") else 2)
     return {"fmt": fmt, "frames_per_s": round(n_done / dt, 1), "msps": round(n_done / nb * nEch / dt / 1e6, 1),
             "pcie_GBs": round(n_done / nb * bytes_per_buf / dt / 1e9, 2), "buffers": n_done // nb, "seconds": round(dt, 3),
             "overflow": st["overflow"], "depth": depth}

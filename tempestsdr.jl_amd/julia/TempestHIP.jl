@@ -19,7 +19,7 @@ export sig_to_image, downgradeImage, naiveResampler, init_resampler
 export calculate_autocorrelation, zoom_autocorr
 export getSpectrum, getWelch, getWaterfall
 export SyncXY, vsync
-export hip_frames!, hip_frames_submit!, hip_frames_submit_sc16!, hip_frames_flush, hip_synchronize   # fused GUI.jl:163-178 loop body (optional fast path; pipelined form)
+export hip_frames!, hip_frames_submit!, hip_frames_submit_sc16!, hip_frames_submit_iq!, hip_frames_flush, hip_synchronize   # fused GUI.jl:163-178 loop body (optional fast path; pipelined form)
 export hip_extract_configuration, sync_guard_stats, sync_guard_auto, wait_stats   # fused GUI.jl:67-81 search; counters of the FAST loop's sync guard
 export hip_set_precision, hip_set_option                              # TSDR_EXACT / TSDR_FAST and the library's options, per task context
 export HipGroup, hip_group                                            # one process, several GPUs (RCCL inside the library): `devices = ...`
@@ -383,6 +383,24 @@ function hip_frames_submit_sc16!(d_imageOut::Ptr{Cvoid}, d_sigId16::Ptr{Cvoid}, 
                         sync.c.h, sync.h, d_sigId16, scale, nEch, S, y_t, x_t, α, do_align ? 1 : 0, d_imageOut, d_frames, d_raster, d_idx, n), "hip_frames_submit_sc16!")
     return Int(n[])
 end
+"""
+    hip_frames_submit_iq!(d_imageOut, d_iq, fmt, scale, nEch, sync, S, y_t, x_t, α; d_frames, ...) -> nb
+
+`hip_frames_submit!` on a device buffer of `nEch` samples of format `fmt` -- `:cf32`, `:sc16` (Int16 pairs), `:sc8` (Int8 pairs:
+HackRF, UHD sc8) or `:uc8` (UInt8 pairs around 127.5: RTL-SDR), e.g. the slots of a `HipRing(...; fmt = :sc8raw)`.  Integer
+samples become `ComplexF32((I - offset) * scale, (Q - offset) * scale)` in the kernels' loaders (offset 127.5 for `:uc8`, else 0),
+so the buffer is never expanded in HBM (`tsdr_frames_submit_iq_d`).
+"""
+function hip_frames_submit_iq!(d_imageOut::Ptr{Cvoid}, d_iq::Ptr{Cvoid}, fmt::Symbol, scale::Float32, nEch::Integer, sync::SyncXY{Float32}, S, y_t, x_t, α::Float32;
+                               d_frames::Ptr{Cvoid}, d_raster::Ptr{Cvoid} = C_NULL, d_idx::Ptr{Cvoid} = C_NULL, do_align = true)
+    haskey(IQ_FORMATS, fmt) || throw(ArgumentError("unknown IQ format $fmt (:cf32, :sc16, :sc8, :uc8)"))
+    n = Ref{Cint}(0)
+    check(sync.c, ccall((:tsdr_frames_submit_iq_d, LIB), Cint,
+                        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cfloat, Csize_t, Csize_t, Cint, Cint, Cfloat, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cint}),
+                        sync.c.h, sync.h, d_iq, IQ_FORMATS[fmt], scale, nEch, S, y_t, x_t, α, do_align ? 1 : 0, d_imageOut, d_frames, d_raster, d_idx, n), "hip_frames_submit_iq!")
+    return Int(n[])
+end
+const IQ_FORMATS = Dict(:cf32 => 0, :sc16 => 1, :sc8 => 2, :uc8 => 3)   # TSDR_IQ_*
 hip_frames_flush() = (c = ctx(); check(c, ccall((:tsdr_frames_flush, LIB), Cint, (Ptr{Cvoid},), c.h), "hip_frames_flush"))
 hip_synchronize() = (c = ctx(); check(c, ccall((:tsdr_synchronize, LIB), Cint, (Ptr{Cvoid},), c.h), "hip_synchronize"))
 
@@ -413,6 +431,38 @@ function hip_extract_configuration(sigId::Vector{ComplexF32}, Fs; delay = 0.1, r
         check(c, ccall((:tsdr_download, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Csize_t), c.h, Γ, d_out, n[] * sizeof(Float32)), "download")
     finally
         ccall((:tsdr_dev_free, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), c.h, d_in)
+        ccall((:tsdr_dev_free, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), c.h, d_out)
+    end
+    xAx = (Int(pmin[]):Int(pmax[])) ./ Fs
+    rates_refresh = 1 ./ xAx
+    Γ_refresh = Γ[Int(pmin[]):Int(pmax[])]
+    fv = 1 / (1 / rates_refresh[Int(idx[]) + 1])                            # GUI.jl:80-81
+    return rates_refresh, Γ_refresh, fv
+end
+"""
+    hip_extract_configuration(d_iq::Ptr{Cvoid}, fmt::Symbol, scale, nEch, Fs; delay = 0.1, rate_min = 50, rate_max = 90)
+
+The same on a raw device buffer of `nEch` samples of format `fmt` (`:sc16`, `:sc8`, `:uc8`; 16-byte aligned, as `take_d!` of a
+raw `HipRing` hands out): the first pass of the search converts the stored integers itself, so the search and the frame loop
+read one ring and nothing is expanded (`tsdr_autocorr_search_iq_d`).
+"""
+function hip_extract_configuration(d_iq::Ptr{Cvoid}, fmt::Symbol, scale::Real, nEch::Integer, Fs; delay = 0.1, rate_min = 50, rate_max = 90)
+    haskey(IQ_FORMATS, fmt) || throw(ArgumentError("unknown IQ format $fmt (:cf32, :sc16, :sc8, :uc8)"))
+    indexMax = round(delay * Fs) |> Int
+    Γ = Vector{Float32}(undef, max(indexMax, 1)); n = Ref{Csize_t}(0); c = ctx()
+    pmin = Ref{Csize_t}(0); pmax = Ref{Csize_t}(0)
+    rc = ccall((:tsdr_zoom_bounds, LIB), Cint, (Csize_t, Cdouble, Cdouble, Cdouble, Ptr{Csize_t}, Ptr{Csize_t}),
+               indexMax, Fs, rate_min, rate_max, pmin, pmax)
+    rc == 0 || throw(BoundsError(Γ, Int(pmin[]):Int(pmax[])))
+    d_out = ccall((:tsdr_dev_alloc, LIB), Ptr{Cvoid}, (Ptr{Cvoid}, Csize_t), c.h, sizeof(Γ))
+    d_out == C_NULL && throw(OutOfMemoryError())
+    idx = Ref{Csize_t}(0); val = Ref{Cfloat}(0)
+    try
+        check(c, ccall((:tsdr_autocorr_search_iq_d, LIB), Cint,
+                       (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cfloat, Csize_t, Cdouble, Cdouble, Cdouble, Cint, Ptr{Cvoid}, Ptr{Csize_t}, Csize_t, Csize_t, Ptr{Csize_t}, Ptr{Cfloat}),
+                       c.h, d_iq, IQ_FORMATS[fmt], Float32(scale), nEch, Fs, 0.0, delay, 1, d_out, n, pmin[] - 1, pmax[] - pmin[] + 1, idx, val), "extract_configuration")
+        check(c, ccall((:tsdr_download, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Csize_t), c.h, Γ, d_out, n[] * sizeof(Float32)), "download")
+    finally
         ccall((:tsdr_dev_free, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), c.h, d_out)
     end
     xAx = (Int(pmin[]):Int(pmax[])) ./ Fs
@@ -571,31 +621,41 @@ end
 
 # ---- streaming ingest: the staging ring (AtomicAbstractSDRs.jl:64-190 on pinned memory) ----------
 """
-    HipRing(c::Ctx, nEch; depth=16, sc16=false, scale=1f0)
+    HipRing(c::Ctx, nEch; depth=16, sc16=false, raw=false, fmt=nothing, scale=1f0)
 
 Pinned-host staging ring with the put/take/overflow semantics of `AtomicCircularBuffer`.  The producer task fills
 `write_slot(ring)` in place (e.g. `recv!(write_slot(ring), sdr)`) and calls `commit!(ring)`; the consumer calls
 `take_d!(ring)` in place of `recv!(buffer, csdr)` and gets a device pointer to hand to `tsdr_frames_d`.
+`fmt = :sc8 | :sc8raw | :uc8 | :uc8raw` (beside `sc16` / `raw`): 8-bit slots, `Int8` pairs or `UInt8` pairs around 127.5, two
+bytes per sample -- expanded on the device to `ComplexF32`, or (`raw`) handed out as stored for `hip_frames_submit_iq!` and
+`hip_extract_configuration(d_iq, fmt, ...)`.  `fmt` also takes `:cf32`, `:sc16`, `:sc16raw`.
 """
 mutable struct HipRing
     c::Ctx
     h::Ptr{Cvoid}
     nEch::Int
     sc16::Bool
+    fmt::Symbol
 end
-function HipRing(c::Ctx, nEch::Integer; depth = 16, sc16 = false, raw = false, scale = 1f0)
-    h = Ref{Ptr{Cvoid}}(C_NULL)   # raw: the Int16 slots stay Int16 on the device (for hip_frames_submit_sc16!)
+const RING_FORMATS = Dict(:cf32 => 0, :sc16 => 1, :sc16raw => 2, :sc8 => 3, :sc8raw => 4, :uc8 => 5, :uc8raw => 6)
+function HipRing(c::Ctx, nEch::Integer; depth = 16, sc16 = false, raw = false, fmt::Union{Symbol,Nothing} = nothing, scale = 1f0)
+    h = Ref{Ptr{Cvoid}}(C_NULL)   # raw: the integer slots stay as they are on the device (for hip_frames_submit_sc16! / _iq!)
+    f = fmt === nothing ? (sc16 ? (raw ? :sc16raw : :sc16) : :cf32) : fmt
+    haskey(RING_FORMATS, f) || throw(ArgumentError("unknown ring format $f"))
     check(c, ccall((:tsdr_ring_create, LIB), Cint, (Ptr{Cvoid}, Csize_t, Cint, Cint, Cfloat, Ptr{Ptr{Cvoid}}),
-                   c.h, nEch, depth, sc16 ? (raw ? 2 : 1) : 0, scale, h), "HipRing")
-    r = HipRing(c, h[], nEch, sc16)
+                   c.h, nEch, depth, RING_FORMATS[f], scale, h), "HipRing")
+    r = HipRing(c, h[], nEch, f in (:sc16, :sc16raw), f)
     finalizer(r) do x
         x.c.h != C_NULL && ccall((:tsdr_ring_free, LIB), Cvoid, (Ptr{Cvoid},), x.h)
     end
     return r
 end
-write_slot(r::HipRing) = r.sc16 ?
-    unsafe_wrap(Array, Ptr{Int16}(ccall((:tsdr_ring_write_ptr, LIB), Ptr{Cvoid}, (Ptr{Cvoid},), r.h)), 2 * r.nEch) :
-    unsafe_wrap(Array, Ptr{ComplexF32}(ccall((:tsdr_ring_write_ptr, LIB), Ptr{Cvoid}, (Ptr{Cvoid},), r.h)), r.nEch)
+function write_slot(r::HipRing)
+    p = ccall((:tsdr_ring_write_ptr, LIB), Ptr{Cvoid}, (Ptr{Cvoid},), r.h)
+    r.fmt in (:sc8, :sc8raw) && return unsafe_wrap(Array, Ptr{Int8}(p), 2 * r.nEch)
+    r.fmt in (:uc8, :uc8raw) && return unsafe_wrap(Array, Ptr{UInt8}(p), 2 * r.nEch)
+    return r.sc16 ? unsafe_wrap(Array, Ptr{Int16}(p), 2 * r.nEch) : unsafe_wrap(Array, Ptr{ComplexF32}(p), r.nEch)
+end
 commit!(r::HipRing) = check(r.c, ccall((:tsdr_ring_commit, LIB), Cint, (Ptr{Cvoid},), r.h), "commit!")
 circ_put!(r::HipRing, data) = check(r.c, ccall((:tsdr_ring_put, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), r.h, data), "circ_put!")
 function take_d!(r::HipRing; timeout_ms = -1)

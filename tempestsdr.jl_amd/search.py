@@ -16,8 +16,23 @@ import numpy as np
 from . import video_configurations as vc
 
 
-def extract_configuration(ctx, iq, Fs, delay_rate=0.1, rate_min=50, rate_max=90):
-    """-> (rates_refresh, G_refresh, fv, G) with the reference's conventions (incl. the zoom off-by-one)."""
+def extract_configuration(ctx, iq, Fs, delay_rate=0.1, rate_min=50, rate_max=90, *, iq_fmt=None, iq_scale=1.0, n_samples=None):
+    """-> (rates_refresh, G_refresh, fv, G) with the reference's conventions (incl. the zoom off-by-one).
+    iq_fmt "sc16" / "sc8" / "uc8": iq is integer IQ as a raw staging ring holds it -- an integer array of 2*n interleaved
+    components, or the device address StagingRing.take_d returned with n_samples = n -- read as it is stored by the search's
+    first pass (Context.autocorr_search); nothing is expanded."""
+    if iq_fmt is not None:
+        dev = isinstance(iq, (int, np.integer)) and not isinstance(iq, bool)
+        n = int(n_samples) if dev and n_samples is not None else (0 if dev else np.asarray(iq).size // 2)
+        index_max = int(np.round(delay_rate * Fs))
+        if n < index_max:
+            raise IndexError("capture shorter than the autocorrelation window (BoundsError in the reference)")
+        G, _, _ = ctx.autocorr_search(iq, Fs, 0, delay_rate, rate_min=rate_min, rate_max=rate_max, iq_fmt=iq_fmt, iq_scale=iq_scale,
+                                      n_samples=n_samples)
+        rates, Gz = ctx.zoom_autocorr(G, Fs, rate_min=rate_min, rate_max=rate_max)
+        pos = int(np.argmax(Gz))
+        fv = 1.0 / (1.0 / rates[pos])
+        return rates, Gz, fv, G
     iq = np.ascontiguousarray(iq)
     index_max = int(np.round(delay_rate * Fs))                      # GUI.jl:60
     if iq.size < index_max:
