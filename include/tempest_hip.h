@@ -21,6 +21,18 @@
  *               synchronises.  This is what the Julia shim binds.
  *    `name_d` : device pointers (hipMalloc / torch data_ptr); enqueued asynchronously
  *               on the context's stream, no synchronisation.
+ *  - POINTER ALIGNMENT of the `name_d` forms: every device pointer is aligned to ONE ELEMENT of what it points to -- 4 bytes
+ *    for float / int, 8 for ComplexF32 (interleaved float pairs) and double, 16 for ComplexF64, 8 for the 64-bit key words of
+ *    tsdr_frames_scan_d / _combine_d, one sample for integer IQ unless the entry point says more -- and nothing beyond that:
+ *    `base + k * sizeof(element)` of a larger buffer (a tensor slice, a ring slot, one frame of a capture) is a valid
+ *    argument for every k, input and output independently, and gives the results of a fresh allocation (bit for bit
+ *    where the entry point promises bits; within its stated tolerance where a less aligned pointer takes another transform
+ *    route, as an odd-sample IQ pointer does in tsdr_autocorr_iq_d / _search_d and a real pointer at an odd float in
+ *    tsdr_resampler_run_d).  A pointer that is NOT aligned to one element is refused with TSDR_EINVAL on the host, with the
+ *    argument's name in tsdr_last_error, BEFORE anything is enqueued: every Float32 `name_d` entry point checks every pointer
+ *    it takes; the `name_f64_d` forms check their ComplexF64 inputs (and the demodulators their outputs), a Float64 pointer is
+ *    the caller's to keep 8-byte aligned.  No entry point writes outside the elements it documents as output, or writes its
+ *    input.
  *  - one tsdr_ctx per caller thread (the reference calls the frame path and the
  *    configuration search from two different tasks, GUI.jl:381 vs :411-419).
  *  - there is NO CPU fallback: tsdr_create returns NULL when no HIP device is usable.
@@ -184,7 +196,9 @@ int tsdr_profile_count(tsdr_ctx *ctx); /* synchronises; number of distinct kerne
 int tsdr_profile_get(tsdr_ctx *ctx, int idx, char *name, size_t cap, double *total_ms, long long *launches);
 
 /* ---- Demodulation.jl ----------------------------------------------------------- */
-/* amDemod(sig) = abs.(sig)                              Demodulation.jl:26-28 */
+/* amDemod(sig) = abs.(sig)                              Demodulation.jl:26-28
+ * _d forms of amDemod / invert_amDemod / abs2: iq and out both 16-byte aligned take the kernel that moves 16-byte vectors; any
+ * other element-aligned pair (iq at 8 mod 16, out at 4 / 8 / 12 mod 16) takes a one-sample-per-lane kernel: the same bits. */
 int tsdr_am_demod(tsdr_ctx *ctx, const float *iq, size_t n, float *out);
 int tsdr_am_demod_d(tsdr_ctx *ctx, const float *iq, size_t n, float *out);
 /* invert_amDemod(sig) = 1 .- abs/maximum(abs)           Demodulation.jl:31-35 */

@@ -314,6 +314,8 @@ extern "C" {
 static int autocorr_any_d(tsdr_ctx *ctx, const float *x, int is_iq, size_t len, double Fs, double minDelay, double maxDelay,
                           int log_scale, float *out, size_t *n_out) {
   if (!ctx || !x || !out) return TSDR_EINVAL;
+  TSDR_PTR_ALIGNED(ctx, "autocorr", x, is_iq ? 8 : 4);
+  TSDR_PTR_ALIGNED(ctx, "autocorr", out, 4);
   size_t n, k0, cnt;
   int rc = autocorr_args(ctx, len, Fs, minDelay, maxDelay, &n, &k0, &cnt);
   if (rc) return rc;
@@ -347,6 +349,8 @@ int tsdr_autocorr(tsdr_ctx *ctx, const float *x, size_t len, double Fs, double m
 int tsdr_autocorr_partial_d(tsdr_ctx *ctx, const float *x, int is_iq, size_t n, size_t m0, size_t cnt, size_t n_lags,
                             float *part) {
   if (!ctx || !x || !part) return TSDR_EINVAL;
+  TSDR_PTR_ALIGNED(ctx, "autocorr_partial", x, is_iq ? 8 : 4);
+  TSDR_PTR_ALIGNED(ctx, "autocorr_partial", part, 4);
   if (n == 0 || cnt == 0 || n_lags == 0 || m0 >= n || cnt > n || n_lags > n) return set_err(ctx, TSDR_EINVAL, "autocorr_partial: bad range");
   const size_t vlen = cnt + n_lags - 1;
   const int logM = ilog2(vlen);
@@ -367,6 +371,8 @@ int tsdr_autocorr_partial_d(tsdr_ctx *ctx, const float *x, int is_iq, size_t n, 
 
 int tsdr_autocorr_finish_d(tsdr_ctx *ctx, const float *corr, size_t k0, size_t cnt, int log_scale, float *out) {
   if (!ctx || (cnt && (!corr || !out))) return TSDR_EINVAL;
+  TSDR_PTR_ALIGNED(ctx, "autocorr_finish", corr, 4);
+  TSDR_PTR_ALIGNED(ctx, "autocorr_finish", out, 4);
   if (cnt == 0) return TSDR_OK;
   TSDR_LAUNCH(ctx, "ac_finish", k_ac_finish, dim3(stream_grid(ctx, cnt)), dim3(256), 0, corr, k0, cnt, log_scale, out);
   return TSDR_OK;
@@ -451,6 +457,7 @@ static int argmax_launch(tsdr_ctx *ctx, const float *v, size_t n, const AmaxReq 
 
 int tsdr_argmax_d(tsdr_ctx *ctx, const float *v, size_t n, size_t *idx, float *val) {
   if (!ctx || !v || !idx || n == 0) return TSDR_EINVAL;  // findmax of an empty collection throws
+  TSDR_PTR_ALIGNED(ctx, "argmax", v, 4);
   if (n >= (size_t(1) << 32)) return set_err(ctx, TSDR_EINVAL, "argmax: vector too long");
   AmaxReq r;
   int rc = amax_begin(ctx, &r);
@@ -465,6 +472,9 @@ static int autocorr_search_any_d(tsdr_ctx *ctx, const float *x, int is_iq, float
                                  double maxDelay, int log_scale, float *out, size_t *n_out, size_t win_lo, size_t win_cnt, size_t *idx,
                                  float *val) {
   if (!ctx || !x || !out || !idx) return TSDR_EINVAL;
+  // (integer IQ: is_iq >= 2, its 16-byte rule is the caller's, tsdr_autocorr_search_iq_d)
+  TSDR_PTR_ALIGNED(ctx, "autocorr_search", x, is_iq == 1 ? 8 : 4);
+  TSDR_PTR_ALIGNED(ctx, "autocorr_search", out, 4);
   size_t n, k0, cnt;
   int rc = autocorr_args(ctx, len, Fs, minDelay, maxDelay, &n, &k0, &cnt);
   if (rc) return rc;

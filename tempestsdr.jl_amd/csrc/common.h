@@ -239,6 +239,15 @@ void prof_end(tsdr_ctx *ctx);
     if (_le != hipSuccess) return tsdr::hip_fail((ctx), _le, kname);                          \
   } while (0)
 
+// The pointer rule of every device-pointer entry point (tempest_hip.h, Conventions): a pointer is aligned to one element of
+// what it points to -- 4 bytes for float / int, 8 for ComplexF32 / double, 16 for ComplexF64 -- or the call is refused on the
+// host, before anything is enqueued.  What a kernel may assume beyond that (16-byte vectors) it has to check for itself.
+#define TSDR_PTR_ALIGNED(ctx, fn, p, elem)                                                                     \
+  do {                                                                                                         \
+    if (reinterpret_cast<uintptr_t>(p) & (uintptr_t)((elem) - 1))                                              \
+      return tsdr::set_err((ctx), TSDR_EINVAL, "%s: %s is not aligned to one element (%d bytes)", fn, #p, (int)(elem)); \
+  } while (0)
+
 static inline size_t ceil_div(size_t a, size_t b) { return (a + b - 1) / b; }
 
 // grid for a capped, grid-strided streaming kernel of 256-thread workgroups

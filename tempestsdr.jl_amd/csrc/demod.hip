@@ -53,6 +53,26 @@ __global__ __launch_bounds__(256) void k_demod(const float4 *__restrict__ iq, si
   }
 }
 
+// The same, one sample per lane: for the pointers k_demod's 16-byte vectors cannot take (an IQ buffer that starts at an odd
+// sample of a larger one, an output at any float of a larger one).  One 8-byte load and one 4-byte store per sample; the
+// values -- and so the maximum -- are those of k_demod bit for bit.
+template <int MODE, bool TRACK_MAX>
+__global__ __launch_bounds__(256) void k_demod1(const float2 *__restrict__ iq, size_t n, float *__restrict__ out,
+                                                unsigned *__restrict__ maxbits) {
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  unsigned local = 0u;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const float2 s = iq[i];
+    const float v = demod1<MODE>(s.x, s.y);
+    out[i] = v;
+    if (TRACK_MAX) local = max(local, __float_as_uint(v));
+  }
+  if (TRACK_MAX) {
+    for (int off = 32; off > 0; off >>= 1) local = max(local, (unsigned)__shfl_xor((int)local, off, 64));
+    if ((threadIdx.x & 63) == 0) atomicMax(maxbits, local);
+  }
+}
+
 // out = 1 - out/max   (f32, correctly rounded division, two roundings)
 __global__ __launch_bounds__(256) void k_invert(float *__restrict__ out, size_t n, const unsigned *__restrict__ maxbits) {
   const float mx = __uint_as_float(*maxbits);
@@ -75,14 +95,24 @@ __global__ __launch_bounds__(256) void k_fm(const float2 *__restrict__ iq, size_
   }
 }
 
+// k_demod moves 16-byte vectors on both sides; any other element-aligned pair of pointers takes k_demod1
+static inline bool vec16(const float *iq, const float *out) {
+  return ((reinterpret_cast<uintptr_t>(iq) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0;
+}
+
 template <int MODE>
 static int demod_d(tsdr_ctx *ctx, const char *kname, const float *iq, size_t n, float *out) {
   if (!ctx || (n && (!iq || !out))) return TSDR_EINVAL;
+  TSDR_PTR_ALIGNED(ctx, kname, iq, 8);
+  TSDR_PTR_ALIGNED(ctx, kname, out, 4);
   if (n == 0) return TSDR_OK;
-  if (((uintptr_t)iq & 15) || ((uintptr_t)out & 15)) return set_err(ctx, TSDR_EINVAL, "%s: buffers must be 16-byte aligned", kname);
-  int grid = stream_grid(ctx, ceil_div(n, 4));
-  TSDR_LAUNCH(ctx, MODE == DM_ABS ? "am_demod" : "abs2", (k_demod<MODE, false>), dim3(grid), dim3(256), 0,
-              reinterpret_cast<const float4 *>(iq), n, reinterpret_cast<float4 *>(out), (unsigned *)nullptr);
+  if (vec16(iq, out)) {
+    TSDR_LAUNCH(ctx, MODE == DM_ABS ? "am_demod" : "abs2", (k_demod<MODE, false>), dim3(stream_grid(ctx, ceil_div(n, 4))), dim3(256), 0,
+                reinterpret_cast<const float4 *>(iq), n, reinterpret_cast<float4 *>(out), (unsigned *)nullptr);
+  } else {
+    TSDR_LAUNCH(ctx, MODE == DM_ABS ? "am_demod1" : "abs2_1", (k_demod1<MODE, false>), dim3(stream_grid(ctx, n)), dim3(256), 0,
+                reinterpret_cast<const float2 *>(iq), n, out, (unsigned *)nullptr);
+  }
   return TSDR_OK;
 }
 
@@ -97,19 +127,26 @@ int tsdr_abs2_d(tsdr_ctx *ctx, const float *iq, size_t n, float *out) { return d
 
 int tsdr_invert_am_d(tsdr_ctx *ctx, const float *iq, size_t n, float *out) {
   if (!ctx || n == 0 || !iq || !out) return TSDR_EINVAL;  // maximum() of an empty collection throws
-  if (((uintptr_t)iq & 15) || ((uintptr_t)out & 15)) return set_err(ctx, TSDR_EINVAL, "invert_am: buffers must be 16-byte aligned");
+  TSDR_PTR_ALIGNED(ctx, "invert_am", iq, 8);
+  TSDR_PTR_ALIGNED(ctx, "invert_am", out, 4);
   unsigned *mx = (unsigned *)ctx->scratch(WS_MISC, 16);
   if (!mx) return TSDR_ENOMEM;
   TSDR_HIP(ctx, hipMemsetAsync(mx, 0, 4, ctx->stream));
-  int grid = stream_grid(ctx, ceil_div(n, 4));
-  TSDR_LAUNCH(ctx, "invert_am_abs", (k_demod<DM_ABS, true>), dim3(grid), dim3(256), 0,
-              reinterpret_cast<const float4 *>(iq), n, reinterpret_cast<float4 *>(out), mx);
+  if (vec16(iq, out)) {
+    TSDR_LAUNCH(ctx, "invert_am_abs", (k_demod<DM_ABS, true>), dim3(stream_grid(ctx, ceil_div(n, 4))), dim3(256), 0,
+                reinterpret_cast<const float4 *>(iq), n, reinterpret_cast<float4 *>(out), mx);
+  } else {
+    TSDR_LAUNCH(ctx, "invert_am_abs1", (k_demod1<DM_ABS, true>), dim3(stream_grid(ctx, n)), dim3(256), 0,
+                reinterpret_cast<const float2 *>(iq), n, out, mx);
+  }
   TSDR_LAUNCH(ctx, "invert_am_scale", k_invert, dim3(stream_grid(ctx, n)), dim3(256), 0, out, n, (const unsigned *)mx);
   return TSDR_OK;
 }
 
 int tsdr_fm_demod_d(tsdr_ctx *ctx, const float *iq, size_t n, float *out) {
   if (!ctx || (n && (!iq || !out))) return TSDR_EINVAL;
+  TSDR_PTR_ALIGNED(ctx, "fm_demod", iq, 8);
+  TSDR_PTR_ALIGNED(ctx, "fm_demod", out, 4);
   if (n == 0) return TSDR_OK;
   TSDR_LAUNCH(ctx, "fm_demod", k_fm, dim3(stream_grid(ctx, n)), dim3(256), 0, reinterpret_cast<const float2 *>(iq), n, out);
   return TSDR_OK;

@@ -512,7 +512,7 @@ static int get_bluestein(tsdr_ctx *ctx, size_t n, BluesteinPlan **out) {
 int fft_any(tsdr_ctx *ctx, const float *x, int is_complex, float2 *out, size_t n, size_t batch, int dir) {
   if (n == 0 || batch == 0) return TSDR_OK;
   const int d = dir < 0 ? -1 : 1;
-  if (is_complex && batch > 1 && (reinterpret_cast<uintptr_t>(x) & 7u) == 0) {  // rows of 257 .. 4096 points: one launch, on chip
+  if (is_complex && batch > 1) {  // rows of 257 .. 4096 points: one launch, on chip
     if (n == 1024) return fft_rows1024(ctx, reinterpret_cast<const float2 *>(x), out, batch, d, d > 0 ? (float)(1.0 / 1024.0) : 1.0f);
     bool did = false;
     int rcr = fft_rows_store(ctx, reinterpret_cast<const float2 *>(x), out, n, batch, d, d > 0 ? (float)(1.0 / (double)n) : 1.0f, &did);
@@ -566,6 +566,8 @@ extern "C" {
 
 int tsdr_fft_c2c_d(tsdr_ctx *ctx, const float *in, float *out, size_t n, size_t batch, int dir) {
   if (!ctx || ((n * batch) && (!in || !out))) return TSDR_EINVAL;
+  TSDR_PTR_ALIGNED(ctx, "fft_c2c", in, 8);
+  TSDR_PTR_ALIGNED(ctx, "fft_c2c", out, 8);
   return fft_any(ctx, in, 1, reinterpret_cast<float2 *>(out), n, batch, dir);
 }
 

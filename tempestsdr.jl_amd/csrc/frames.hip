@@ -229,6 +229,10 @@ int tsdr_frames_scan_d(tsdr_ctx *ctx, tsdr_sync *sync, const float *iq, size_t n
   if (nEch && !iq) return TSDR_EINVAL;
   int rc = frames_check(ctx, sync, do_align);
   if (rc) return rc;
+  TSDR_PTR_ALIGNED(ctx, "frames_scan", iq, iq_bytes(ctx->iq_fmt));
+  TSDR_PTR_ALIGNED(ctx, "frames_scan", img_out, 4);
+  TSDR_PTR_ALIGNED(ctx, "frames_scan", raster_out, 4);
+  TSDR_PTR_ALIGNED(ctx, "frames_scan", keys_out, 8);
   rc = pipe_drain(ctx);  // a pipelined submission on this context comes first (its SyncXY / image slots are in use)
   if (rc) return rc;
   const size_t nb = nEch / S;
@@ -246,6 +250,11 @@ int tsdr_frames_combine_d(tsdr_ctx *ctx, tsdr_sync *sync, const float *img, cons
   if (!ctx || !imageOut_state || n_frames < 0) return TSDR_EINVAL;
   int rc = frames_check(ctx, sync, do_align);
   if (rc) return rc;
+  TSDR_PTR_ALIGNED(ctx, "frames_combine", img, 4);
+  TSDR_PTR_ALIGNED(ctx, "frames_combine", keys, 8);
+  TSDR_PTR_ALIGNED(ctx, "frames_combine", imageOut_state, 4);
+  TSDR_PTR_ALIGNED(ctx, "frames_combine", frames_out, 4);
+  TSDR_PTR_ALIGNED(ctx, "frames_combine", sync_idx, 4);
   rc = pipe_drain(ctx);
   if (rc) return rc;
   if (n_frames == 0) return TSDR_OK;
@@ -259,6 +268,11 @@ int tsdr_frames_d(tsdr_ctx *ctx, tsdr_sync *sync, const float *iq, size_t nEch, 
                   int *n_frames) {
   if (!ctx || !imageOut_state || S == 0 || y_t <= 0 || x_t <= 0) return TSDR_EINVAL;
   if (int rc = sync_f32_check(ctx, sync)) return rc;
+  TSDR_PTR_ALIGNED(ctx, "frames", iq, iq_bytes(ctx->iq_fmt));
+  TSDR_PTR_ALIGNED(ctx, "frames", imageOut_state, 4);
+  TSDR_PTR_ALIGNED(ctx, "frames", frames_out, 4);
+  TSDR_PTR_ALIGNED(ctx, "frames", raster_out, 4);
+  TSDR_PTR_ALIGNED(ctx, "frames", sync_idx, 4);
   const size_t nb = nEch / S;
   if (nb > (size_t)1 << 20) return set_err(ctx, TSDR_EINVAL, "too many frames in one buffer");
   if (ctx->pipe_n) {  // buffers submitted through the pipeline come first (SyncXY and imageOut state are sequential)
@@ -466,6 +480,11 @@ int tsdr_frames_submit_d(tsdr_ctx *ctx, tsdr_sync *sync, const float *iq, size_t
   if (nEch && !iq) return TSDR_EINVAL;
   int rc = frames_check(ctx, sync, do_align);
   if (rc) return rc;
+  TSDR_PTR_ALIGNED(ctx, "frames_submit", iq, iq_bytes(ctx->iq_fmt));
+  TSDR_PTR_ALIGNED(ctx, "frames_submit", imageOut_state, 4);
+  TSDR_PTR_ALIGNED(ctx, "frames_submit", frames_out, 4);
+  TSDR_PTR_ALIGNED(ctx, "frames_submit", raster_out, 4);
+  TSDR_PTR_ALIGNED(ctx, "frames_submit", sync_idx, 4);
   const size_t nb = nEch / S;
   if (nb > (size_t)1 << 20) return set_err(ctx, TSDR_EINVAL, "too many frames in one buffer");
   if (n_frames) *n_frames = (int)nb;

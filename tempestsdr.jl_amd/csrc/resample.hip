@@ -1671,6 +1671,8 @@ extern "C" {
 
 int tsdr_resize1d_d(tsdr_ctx *ctx, const float *sig, size_t n_in, size_t n_out, float *out) {
   if (!ctx || (n_out && (!sig || !out))) return TSDR_EINVAL;
+  TSDR_PTR_ALIGNED(ctx, "resize1d", sig, 4);
+  TSDR_PTR_ALIGNED(ctx, "resize1d", out, 4);
   if (n_out == 0) return TSDR_OK;
   if (n_in != n_out && n_in < 2) return set_err(ctx, TSDR_EINVAL, "imresize needs at least 2 input samples");
   TSDR_LAUNCH(ctx, "resize1d", k_resize1d, dim3(stream_grid(ctx, n_out)), dim3(256), 0, sig, n_in, n_out, out);
@@ -1679,11 +1681,15 @@ int tsdr_resize1d_d(tsdr_ctx *ctx, const float *sig, size_t n_in, size_t n_out, 
 
 int tsdr_sig_to_image_d(tsdr_ctx *ctx, const float *sig, size_t S, int y_t, int x_t, float *img) {
   if (!ctx || !sig || !img) return TSDR_EINVAL;
+  TSDR_PTR_ALIGNED(ctx, "sig_to_image", sig, 4);
+  TSDR_PTR_ALIGNED(ctx, "sig_to_image", img, 4);
   return raster_frames_d(ctx, sig, 0, S, S, y_t, x_t, 1, img, (size_t)y_t * x_t);
 }
 
 int tsdr_resize2d_d(tsdr_ctx *ctx, const float *img, int h_in, int w_in, int h_out, int w_out, float *out) {
   if (!ctx || !img || !out) return TSDR_EINVAL;
+  TSDR_PTR_ALIGNED(ctx, "resize2d", img, 4);
+  TSDR_PTR_ALIGNED(ctx, "resize2d", out, 4);
   return resize2d_d(ctx, img, h_in, w_in, h_out, w_out, out);
 }
 
@@ -1693,6 +1699,8 @@ int tsdr_downgrade_d(tsdr_ctx *ctx, const float *img, int y_t, int x_t, float *o
 
 int tsdr_naive_resample_d(tsdr_ctx *ctx, const float *in, size_t n, int up, float *out) {
   if (!ctx || up < 1 || (n && (!in || !out))) return TSDR_EINVAL;
+  TSDR_PTR_ALIGNED(ctx, "naive_resample", in, 4);
+  TSDR_PTR_ALIGNED(ctx, "naive_resample", out, 4);
   if (n == 0) return TSDR_OK;
   TSDR_LAUNCH(ctx, "naive_resample", k_naive, dim3(stream_grid(ctx, n * (size_t)up)), dim3(256), 0, in, n * (size_t)up,
               (unsigned)up, out);

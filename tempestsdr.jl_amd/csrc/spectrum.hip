@@ -443,7 +443,7 @@ static int spectrum_d(tsdr_ctx *ctx, const float *sig, int is_complex, size_t N,
   // 16 wavefronts of ~2600 instructions share one CU -- 20 us of issue before any latency.  NOTEBOOK.md.)
   float2 *X = (float2 *)ctx->scratch(WS_FFT_A, N * sizeof(float2));
   if (!X) return TSDR_ENOMEM;
-  if (fft_passes(N) >= 2 && (reinterpret_cast<uintptr_t>(sig) & (is_complex ? 7u : 3u)) == 0) {
+  if (fft_passes(N) >= 2) {
     // the passes alone: a real signal enters through the first pass's loader, abs2 / 10log10 and the fftshift leave
     // through the last pass's epilogue
     FftEpilogue epi;
@@ -480,6 +480,8 @@ extern "C" {
 
 int tsdr_spectrum_d(tsdr_ctx *ctx, const float *sig, int is_complex, size_t N, int lin, float *y) {
   if (!ctx || (N && (!sig || !y))) return TSDR_EINVAL;
+  TSDR_PTR_ALIGNED(ctx, "spectrum", sig, is_complex ? 8 : 4);
+  TSDR_PTR_ALIGNED(ctx, "spectrum", y, 4);
   return spectrum_d(ctx, sig, is_complex, N, lin, y);
 }
 
@@ -515,8 +517,9 @@ extern "C" {
 
 int tsdr_welch_d(tsdr_ctx *ctx, const float *sig, int is_complex, size_t len, size_t sizeFFT, int lin, float *y) {
   if (!ctx || !y || (len && !sig)) return TSDR_EINVAL;
-  if (sizeFFT == (size_t)kSegN && len / sizeFFT > 0 && len / sizeFFT < (size_t(1) << 31) &&
-      (reinterpret_cast<uintptr_t>(sig) & (is_complex ? 7u : 3u)) == 0) {
+  TSDR_PTR_ALIGNED(ctx, "welch", sig, is_complex ? 8 : 4);
+  TSDR_PTR_ALIGNED(ctx, "welch", y, 4);
+  if (sizeFFT == (size_t)kSegN && len / sizeFFT > 0 && len / sizeFFT < (size_t(1) << 31)) {
     const size_t nbSeg = len / sizeFFT;
     unsigned blocks = 0;
     const unsigned nwaves = seg_waves(ctx, nbSeg, &blocks);
@@ -532,7 +535,7 @@ int tsdr_welch_d(tsdr_ctx *ctx, const float *sig, int is_complex, size_t len, si
     TSDR_LAUNCH(ctx, "welch_finish", k_welch_finish, dim3(kSegN / 16), dim3(256), 0, (const float *)part, blocks, lin, y);
     return TSDR_OK;
   }
-  if (sizeFFT >= 2 && sizeFFT <= 4096 && len / sizeFFT > 0 && (reinterpret_cast<uintptr_t>(sig) & (is_complex ? 7u : 3u)) == 0) {
+  if (sizeFFT >= 2 && sizeFFT <= 4096 && len / sizeFFT > 0) {
     // any other 2^a 3^b 5^c segment length that fits one workgroup's LDS: the segment transforms stay on the chip too --
     // every workgroup adds abs2 of the spectra it forms and leaves one partial sum (round 4: the segment spectra of this
     // route used to go through HBM, 5.1x the algorithmic traffic)
@@ -575,8 +578,9 @@ int tsdr_welch(tsdr_ctx *ctx, const float *sig, int is_complex, size_t len, size
 
 int tsdr_waterfall_d(tsdr_ctx *ctx, const float *sig, int is_complex, size_t len, size_t sizeFFT, double *sMatrix) {
   if (!ctx || (len && !sig)) return TSDR_EINVAL;
-  if (sizeFFT == (size_t)kSegN && len / sizeFFT > 0 && len / sizeFFT < (size_t(1) << 31) && sMatrix &&
-      (reinterpret_cast<uintptr_t>(sig) & (is_complex ? 7u : 3u)) == 0) {
+  TSDR_PTR_ALIGNED(ctx, "waterfall", sig, is_complex ? 8 : 4);
+  TSDR_PTR_ALIGNED(ctx, "waterfall", sMatrix, 8);
+  if (sizeFFT == (size_t)kSegN && len / sizeFFT > 0 && len / sizeFFT < (size_t(1) << 31) && sMatrix) {
     const size_t nbSeg = len / sizeFFT;
     unsigned blocks = 0;
     const unsigned nwaves = seg_waves(ctx, nbSeg, &blocks);
@@ -589,7 +593,7 @@ int tsdr_waterfall_d(tsdr_ctx *ctx, const float *sig, int is_complex, size_t len
     }
     return TSDR_OK;
   }
-  if (sizeFFT && sMatrix && len / sizeFFT > 0 && (reinterpret_cast<uintptr_t>(sig) & (is_complex ? 7u : 3u)) == 0) {
+  if (sizeFFT && sMatrix && len / sizeFFT > 0) {
     bool did = false;
     int rcw = fft_rows_waterfall(ctx, sig, is_complex, sizeFFT, len / sizeFFT, sMatrix, &did);
     if (rcw || did) return rcw;
@@ -725,6 +729,8 @@ int tsdr_resampler_run_d(tsdr_resampler *r, const float *in, size_t n_in, float 
   tsdr_ctx *ctx = r->ctx;
   if (r->f64) return set_err(ctx, TSDR_EINVAL, "resampler!: a Float64 resampler takes Float64 buffers (tsdr_resampler_run_f64)");
   if (n_in != r->bufferSize) return set_err(ctx, TSDR_EINVAL, "Size of input %zu should match size used during init %zu", n_in, r->bufferSize);
+  TSDR_PTR_ALIGNED(ctx, "resampler!", in, 4);
+  TSDR_PTR_ALIGNED(ctx, "resampler!", out, 4);
   const size_t N = r->sizeFFT;
   if (N == 4096) {  // one workgroup, one launch
     int rc = ensure_tw_small(ctx);

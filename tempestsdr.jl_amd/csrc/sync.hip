@@ -1042,6 +1042,8 @@ int tsdr_vsync_d(tsdr_sync *s, const float *img, int *s_yx_dev) {
   if (!s || !img) return TSDR_EINVAL;
   tsdr_ctx *ctx = s->ctx;
   if (s->f64) return set_err(ctx, TSDR_EINVAL, "tsdr_vsync_d: SyncXY{Float64} state (use tsdr_vsync_f64_d)");
+  TSDR_PTR_ALIGNED(ctx, "vsync", img, 4);
+  TSDR_PTR_ALIGNED(ctx, "vsync", s_yx_dev, 4);
   {
     int rc = pipe_drain(ctx);
     if (rc) return rc;
