@@ -72,8 +72,8 @@ struct tsdr_ctx {
   hipStream_t launch_stream = nullptr;  // stream TSDR_LAUNCH targets (== stream)
   std::string err;
   int cu_count = 0;
-  int precision = TSDR_FAST;  // tsdr_precision
-  tsdr::IqFmt iq_fmt;         // set for the duration of a tsdr_frames_sc16* / tsdr_frames_iq_d call
+  int precision = TSDR_FAST;  // tsdr_precision: written by tsdr_set_precision only (a buffer that has to run in TSDR_EXACT
+                              // carries that in its frames.hip:FrameJob, as it carries its IQ format)
   // development switches (tsdr_set_option; environment variables of the same upper-case names are read ONCE, in tsdr_create)
   int opt_ac_mixed = 1;     // autocorrelation of n = 2*(2^a3^b5^c) samples: native mixed-radix route (0: zero-padded power of two)
   int opt_fft_no_mix2 = 0;  // 1: every mixed-radix factor through the generic LDS-stage kernel
@@ -174,8 +174,7 @@ struct tsdr_ctx {
   int opt_pipe_lanes = 2;           // equal lanes of the forced arrangement 1: 2 or 3
   int opt_pipe_priority = 1;        // forced arrangement 0: the tail lane is a stream of the highest priority
   int opt_pipe_ext_event = 1;       // 1: a buffer's tail event rides on its shift + IIR dispatch (hipExtLaunchKernelGGL's stop event) instead of
-                                    // a marker packet of its own behind it
-  hipEvent_t launch_stop_ev = nullptr;  // set by the pipeline for the next shift + IIR launch, cleared by it
+                                    // a marker packet of its own behind it (the event is an argument of sync.hip:shift_iir_d)
   int opt_pipe_dev_events = 1;      // the pipeline's hand-over events release to device scope (TSDR_PIPE_DEV_EVENTS=0: the default system scope; A/B)
   int opt_pipe_tune = 1;            // 0: "pipe_mode" -1 means arrangement 0 with rasters, 1 without (rounds 1-4), nothing is measured
   struct PipeTune {                 // the measured choice for one PipeKey

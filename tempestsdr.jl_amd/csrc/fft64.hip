@@ -124,24 +124,17 @@ int fft64_d(tsdr_ctx *ctx, double2 *data, double2 *scratch, size_t N, int dir) {
   }
   std::vector<unsigned> two;
   for (size_t v = L; v > 1; v >>= 1) two.push_back(2u);
-  auto checked = [&](const char *what) {   // a launch failure must surface here, not as the sticky error of a later, unrelated launch
-    const hipError_t le = hipGetLastError();
-    return le == hipSuccess ? (int)TSDR_OK : hip_fail(ctx, le, what);
-  };
-  hipLaunchKernelGGL(k_blue64_prep, dim3(stream_grid(ctx, L)), dim3(256), 0, ctx->launch_stream, (const double2 *)data, N, L, sign, a, b);
-  int rc = checked("fft64: k_blue64_prep");
-  if (!rc) rc = smooth_passes(ctx, a, t, L, two, -1.0);
-  if (!rc) rc = smooth_passes(ctx, b, t, L, two, -1.0);
-  if (!rc) {
-    hipLaunchKernelGGL(k_mul64, dim3(stream_grid(ctx, L)), dim3(256), 0, ctx->launch_stream, a, (const double2 *)b, L);
-    rc = checked("fft64: k_mul64");
-    if (!rc) rc = smooth_passes(ctx, a, t, L, two, +1.0);
-  }
-  if (!rc) {
+  auto convolve = [&]() -> int {   // (a failure leaves through the clean-up below)
+    TSDR_LAUNCH(ctx, "fft64_blue_prep", k_blue64_prep, dim3(stream_grid(ctx, L)), dim3(256), 0, (const double2 *)data, N, L, sign, a, b);
+    if (int rc = smooth_passes(ctx, a, t, L, two, -1.0)) return rc;
+    if (int rc = smooth_passes(ctx, b, t, L, two, -1.0)) return rc;
+    TSDR_LAUNCH(ctx, "fft64_blue_mul", k_mul64, dim3(stream_grid(ctx, L)), dim3(256), 0, a, (const double2 *)b, L);
+    if (int rc = smooth_passes(ctx, a, t, L, two, +1.0)) return rc;
     const double g = (1.0 / (double)L) * (dir > 0 ? 1.0 / (double)N : 1.0);
-    hipLaunchKernelGGL(k_blue64_post, dim3(stream_grid(ctx, N)), dim3(256), 0, ctx->launch_stream, (const double2 *)a, N, sign, g, data);
-    rc = checked("fft64: k_blue64_post");
-  }
+    TSDR_LAUNCH(ctx, "fft64_blue_post", k_blue64_post, dim3(stream_grid(ctx, N)), dim3(256), 0, (const double2 *)a, N, sign, g, data);
+    return TSDR_OK;
+  };
+  const int rc = convolve();
   // (a stream that never completes keeps its scratch: hipFree would wait for the device without a bound)
   if (int w = tsdr::wait_stream(ctx, ctx->stream, "fft64")) return rc ? rc : w;
   (void)hipFree(a); (void)hipFree(b); (void)hipFree(t);

@@ -24,14 +24,13 @@ namespace tsdr {
 // (TSDR_FAST in-walk sums) and clear the two argmax keys of every frame in `keys`; *got then describes the sums
 // (ncp == 0: nothing was produced, keys untouched).  plan_only: no launch, only report in *got what a real call would
 // produce.
-int raster_and_down_d(tsdr_ctx *ctx, const float *in, int cplx, size_t in_stride, size_t S, int y_t, int x_t, int h_out,
-                      int w_out, int frames, float *raster, size_t raster_stride, float *down, size_t down_stride,
-                      float *proj = nullptr, ProjLayout *got = nullptr, bool plan_only = false,
-                      unsigned long long *keys = nullptr);
+int raster_and_down_d(tsdr_ctx *ctx, const float *in, int cplx, IqFmt iqf, int precision, size_t in_stride, size_t S, int y_t, int x_t,
+                      int h_out, int w_out, int frames, float *raster, size_t raster_stride, float *down, size_t down_stride,
+                      float *proj, ProjLayout *got, bool plan_only, unsigned long long *keys);
 int sync_scan_d(tsdr_sync *s, const float *img, size_t img_stride, int frames, unsigned long long *keys, float *proj,
                 const ProjLayout *have, uint2 *top2);
 void sync_beta_blocks(const tsdr_sync *s, int *nbx, int *nby);
-int sync_guard_d(tsdr_sync *s, const float *iq, size_t S, int y_t, int x_t, int frames, float *img, size_t img_stride,
+int sync_guard_d(tsdr_sync *s, const float *iq, IqFmt iqf, size_t S, int y_t, int x_t, int frames, float *img, size_t img_stride,
                  unsigned long long *keys, float *proj, const GuardArgs &g, bool *can, bool plan_only);
 int sync_workspace(tsdr_sync *s, int frames, int slot, int nslots, const ProjLayout *pl_in, float **proj,
                    unsigned long long **keys);
@@ -39,7 +38,7 @@ int sync_use_lane(tsdr_sync *s, int lane);
 bool sync_is_f64(const tsdr_sync *s);
 int shift_iir_d(tsdr_ctx *ctx, tsdr_sync *s, const float *img, size_t img_stride, int h, int w, int frames,
                 const unsigned long long *keys, int do_align, float alpha, float *state, float *frames_out,
-                int *sync_idx);
+                int *sync_idx, hipEvent_t done);
 }  // namespace tsdr
 
 using namespace tsdr;
@@ -72,10 +71,21 @@ struct GuardPlan {
   uint2 *top2 = nullptr;
 };
 
-struct PrecisionScope {  // a call that has to run in TSDR_EXACT restores the caller's mode on every exit path
-  tsdr_ctx *ctx; int saved;
-  explicit PrecisionScope(tsdr_ctx *c) : ctx(c), saved(c->precision) {}
-  ~PrecisionScope() { ctx->precision = saved; }
+// One buffer's work: what the caller asked for, and what job_prepare leaves for the launches.  The steps below take
+// everything from here -- the IQ format and the precision the buffer runs in included -- and nothing from mutable fields
+// of the context, except the stream their launches go to (launch_stream / pipe_lane: LaneScope).
+struct FrameJob {
+  tsdr_ctx *ctx; tsdr_sync *sync;
+  const float *iq; IqFmt fmt;
+  size_t S; int y_t, x_t, F, do_align; float alpha;
+  float *img; unsigned long long *keys;            // the buffer's 600x800 images and argmax keys (slot `slot`)
+  float *raster_out, *state, *frames_out; int *sync_idx;
+  int slot, nslots;                                // which part of the sync / guard workspaces this buffer uses
+  // job_prepare:
+  int precision = TSDR_FAST;                       // the context's, or TSDR_EXACT for this buffer alone
+  GuardPlan gp;
+  float *proj = nullptr;                           // projection partial sums
+  ProjLayout plan{}, sums{};                       // their layout as planned (sizes the workspace) / as job_images left them
 };
 
 // the adaptive route's decision (common.h): evaluated over windows of at least kGuardAutoWindow frames, from the per-call
@@ -131,18 +141,21 @@ static void guard_auto_update(tsdr_ctx *ctx, unsigned long long upto) {
   if (!ctx->opt_guard_auto) ctx->guard_exact_now = false;
 }
 
-static int guard_prepare(tsdr_ctx *ctx, tsdr_sync *sync, size_t S, int y_t, int x_t, int do_align, int F, int slot, int nslots,
-                         GuardPlan *gp) {
-  *gp = GuardPlan{};
-  if (!do_align || ctx->precision != TSDR_FAST || !(ctx->guard_thr > 0.f)) return TSDR_OK;
+// The guard's part of job_prepare.  This is where a buffer's precision is decided.
+static int guard_plan(FrameJob &j) {
+  tsdr_ctx *ctx = j.ctx;
+  const int F = j.F;
+  j.gp = GuardPlan{};
+  j.precision = ctx->precision;
+  if (!j.do_align || j.precision != TSDR_FAST || !(ctx->guard_thr > 0.f)) return TSDR_OK;
   int nbx = 0, nby = 0;
-  sync_beta_blocks(sync, &nbx, &nby);
+  sync_beta_blocks(j.sync, &nbx, &nby);
   GuardArgs g;
   g.nbx = nbx; g.nby = nby; g.thr = ctx->guard_thr;
   bool can = false;
-  int rc = sync_guard_d(sync, nullptr, S, y_t, x_t, F, nullptr, 0, nullptr, nullptr, g, &can, true);
+  int rc = sync_guard_d(j.sync, nullptr, j.fmt, j.S, j.y_t, j.x_t, F, nullptr, 0, nullptr, nullptr, g, &can, true);
   if (rc) return rc;
-  if (!can) { ctx->precision = TSDR_EXACT; return TSDR_OK; }  // (the caller holds a PrecisionScope)
+  if (!can) { j.precision = TSDR_EXACT; return TSDR_OK; }
   if (!ctx->guard_stats) {
     TSDR_HIP(ctx, hipMalloc((void **)&ctx->guard_stats, 32));
     TSDR_HIP(ctx, hipMemsetAsync(ctx->guard_stats, 0, 32, ctx->stream));
@@ -152,84 +165,76 @@ static int guard_prepare(tsdr_ctx *ctx, tsdr_sync *sync, size_t S, int y_t, int 
   // this call is guarded call number guard_seq: its route follows from the calls up to guard_seq - kGuardLag
   if (ctx->guard_seq >= (unsigned long long)tsdr_ctx::kGuardLag) guard_auto_update(ctx, ctx->guard_seq - tsdr_ctx::kGuardLag + 1);
   if (ctx->opt_guard_auto && ctx->guard_exact_now) {  // this buffer: the exact sequence as a whole; flagged frames are only counted
-    ctx->precision = TSDR_EXACT;                      // (the caller holds a PrecisionScope)
+    j.precision = TSDR_EXACT;
     g.count_only = 1;
     ++ctx->guard_auto_buffers;
   }
   const size_t per = ((size_t)F * 4 + 15) / 16 * 16 + (size_t)F * (size_t)(nbx + nby) * 8;
-  char *w = (char *)ctx->scratch(WS_GUARD, (size_t)nslots * per);
+  char *w = (char *)ctx->scratch(WS_GUARD, (size_t)j.nslots * per);
   if (!w) return TSDR_ENOMEM;
-  w += (size_t)slot * per;
+  w += (size_t)j.slot * per;
   g.flags = (int *)w;
-  gp->top2 = (uint2 *)(w + ((size_t)F * 4 + 15) / 16 * 16);
-  g.top2 = gp->top2;
+  j.gp.top2 = (uint2 *)(w + ((size_t)F * 4 + 15) / 16 * 16);
+  g.top2 = j.gp.top2;
   g.stats = ctx->guard_stats;
   g.host = ctx->guard_ring + (ctx->guard_seq % tsdr_ctx::kGuardRing);
   g.host_tag = (ctx->guard_seq + 1) & 0xFFFFull;
   ++ctx->guard_seq;
-  gp->g = g;
-  gp->on = true;
+  j.gp.g = g;
+  j.gp.on = true;
   // (an offset, not the pointer: the workspace may be reallocated by a later, larger call)
-  ctx->guard_last_off = (size_t)((const char *)gp->top2 - (const char *)ctx->ws[WS_GUARD].p);
+  ctx->guard_last_off = (size_t)((const char *)j.gp.top2 - (const char *)ctx->ws[WS_GUARD].p);
   ctx->guard_last_frames = F; ctx->guard_last_nbx = nbx; ctx->guard_last_nby = nby;
   return TSDR_OK;
 }
 
-static int guard_run(tsdr_ctx *ctx, tsdr_sync *sync, const GuardPlan &gp, const float *iq, size_t S, int y_t, int x_t, int F,
-                     float *img, unsigned long long *keys, float *proj) {
-  const size_t npx = (size_t)TSDR_RENDER_H * TSDR_RENDER_W;
-  (void)ctx;
-  return sync_guard_d(sync, iq, S, y_t, x_t, F, img, npx, keys, proj, gp.g, nullptr, false);
+// The loop body for one buffer of F frames, as four steps over a FrameJob.  Every arrangement of the loop is a schedule over
+// them -- which stream a step goes to, which events sit between two steps: one call per buffer on the context's stream
+// (frames_scan, then tsdr_frames_combine_d) and the pipeline's equal lanes and image lane + tail lane (frames_submit).
+//   job_prepare  everything that may allocate or grow a workspace: guard plan (and with it the buffer's precision), the image
+//                call's plan, the sync workspace.  Launches nothing.
+//   job_images   stage R: raster (optional) + 600x800 image of every frame in one launch; in TSDR_FAST mode the same kernel
+//                also forms the images' projection partial sums on the fly, so no kernel re-reads the images for them
+//   job_stats    stage S: vsync statistics (two argmax keys per frame), in TSDR_FAST mode followed by the sync guard
+//   job_combine  shift + IIR; `done`: an event recorded behind it, or nullptr
+constexpr size_t kNpx = (size_t)TSDR_RENDER_H * TSDR_RENDER_W;
+
+static int job_images_call(FrameJob &j, float *proj, ProjLayout *got, bool plan_only, unsigned long long *keys) {
+  return raster_and_down_d(j.ctx, j.iq, 1, j.fmt, j.precision, j.S, j.S, j.y_t, j.x_t, TSDR_RENDER_H, TSDR_RENDER_W, j.F, j.raster_out,
+                           (size_t)j.y_t * j.x_t, j.img, kNpx, proj, got, plan_only, keys);
 }
 
-// The loop body for F frames.  Stage R: raster (optional) + 600x800 image of every frame in one launch; in TSDR_FAST
-// mode the same kernel also forms the images' projection partial sums on the fly, so no kernel re-reads the images
-// for them.  Stage S: vsync statistics (two argmax keys per frame), in TSDR_FAST mode followed by the sync guard, and,
-// with `combine`, shift + IIR.
-// slot/nslots: which half of the sync workspaces this buffer uses.  Everything goes to the context's stream.
-static int frames_stage(tsdr_ctx *ctx, tsdr_sync *sync, const float *iq, size_t S, int y_t, int x_t, int do_align, int F,
-                        float *img, float *raster_out, unsigned long long *keys, int slot, int nslots, float alpha,
-                        float *state, float *frames_out, int *sync_idx, bool combine = true) {
-  const size_t npx = (size_t)TSDR_RENDER_H * TSDR_RENDER_W;
-  float *proj = nullptr;
-  ProjLayout plan{}, got{};
-  PrecisionScope scope(ctx);
-  GuardPlan gp;
-  int rc = guard_prepare(ctx, sync, S, y_t, x_t, do_align, F, slot, nslots, &gp);
+static int job_prepare(FrameJob &j) {
+  int rc = guard_plan(j);
+  if (rc || !j.do_align) return rc;
+  rc = job_images_call(j, nullptr, &j.plan, /*plan_only=*/true, nullptr);
   if (rc) return rc;
-  if (do_align) {
-    rc = raster_and_down_d(ctx, iq, 1, S, S, y_t, x_t, TSDR_RENDER_H, TSDR_RENDER_W, F, raster_out, (size_t)y_t * x_t, img, npx,
-                           nullptr, &plan, true);
-    if (rc) return rc;
-    rc = sync_workspace(sync, F, slot, nslots, plan.ncp ? &plan : nullptr, &proj, nullptr);
-    if (rc) return rc;
-  }
-  rc = raster_and_down_d(ctx, iq, 1, S, S, y_t, x_t, TSDR_RENDER_H, TSDR_RENDER_W, F, raster_out, (size_t)y_t * x_t, img, npx,
-                         proj, &got, false, keys);
-  if (rc) return rc;
-  if (do_align) {
-    rc = sync_scan_d(sync, img, npx, F, keys, proj, got.ncp ? &got : nullptr, gp.on ? gp.top2 : nullptr);
-    if (rc) return rc;
-    if (gp.on) {
-      rc = guard_run(ctx, sync, gp, iq, S, y_t, x_t, F, img, keys, proj);
-      if (rc) return rc;
-    }
-  }
-  if (combine) {
-    rc = shift_iir_d(ctx, sync, img, npx, TSDR_RENDER_H, TSDR_RENDER_W, F, keys, do_align, alpha, state, frames_out,
-                     do_align ? sync_idx : nullptr);
-    if (rc) return rc;
-  }
-  return TSDR_OK;
+  return sync_workspace(j.sync, j.F, j.slot, j.nslots, j.plan.ncp ? &j.plan : nullptr, &j.proj, nullptr);
 }
 
-int tsdr_frames_scan_d(tsdr_ctx *ctx, tsdr_sync *sync, const float *iq, size_t nEch, size_t S, int y_t, int x_t,
+static int job_images(FrameJob &j) { return job_images_call(j, j.proj, &j.sums, /*plan_only=*/false, j.keys); }
+
+static int job_stats(FrameJob &j) {
+  if (!j.do_align) return TSDR_OK;
+  int rc = sync_scan_d(j.sync, j.img, kNpx, j.F, j.keys, j.proj, j.sums.ncp ? &j.sums : nullptr, j.gp.on ? j.gp.top2 : nullptr);
+  if (rc || !j.gp.on) return rc;
+  return sync_guard_d(j.sync, j.iq, j.fmt, j.S, j.y_t, j.x_t, j.F, j.img, kNpx, j.keys, j.proj, j.gp.g, nullptr, false);
+}
+
+static int job_combine(FrameJob &j, hipEvent_t done) {
+  return shift_iir_d(j.ctx, j.sync, j.img, kNpx, TSDR_RENDER_H, TSDR_RENDER_W, j.F, j.keys, j.do_align, j.alpha, j.state, j.frames_out,
+                     j.do_align ? j.sync_idx : nullptr, done);
+}
+
+// The sequential arrangement, first part: prepare, images, statistics of one buffer on the context's stream, into the caller's
+// image and key buffers (tsdr_frames_scan_d; tsdr_group_* gathers these before shift + IIR runs on the root).
+static int frames_scan(tsdr_ctx *ctx, tsdr_sync *sync, const float *iq, IqFmt fmt, size_t nEch, size_t S, int y_t, int x_t,
                        int do_align, float *img_out, float *raster_out, unsigned long long *keys_out, int *n_frames) {
   if (!ctx || S == 0 || y_t <= 0 || x_t <= 0) return TSDR_EINVAL;
   if (nEch && !iq) return TSDR_EINVAL;
   int rc = frames_check(ctx, sync, do_align);
   if (rc) return rc;
-  TSDR_PTR_ALIGNED(ctx, "frames_scan", iq, iq_bytes(ctx->iq_fmt));
+  TSDR_PTR_ALIGNED(ctx, "frames_scan", iq, iq_bytes(fmt));
   TSDR_PTR_ALIGNED(ctx, "frames_scan", img_out, 4);
   TSDR_PTR_ALIGNED(ctx, "frames_scan", raster_out, 4);
   TSDR_PTR_ALIGNED(ctx, "frames_scan", keys_out, 8);
@@ -240,11 +245,19 @@ int tsdr_frames_scan_d(tsdr_ctx *ctx, tsdr_sync *sync, const float *iq, size_t n
   if (n_frames) *n_frames = (int)nb;
   if (nb == 0) return TSDR_OK;
   if (!img_out || (do_align && !keys_out)) return TSDR_EINVAL;
-  const int F = (int)nb;
-  return frames_stage(ctx, sync, iq, S, y_t, x_t, do_align, F, img_out, raster_out, keys_out, 0, 1, 0.0f, nullptr, nullptr, nullptr,
-                      /*combine=*/false);
+  FrameJob j{ctx, sync, iq, fmt, S, y_t, x_t, (int)nb, do_align, 0.0f, img_out, keys_out, raster_out, nullptr, nullptr, nullptr, 0, 1};
+  rc = job_prepare(j);
+  if (!rc) rc = job_images(j);
+  if (!rc) rc = job_stats(j);
+  return rc;
 }
 
+int tsdr_frames_scan_d(tsdr_ctx *ctx, tsdr_sync *sync, const float *iq, size_t nEch, size_t S, int y_t, int x_t,
+                       int do_align, float *img_out, float *raster_out, unsigned long long *keys_out, int *n_frames) {
+  return frames_scan(ctx, sync, iq, IqFmt{}, nEch, S, y_t, x_t, do_align, img_out, raster_out, keys_out, n_frames);
+}
+
+// ... second part: shift + IIR over the frames in order
 int tsdr_frames_combine_d(tsdr_ctx *ctx, tsdr_sync *sync, const float *img, const unsigned long long *keys, int n_frames,
                           float alpha, int do_align, float *imageOut_state, float *frames_out, int *sync_idx) {
   if (!ctx || !imageOut_state || n_frames < 0) return TSDR_EINVAL;
@@ -259,16 +272,16 @@ int tsdr_frames_combine_d(tsdr_ctx *ctx, tsdr_sync *sync, const float *img, cons
   if (rc) return rc;
   if (n_frames == 0) return TSDR_OK;
   if (!img || (do_align && !keys)) return TSDR_EINVAL;
-  return shift_iir_d(ctx, sync, img, (size_t)TSDR_RENDER_H * TSDR_RENDER_W, TSDR_RENDER_H, TSDR_RENDER_W, n_frames, keys,
-                     do_align, alpha, imageOut_state, frames_out, do_align ? sync_idx : nullptr);
+  return shift_iir_d(ctx, sync, img, kNpx, TSDR_RENDER_H, TSDR_RENDER_W, n_frames, keys, do_align, alpha, imageOut_state, frames_out,
+                     do_align ? sync_idx : nullptr, nullptr);
 }
 
-int tsdr_frames_d(tsdr_ctx *ctx, tsdr_sync *sync, const float *iq, size_t nEch, size_t S, int y_t, int x_t, float alpha,
-                  int do_align, float *imageOut_state, float *frames_out, float *raster_out, int *sync_idx,
-                  int *n_frames) {
+// run one buffer: both parts, through workspace images and keys
+static int frames_run(tsdr_ctx *ctx, tsdr_sync *sync, const float *iq, IqFmt fmt, size_t nEch, size_t S, int y_t, int x_t, float alpha,
+                      int do_align, float *imageOut_state, float *frames_out, float *raster_out, int *sync_idx, int *n_frames) {
   if (!ctx || !imageOut_state || S == 0 || y_t <= 0 || x_t <= 0) return TSDR_EINVAL;
   if (int rc = sync_f32_check(ctx, sync)) return rc;
-  TSDR_PTR_ALIGNED(ctx, "frames", iq, iq_bytes(ctx->iq_fmt));
+  TSDR_PTR_ALIGNED(ctx, "frames", iq, iq_bytes(fmt));
   TSDR_PTR_ALIGNED(ctx, "frames", imageOut_state, 4);
   TSDR_PTR_ALIGNED(ctx, "frames", frames_out, 4);
   TSDR_PTR_ALIGNED(ctx, "frames", raster_out, 4);
@@ -279,19 +292,24 @@ int tsdr_frames_d(tsdr_ctx *ctx, tsdr_sync *sync, const float *iq, size_t nEch, 
     int rcd = pipe_drain(ctx);
     if (rcd) return rcd;
   }
-  const size_t npx = (size_t)TSDR_RENDER_H * TSDR_RENDER_W;
-  float *img = (float *)ctx->scratch(WS_IMG, (nb ? nb : 1) * npx * 4);
+  float *img = (float *)ctx->scratch(WS_IMG, (nb ? nb : 1) * kNpx * 4);
   unsigned long long *keys = (unsigned long long *)ctx->scratch(WS_KEYS, (nb ? nb : 1) * 2 * 8);
   if (!img || !keys) return TSDR_ENOMEM;
   // (Measured and closed: cutting ONE buffer into frame chunks whose tails run beside the next chunk's image launch -- round 1:
   // 0.245 -> 0.271 ms with 2 chunks; round 5 on the pipeline's lanes: 0.162 -> 0.247 ms (2), 0.266 (3); raster-free 0.086 ->
   // 0.130 / 0.164.  Half-size image launches fill the machine worse and the chain of tails is exposed at the call's end.
-  // The overlap lives ACROSS buffers: tsdr_frames_submit_d.)
+  // The overlap lives ACROSS buffers: frames_submit.)
   int nf = 0;
-  int rc = tsdr_frames_scan_d(ctx, sync, iq, nEch, S, y_t, x_t, do_align, img, raster_out, keys, &nf);
+  int rc = frames_scan(ctx, sync, iq, fmt, nEch, S, y_t, x_t, do_align, img, raster_out, keys, &nf);
   if (n_frames) *n_frames = nf;
   if (rc || nf == 0) return rc;
   return tsdr_frames_combine_d(ctx, sync, img, keys, nf, alpha, do_align, imageOut_state, frames_out, sync_idx);
+}
+
+int tsdr_frames_d(tsdr_ctx *ctx, tsdr_sync *sync, const float *iq, size_t nEch, size_t S, int y_t, int x_t, float alpha,
+                  int do_align, float *imageOut_state, float *frames_out, float *raster_out, int *sync_idx,
+                  int *n_frames) {
+  return frames_run(ctx, sync, iq, IqFmt{}, nEch, S, y_t, x_t, alpha, do_align, imageOut_state, frames_out, raster_out, sync_idx, n_frames);
 }
 
 // ---- the same body pipelined across successive buffers ----------------------------------------------------------
@@ -299,7 +317,8 @@ int tsdr_frames_d(tsdr_ctx *ctx, tsdr_sync *sync, const float *iq, size_t nEch, 
 // latencies that leave most of the machine idle) behind one throughput-bound launch (raster / images).  Two independent
 // capture streams on one GPU fill each other's gaps; the same overlap is available to ONE capture stream, because
 // everything that couples successive buffers -- the lagged s_y, the IIR recurrence -- sits in shift + IIR.  Two kinds of
-// arrangement on internal HIP streams ("lanes"):
+// arrangement on internal HIP streams ("lanes"), each a schedule over the four steps above (R = job_images, B G = job_stats:
+// statistics, guard, C = job_combine; job_prepare comes first in both, on the host):
 //
 //  A  image lane:  R(k)      R(k+1)            R(k+2)  ...          back to back
 //     tail lane :       [R(k) done] B(k) G(k) C(k)  [R(k+1) done] B(k+1) ...
@@ -464,23 +483,33 @@ struct SubmitGuard {
   ~SubmitGuard() { if (!ok) pipe_sync_lanes(ctx); }
 };
 
-struct LaneScope {  // launches of this scope go to a lane
+struct LaneScope {  // launches of this scope go to a lane: the one piece of ambient state the steps read (TSDR_LAUNCH)
   tsdr_ctx *ctx; hipStream_t saved;
   LaneScope(tsdr_ctx *c, int lane) : ctx(c), saved(c->launch_stream) { c->launch_stream = c->lane[lane]; c->pipe_lane = lane; }
   ~LaneScope() { ctx->launch_stream = saved; ctx->pipe_lane = 0; }
 };
+
+// The caller's inputs: whatever the context's stream holds now (uploads, a producer's kernels, an earlier call's launches)
+// comes before `lane`'s next launch.  An idle stream -- the steady state of a caller that only submits -- needs no fence.
+static int fence_inputs(tsdr_ctx *ctx, hipStream_t lane) {
+  if (hipStreamQuery(ctx->stream) == hipSuccess) return TSDR_OK;
+  (void)hipGetLastError();  // (hipErrorNotReady is a status here, not a failure for the next launch check to find)
+  TSDR_HIP(ctx, hipEventRecord(ctx->lane_in, ctx->stream));
+  TSDR_HIP(ctx, hipStreamWaitEvent(lane, ctx->lane_in, 0));
+  return TSDR_OK;
+}
 }  // namespace tsdr
 
 extern "C" {
 
-int tsdr_frames_submit_d(tsdr_ctx *ctx, tsdr_sync *sync, const float *iq, size_t nEch, size_t S, int y_t, int x_t,
-                         float alpha, int do_align, float *imageOut_state, float *frames_out, float *raster_out,
-                         int *sync_idx, int *n_frames) {
+// submit one buffer to the pipeline
+static int frames_submit(tsdr_ctx *ctx, tsdr_sync *sync, const float *iq, IqFmt fmt, size_t nEch, size_t S, int y_t, int x_t, float alpha,
+                         int do_align, float *imageOut_state, float *frames_out, float *raster_out, int *sync_idx, int *n_frames) {
   if (!ctx || !imageOut_state || S == 0 || y_t <= 0 || x_t <= 0) return TSDR_EINVAL;
   if (nEch && !iq) return TSDR_EINVAL;
   int rc = frames_check(ctx, sync, do_align);
   if (rc) return rc;
-  TSDR_PTR_ALIGNED(ctx, "frames_submit", iq, iq_bytes(ctx->iq_fmt));
+  TSDR_PTR_ALIGNED(ctx, "frames_submit", iq, iq_bytes(fmt));
   TSDR_PTR_ALIGNED(ctx, "frames_submit", imageOut_state, 4);
   TSDR_PTR_ALIGNED(ctx, "frames_submit", frames_out, 4);
   TSDR_PTR_ALIGNED(ctx, "frames_submit", raster_out, 4);
@@ -489,14 +518,12 @@ int tsdr_frames_submit_d(tsdr_ctx *ctx, tsdr_sync *sync, const float *iq, size_t
   if (nb > (size_t)1 << 20) return set_err(ctx, TSDR_EINVAL, "too many frames in one buffer");
   if (n_frames) *n_frames = (int)nb;
   if (nb == 0) return TSDR_OK;
-  const int F = (int)nb;
-  const size_t npx = (size_t)TSDR_RENDER_H * TSDR_RENDER_W;
   constexpr int NS = tsdr_ctx::kPipeSlots;
   rc = pipe_init(ctx);
   if (rc) return rc;
   tsdr_ctx::PipeKey key;
   key.nb = nb; key.S = S; key.y_t = y_t; key.x_t = x_t; key.raster = raster_out ? 1 : 0; key.prec = ctx->precision;
-  key.align = do_align ? 1 : 0; key.sync = (const void *)sync; key.iq_kind = ctx->iq_fmt.kind;
+  key.align = do_align ? 1 : 0; key.sync = (const void *)sync; key.iq_kind = fmt.kind;
   const int cand = pipe_pick(ctx, key);
   if (cand < 0) return cand;
   const PipeCand &pc = kCands[cand];
@@ -524,102 +551,50 @@ int tsdr_frames_submit_d(tsdr_ctx *ctx, tsdr_sync *sync, const float *iq, size_t
   // symmetric: whole buffers alternate between nl equal lanes; slot = position in the rotation
   const int slot = (int)(ctx->pipe_seq % (unsigned long long)(sym ? nl : NS));
   // (workspaces first: growing one synchronises and frees what the lanes may be using)
-  float *img3 = (float *)ctx->scratch(WS_IMG, NS * nb * npx * 4);
+  float *img3 = (float *)ctx->scratch(WS_IMG, NS * nb * kNpx * 4);
   unsigned long long *keys3 = (unsigned long long *)ctx->scratch(WS_KEYS, NS * nb * 2 * 8);
   if (!img3 || !keys3) return TSDR_ENOMEM;
-  float *img = img3 + (size_t)slot * nb * npx;
-  unsigned long long *keys = keys3 + (size_t)slot * nb * 2;
-  float *proj = nullptr;
-  ProjLayout plan{}, got{};
-  PrecisionScope scope(ctx);
+  FrameJob j{ctx, sync, iq, fmt, S, y_t, x_t, (int)nb, do_align, alpha, img3 + (size_t)slot * nb * kNpx, keys3 + (size_t)slot * nb * 2,
+             raster_out, imageOut_state, frames_out, sync_idx, slot, NS};
   SubmitGuard submitted(ctx);
-  GuardPlan gp;
-  rc = guard_prepare(ctx, sync, S, y_t, x_t, do_align, F, slot, NS, &gp);
+  rc = job_prepare(j);
   if (rc) return rc;
-  if (do_align) {
-    rc = raster_and_down_d(ctx, iq, 1, S, S, y_t, x_t, TSDR_RENDER_H, TSDR_RENDER_W, F, raster_out, (size_t)y_t * x_t, img, npx, nullptr,
-                           &plan, true);
-    if (rc) return rc;
-    rc = sync_workspace(sync, F, slot, NS, plan.ncp ? &plan : nullptr, &proj, nullptr);
-    if (rc) return rc;
-  }
   hipStream_t tail_stream = nullptr;
   if (sym) {
     // R(k) B(k) G(k) [shift + IIR of the previous buffer done] C(k), all on lane `slot`: a lane's next buffer is stream-ordered
     // behind its previous one, and the only cross-lane dependency is the chain of shift + IIR launches (lagged s_y, IIR state)
     const int li = slot == 2 ? 3 : slot;
     LaneScope lane_scope(ctx, li);
-    hipStream_t st = ctx->lane[li];
-    tail_stream = st;
-    if (hipStreamQuery(ctx->stream) != hipSuccess) {
-      (void)hipGetLastError();
-      TSDR_HIP(ctx, hipEventRecord(ctx->lane_in, ctx->stream));
-      TSDR_HIP(ctx, hipStreamWaitEvent(st, ctx->lane_in, 0));
-    }
-    if (do_align) {
-      rc = sync_use_lane(sync, slot);
-      if (rc) return rc;
-    }
-    rc = raster_and_down_d(ctx, iq, 1, S, S, y_t, x_t, TSDR_RENDER_H, TSDR_RENDER_W, F, raster_out, (size_t)y_t * x_t, img, npx, proj,
-                           &got, false, keys);
+    tail_stream = ctx->lane[li];
+    rc = fence_inputs(ctx, tail_stream);
+    if (!rc && do_align) rc = sync_use_lane(sync, slot);
+    if (!rc) rc = job_images(j);
+    if (!rc) rc = job_stats(j);
     if (rc) return rc;
-    if (do_align) {
-      rc = sync_scan_d(sync, img, npx, F, keys, proj, got.ncp ? &got : nullptr, gp.on ? gp.top2 : nullptr);
-      if (rc) return rc;
-      if (gp.on) {
-        rc = guard_run(ctx, sync, gp, iq, S, y_t, x_t, F, img, keys, proj);
-        if (rc) return rc;
-      }
-    }
     if (ctx->pipe_last_slot >= 0 && ctx->pipe_last_slot != slot && ctx->ev_tail_used[ctx->pipe_last_slot])
-      TSDR_HIP(ctx, hipStreamWaitEvent(st, ctx->ev_tail[ctx->pipe_last_slot], 0));
-    const bool want_ev = nl > 1;
-    if (ctx->opt_pipe_ext_event && want_ev) ctx->launch_stop_ev = ctx->ev_tail[slot];
-    rc = shift_iir_d(ctx, sync, img, npx, TSDR_RENDER_H, TSDR_RENDER_W, F, keys, do_align, alpha, imageOut_state, frames_out,
-                     do_align ? sync_idx : nullptr);
-    ctx->launch_stop_ev = nullptr;
+      TSDR_HIP(ctx, hipStreamWaitEvent(tail_stream, ctx->ev_tail[ctx->pipe_last_slot], 0));
+    rc = job_combine(j, nl > 1 ? ctx->ev_tail[slot] : nullptr);   // (one lane: no event per buffer, see pipe_drain)
     if (rc) return rc;
-    if (!ctx->opt_pipe_ext_event && want_ev) TSDR_HIP(ctx, hipEventRecord(ctx->ev_tail[slot], st));
   } else {
     tail_stream = ctx->lane[2];
     {
       LaneScope image_lane(ctx, 0);
-      // inputs: whatever the context's stream holds now (uploads, a producer's kernels, an earlier call's launches) comes
-      // first.  An idle stream -- the steady state of a caller that only submits -- needs no fence.
-      if (hipStreamQuery(ctx->stream) != hipSuccess) {
-        (void)hipGetLastError();  // (hipErrorNotReady is a status here, not a failure for the next launch check to find)
-        TSDR_HIP(ctx, hipEventRecord(ctx->lane_in, ctx->stream));
-        TSDR_HIP(ctx, hipStreamWaitEvent(ctx->lane[0], ctx->lane_in, 0));
-      }
+      rc = fence_inputs(ctx, ctx->lane[0]);
+      if (rc) return rc;
       // this slot's previous user: submission k - NS, whose tail read its images / keys / sums
       if (ctx->ev_tail_used[slot]) TSDR_HIP(ctx, hipStreamWaitEvent(ctx->lane[0], ctx->ev_tail[slot], 0));
-      if (do_align) {   // (one beta set serves: the statistics run in stream order on the tail lane)
-        rc = sync_use_lane(sync, 0);
-        if (rc) return rc;
-      }
-      rc = raster_and_down_d(ctx, iq, 1, S, S, y_t, x_t, TSDR_RENDER_H, TSDR_RENDER_W, F, raster_out, (size_t)y_t * x_t, img, npx, proj,
-                             &got, false, keys);
+      if (do_align) rc = sync_use_lane(sync, 0);   // (one beta set serves: the statistics run in stream order on the tail lane)
+      if (!rc) rc = job_images(j);
       if (rc) return rc;
       TSDR_HIP(ctx, hipEventRecord(ctx->ev_img[slot], ctx->lane[0]));
     }
     {
       LaneScope tail_lane(ctx, 2);
       TSDR_HIP(ctx, hipStreamWaitEvent(ctx->lane[2], ctx->ev_img[slot], 0));
-      if (do_align) {
-        rc = sync_scan_d(sync, img, npx, F, keys, proj, got.ncp ? &got : nullptr, gp.on ? gp.top2 : nullptr);
-        if (rc) return rc;
-        if (gp.on) {
-          rc = guard_run(ctx, sync, gp, iq, S, y_t, x_t, F, img, keys, proj);
-          if (rc) return rc;
-        }
-      }
+      rc = job_stats(j);
       // (shift + IIR on a third stream of its own: 348 k vs 357 k frames/s raster-free, 175 k vs 181 k with rasters -- dropped)
-      if (ctx->opt_pipe_ext_event) ctx->launch_stop_ev = ctx->ev_tail[slot];
-      rc = shift_iir_d(ctx, sync, img, npx, TSDR_RENDER_H, TSDR_RENDER_W, F, keys, do_align, alpha, imageOut_state, frames_out,
-                       do_align ? sync_idx : nullptr);
-      ctx->launch_stop_ev = nullptr;
+      if (!rc) rc = job_combine(j, ctx->ev_tail[slot]);
       if (rc) return rc;
-      if (!ctx->opt_pipe_ext_event) TSDR_HIP(ctx, hipEventRecord(ctx->ev_tail[slot], ctx->lane[2]));
     }
   }
   if (ctx->opt_pipe_pin < 0 && ctx->opt_pipe_mode < 0 && ctx->opt_pipe_tune && ctx->tune.state == 1 && ctx->tune.pos < tsdr_ctx::kTrial) {
@@ -660,63 +635,57 @@ int tsdr_frames_pipeline_info(tsdr_ctx *ctx, int *trials_left, int *chosen, floa
   return TSDR_OK;
 }
 
+int tsdr_frames_submit_d(tsdr_ctx *ctx, tsdr_sync *sync, const float *iq, size_t nEch, size_t S, int y_t, int x_t,
+                         float alpha, int do_align, float *imageOut_state, float *frames_out, float *raster_out,
+                         int *sync_idx, int *n_frames) {
+  return frames_submit(ctx, sync, iq, IqFmt{}, nEch, S, y_t, x_t, alpha, do_align, imageOut_state, frames_out, raster_out, sync_idx, n_frames);
+}
+
 // ---- int16 I/Q input (what SDR hardware delivers, AtomicAbstractSDRs.jl:284-306 before its conversion): the same loop with
 // the ComplexF32(re, im) * scale conversion inside the kernels' loaders, so the int16 buffer is never expanded in HBM
-namespace {
-struct IqScope {
-  tsdr_ctx *ctx;
-  IqScope(tsdr_ctx *c, int kind, float scale) : ctx(c) { c->iq_fmt.kind = kind; c->iq_fmt.scale = scale; }
-  ~IqScope() { ctx->iq_fmt = tsdr::IqFmt{}; }
-};
-// tsdr_frames_iq_d / tsdr_frames_submit_iq_d: the format is one of TSDR_IQ_*, the base aligned to one sample
-int iq_args_check(tsdr_ctx *ctx, const void *iq, int iq_fmt) {
-  static_assert(TSDR_IQ_CF32 == tsdr::IQK_CF32 && TSDR_IQ_SC16 == tsdr::IQK_SC16 && TSDR_IQ_SC8 == tsdr::IQK_SC8 && TSDR_IQ_UC8 == tsdr::IQK_UC8,
-                "IqFmt::kind is the public format code");
-  if (iq_fmt < TSDR_IQ_CF32 || iq_fmt > TSDR_IQ_UC8) return tsdr::set_err(ctx, TSDR_EINVAL, "frames_iq: unknown IQ format %d", iq_fmt);
-  tsdr::IqFmt f; f.kind = iq_fmt;
-  if (reinterpret_cast<uintptr_t>(iq) % tsdr::iq_bytes(f)) return tsdr::set_err(ctx, TSDR_EINVAL, "frames_iq: the buffer is not aligned to one sample of its format");
-  return TSDR_OK;
-}
-}  // namespace
-
 int tsdr_frames_sc16_d(tsdr_ctx *ctx, tsdr_sync *sync, const int16_t *iq, float scale, size_t nEch, size_t S, int y_t, int x_t,
                        float alpha, int do_align, float *imageOut_state, float *frames_out, float *raster_out, int *sync_idx,
                        int *n_frames) {
-  if (!ctx) return TSDR_EINVAL;
-  IqScope fmt(ctx, tsdr::IQK_SC16, scale);
-  return tsdr_frames_d(ctx, sync, reinterpret_cast<const float *>(iq), nEch, S, y_t, x_t, alpha, do_align, imageOut_state, frames_out,
-                       raster_out, sync_idx, n_frames);
+  return frames_run(ctx, sync, reinterpret_cast<const float *>(iq), IqFmt{IQK_SC16, scale}, nEch, S, y_t, x_t, alpha, do_align,
+                    imageOut_state, frames_out, raster_out, sync_idx, n_frames);
 }
 
 int tsdr_frames_submit_sc16_d(tsdr_ctx *ctx, tsdr_sync *sync, const int16_t *iq, float scale, size_t nEch, size_t S, int y_t,
                               int x_t, float alpha, int do_align, float *imageOut_state, float *frames_out, float *raster_out,
                               int *sync_idx, int *n_frames) {
-  if (!ctx) return TSDR_EINVAL;
-  IqScope fmt(ctx, tsdr::IQK_SC16, scale);
-  return tsdr_frames_submit_d(ctx, sync, reinterpret_cast<const float *>(iq), nEch, S, y_t, x_t, alpha, do_align, imageOut_state,
-                              frames_out, raster_out, sync_idx, n_frames);
+  return frames_submit(ctx, sync, reinterpret_cast<const float *>(iq), IqFmt{IQK_SC16, scale}, nEch, S, y_t, x_t, alpha, do_align,
+                       imageOut_state, frames_out, raster_out, sync_idx, n_frames);
 }
 
 // ---- any input format (TSDR_IQ_*): ComplexF32, int16 pairs, or the 8-bit pairs of HackRF / UHD sc8 (int8) and RTL-SDR
 // (uint8 around 127.5).  CF32 ignores the scale and is tsdr_frames_d; every other format converts in the loaders.
+// The format is one of TSDR_IQ_*, the base aligned to one sample.
+static int iq_fmt_arg(tsdr_ctx *ctx, const void *iq, int iq_fmt, float scale, IqFmt *f) {
+  static_assert(TSDR_IQ_CF32 == IQK_CF32 && TSDR_IQ_SC16 == IQK_SC16 && TSDR_IQ_SC8 == IQK_SC8 && TSDR_IQ_UC8 == IQK_UC8,
+                "IqFmt::kind is the public format code");
+  if (!ctx) return TSDR_EINVAL;
+  if (iq_fmt < TSDR_IQ_CF32 || iq_fmt > TSDR_IQ_UC8) return set_err(ctx, TSDR_EINVAL, "frames_iq: unknown IQ format %d", iq_fmt);
+  *f = IqFmt{iq_fmt, iq_fmt == TSDR_IQ_CF32 ? 1.0f : scale};
+  if (reinterpret_cast<uintptr_t>(iq) % iq_bytes(*f)) return set_err(ctx, TSDR_EINVAL, "frames_iq: the buffer is not aligned to one sample of its format");
+  return TSDR_OK;
+}
+
 int tsdr_frames_iq_d(tsdr_ctx *ctx, tsdr_sync *sync, const void *iq, int iq_fmt, float scale, size_t nEch, size_t S, int y_t, int x_t,
                      float alpha, int do_align, float *imageOut_state, float *frames_out, float *raster_out, int *sync_idx,
                      int *n_frames) {
-  if (!ctx) return TSDR_EINVAL;
-  if (int rc = iq_args_check(ctx, iq, iq_fmt)) return rc;
-  IqScope fmt(ctx, iq_fmt, iq_fmt == TSDR_IQ_CF32 ? 1.0f : scale);
-  return tsdr_frames_d(ctx, sync, reinterpret_cast<const float *>(iq), nEch, S, y_t, x_t, alpha, do_align, imageOut_state, frames_out,
-                       raster_out, sync_idx, n_frames);
+  IqFmt f;
+  if (int rc = iq_fmt_arg(ctx, iq, iq_fmt, scale, &f)) return rc;
+  return frames_run(ctx, sync, reinterpret_cast<const float *>(iq), f, nEch, S, y_t, x_t, alpha, do_align, imageOut_state, frames_out,
+                    raster_out, sync_idx, n_frames);
 }
 
 int tsdr_frames_submit_iq_d(tsdr_ctx *ctx, tsdr_sync *sync, const void *iq, int iq_fmt, float scale, size_t nEch, size_t S, int y_t,
                             int x_t, float alpha, int do_align, float *imageOut_state, float *frames_out, float *raster_out,
                             int *sync_idx, int *n_frames) {
-  if (!ctx) return TSDR_EINVAL;
-  if (int rc = iq_args_check(ctx, iq, iq_fmt)) return rc;
-  IqScope fmt(ctx, iq_fmt, iq_fmt == TSDR_IQ_CF32 ? 1.0f : scale);
-  return tsdr_frames_submit_d(ctx, sync, reinterpret_cast<const float *>(iq), nEch, S, y_t, x_t, alpha, do_align, imageOut_state,
-                              frames_out, raster_out, sync_idx, n_frames);
+  IqFmt f;
+  if (int rc = iq_fmt_arg(ctx, iq, iq_fmt, scale, &f)) return rc;
+  return frames_submit(ctx, sync, reinterpret_cast<const float *>(iq), f, nEch, S, y_t, x_t, alpha, do_align, imageOut_state, frames_out,
+                       raster_out, sync_idx, n_frames);
 }
 
 int tsdr_frames_flush(tsdr_ctx *ctx) {

@@ -1194,8 +1194,8 @@ static int launch_tile(tsdr_ctx *ctx, const char *name, const float *in, size_t 
 // tile kernel applies) and, when `down` != null, the (h_out,w_out) image of each frame from the same launch.
 // Returns TSDR_OK and sets *did_down when the down image was produced here.
 // proj / got / plan_only: see raster_and_down_d.
-int raster_frames_d(tsdr_ctx *ctx, const float *in, int cplx, size_t in_stride, size_t S, int y_t, int x_t, int frames,
-                    float *out, size_t out_stride, float *down = nullptr, size_t down_stride = 0, int h_out = 0,
+int raster_frames_d(tsdr_ctx *ctx, const float *in, int cplx, IqFmt iqf, int precision, size_t in_stride, size_t S, int y_t, int x_t,
+                    int frames, float *out, size_t out_stride, float *down = nullptr, size_t down_stride = 0, int h_out = 0,
                     int w_out = 0, bool *did_down = nullptr, float *proj = nullptr, ProjLayout *got = nullptr,
                     bool plan_only = false, unsigned long long *keys = nullptr) {
   if (did_down) *did_down = false;
@@ -1206,13 +1206,13 @@ int raster_frames_d(tsdr_ctx *ctx, const float *in, int cplx, size_t in_stride, 
   const double sf = (double)S / (double)P;
   // TSDR_FAST exists for the steady-state frame loop (tsdr_frames*), whose input is IQ; the per-function entry
   // points (real input) always run the oracle's operation sequence
-  const bool exact = ctx->precision == TSDR_EXACT || !cplx || P >= (size_t(1) << 30);
+  const bool exact = precision == TSDR_EXACT || !cplx || P >= (size_t(1) << 30);
   // fused downgrade in the raster launch: only when both axes shrink (<= 66 x 130 candidates per tile)
   const bool want_down = down && !(y_t == h_out && x_t == w_out) && y_t >= 2 * 64 && x_t >= 2 * 128 &&
                          (double)y_t / h_out >= 1.0 && (double)x_t / w_out >= 1.0;
   TileParams q{};
   q.S = (unsigned)S; q.y_t = y_t; q.x_t = x_t; q.frames = frames;
-  if (cplx) q.iqf = ctx->iq_fmt;
+  if (cplx) q.iqf = iqf;
   // pairs of strips.  Measured on C2 -- round 2 (16-byte sample records, 3 workgroups per CU): G=1 0.138 ms, G=4 0.132 ms, G=41 0.146 ms;
   // round 4 (f32 samples, 4 per CU), the launch alone on two boxes: G=1 115.3, G=2 110.9 / 114.9, G=4 113.7 / 117.4, G=8 118.4, G=16 120.5 us
   // (C3: no difference; C5: G=2 1 % behind G=4).  The EXACT tile kernel (two workgroups per CU fewer) keeps four: 146.5 against 148.3 us
@@ -1423,7 +1423,7 @@ int raster_frames_d(tsdr_ctx *ctx, const float *in, int cplx, size_t in_stride, 
   dim3 grid((unsigned)stream_grid(ctx, ceil_div((size_t)y_t, 64) * 64 * (size_t)x_t), (unsigned)frames);
   if (cplx) {
     TSDR_LAUNCH(ctx, "raster_direct_iq", (k_raster_direct<true>), grid, dim3(256), 0, in, in_stride, (unsigned)S, y_t, x_t,
-                out, out_stride, ctx->iq_fmt);
+                out, out_stride, iqf);
   } else {
     TSDR_LAUNCH(ctx, "raster_direct_f32", (k_raster_direct<false>), grid, dim3(256), 0, in, in_stride, (unsigned)S, y_t, x_t,
                 out, out_stride, IqFmt{});
@@ -1502,8 +1502,8 @@ static DownPlan plan_down(size_t S, int y_t, int x_t, int h_out, int w_out, bool
 // sig_to_image |> downgradeImage for `frames` frames, straight from the signal (no raster in HBM)
 // proj / got / keys (FAST, IQ input): the kernel also leaves the images' projection partial sums (layout in *got) and clears the
 // frames' argmax keys; plan_only: nothing is launched, *got says what a real call would produce (ncp == 0: nothing).
-int down_frames_d(tsdr_ctx *ctx, const float *in, int cplx, size_t in_stride, size_t S, int y_t, int x_t, int h_out,
-                  int w_out, int frames, float *out, size_t out_stride, float *proj = nullptr, ProjLayout *got = nullptr,
+int down_frames_d(tsdr_ctx *ctx, const float *in, int cplx, IqFmt iqf, int precision, size_t in_stride, size_t S, int y_t, int x_t,
+                  int h_out, int w_out, int frames, float *out, size_t out_stride, float *proj = nullptr, ProjLayout *got = nullptr,
                   bool plan_only = false, unsigned long long *keys = nullptr) {
   int rc = check_geom(ctx, S, y_t, x_t);
   if (rc) return rc;
@@ -1512,11 +1512,11 @@ int down_frames_d(tsdr_ctx *ctx, const float *in, int cplx, size_t in_stride, si
   if (!same2 && (y_t < 2 || x_t < 2)) return set_err(ctx, TSDR_EINVAL, "imresize needs at least a 2x2 raster");
   if (frames <= 0) return TSDR_OK;
   // imresize returns a copy when the sizes already match: the raster IS the result
-  if (same2) return plan_only ? TSDR_OK : raster_frames_d(ctx, in, cplx, in_stride, S, y_t, x_t, frames, out, out_stride);
+  if (same2) return plan_only ? TSDR_OK : raster_frames_d(ctx, in, cplx, iqf, precision, in_stride, S, y_t, x_t, frames, out, out_stride);
   const size_t P = (size_t)y_t * x_t;
-  const bool exact = ctx->precision == TSDR_EXACT || !cplx;
+  const bool exact = precision == TSDR_EXACT || !cplx;
   DownPlan pl = plan_down(S, y_t, x_t, h_out, w_out, exact, true);
-  if (cplx) pl.q.iqf = ctx->iq_fmt;
+  if (cplx) pl.q.iqf = iqf;
   if (pl.fused) {
     const bool psum = !exact && got != nullptr && (plan_only || (proj != nullptr && keys != nullptr));
     if (psum) {
@@ -1581,7 +1581,8 @@ int down_frames_d(tsdr_ctx *ctx, const float *in, int cplx, size_t in_stride, si
   if (!ras) return TSDR_ENOMEM;
   ras += (size_t)(ctx->pipe_lane & 3) * P;
   for (int f = 0; f < frames; ++f) {
-    rc = raster_frames_d(ctx, cplx ? iq_at(in, (size_t)f * in_stride, iq_bytes(ctx->iq_fmt)) : in + (size_t)f * in_stride, cplx, in_stride, S, y_t, x_t, 1, ras, P);
+    rc = raster_frames_d(ctx, cplx ? iq_at(in, (size_t)f * in_stride, iq_bytes(iqf)) : in + (size_t)f * in_stride, cplx, iqf, precision,
+                         in_stride, S, y_t, x_t, 1, ras, P);
     if (rc) return rc;
     rc = resize2d_d(ctx, ras, y_t, x_t, h_out, w_out, out + (size_t)f * out_stride);
     if (rc) return rc;
@@ -1591,12 +1592,12 @@ int down_frames_d(tsdr_ctx *ctx, const float *in, int cplx, size_t in_stride, si
 
 // Sync guard (guard.h): the tiling of the EXACT raster-free kernel for this geometry, whose workgroup body the guard's
 // kernel (sync.hip) runs on the frames it flags.  false: this geometry has no fused exact kernel.
-bool guard_image_plan(tsdr_ctx *ctx, size_t S, int y_t, int x_t, int h_out, int w_out, DownParams *q, size_t *lds) {
+bool guard_image_plan(tsdr_ctx *ctx, IqFmt iqf, size_t S, int y_t, int x_t, int h_out, int w_out, DownParams *q, size_t *lds) {
   if (check_geom(ctx, S, y_t, x_t)) return false;
   if ((y_t == h_out && x_t == w_out) || y_t < 2 || x_t < 2) return false;
   DownPlan pl = plan_down(S, y_t, x_t, h_out, w_out, /*exact=*/true, false, /*guard_tiles=*/true);
   if (!pl.fused) return false;
-  pl.q.iqf = ctx->iq_fmt;
+  pl.q.iqf = iqf;
   *q = pl.q;
   *lds = pl.lds;
   return true;
@@ -1606,7 +1607,7 @@ bool guard_image_plan(tsdr_ctx *ctx, size_t S, int y_t, int x_t, int h_out, int 
 // proj != nullptr: room for the projection partial sums of every (h_out, w_out) image (layout: sync_layout.h); when the
 // FAST tile kernel runs it leaves them there and describes them in *got (ncp == 0: not produced -- the caller then
 // forms the projections from the images).  plan_only: nothing is launched, *got says what a real call would produce.
-int raster_and_down_d(tsdr_ctx *ctx, const float *in, int cplx, size_t in_stride, size_t S, int y_t, int x_t, int h_out,
+int raster_and_down_d(tsdr_ctx *ctx, const float *in, int cplx, IqFmt iqf, int precision, size_t in_stride, size_t S, int y_t, int x_t, int h_out,
                       int w_out, int frames, float *raster, size_t raster_stride, float *down, size_t down_stride,
                       float *proj, ProjLayout *got, bool plan_only, unsigned long long *keys) {
   if (got) *got = ProjLayout{};
@@ -1614,7 +1615,7 @@ int raster_and_down_d(tsdr_ctx *ctx, const float *in, int cplx, size_t in_stride
   // staged samples and leaves the projection partial sums itself (round 3: 54 us at C2 against the walk's 77 us with
   // out == null -- the walk evaluates all 2.9 M raster pixels of a frame for the 1.8 M that are taps).  Other geometries
   // fall through to the walk, then to the raster + resize fallback.
-  if (!raster && ctx->precision == TSDR_FAST && cplx && !ctx->opt_fast_walk_only) {
+  if (!raster && precision == TSDR_FAST && cplx && !ctx->opt_fast_walk_only) {
     ProjLayout pl{};
     const DownPlan dp = plan_down(S, y_t, x_t, h_out, w_out, false);
     // ... where a tile of at least 32 columns fits (C2: 0.115 samples per raster pixel, 64 columns, 0.102 vs 0.123 ms per buffer
@@ -1625,7 +1626,7 @@ int raster_and_down_d(tsdr_ctx *ctx, const float *in, int cplx, size_t in_stride
     const double spp = (double)S / ((double)y_t * (double)x_t);   // samples per raster pixel
     if (dp.fused && dp.q.TC >= (spp > 0.5 ? 16 : 32) && spp <= (double)ctx->opt_down_spp_max_pct * 0.01 && !(y_t == h_out && x_t == w_out) &&
         check_geom(ctx, S, y_t, x_t) == TSDR_OK && y_t >= 2 && x_t >= 2) {
-      int rc = down_frames_d(ctx, in, cplx, in_stride, S, y_t, x_t, h_out, w_out, frames, down, down_stride, proj, got ? &pl : nullptr,
+      int rc = down_frames_d(ctx, in, cplx, iqf, precision, in_stride, S, y_t, x_t, h_out, w_out, frames, down, down_stride, proj, got ? &pl : nullptr,
                              plan_only, keys);
       if (rc) return rc;
       if (got) *got = pl;
@@ -1635,7 +1636,7 @@ int raster_and_down_d(tsdr_ctx *ctx, const float *in, int cplx, size_t in_stride
   // FAST with a raster (option "raster_split"; A/B of round 4): the rasters by the store-aligned ("sheared") raster-only
   // kernel of raster_shear.hip, the images + projection sums by the raster-free kernel -- two launches, IQ read twice,
   // instead of the one walk that produces raster, image and sums with misaligned column stores
-  if (raster && ctx->precision == TSDR_FAST && cplx && ctx->opt_raster_split && ctx->iq_fmt.kind == IQK_CF32) {   // (the A/B kernel reads ComplexF32 only)
+  if (raster && precision == TSDR_FAST && cplx && ctx->opt_raster_split && iqf.kind == IQK_CF32) {   // (the A/B kernel reads ComplexF32 only)
     const DownPlan dp = plan_down(S, y_t, x_t, h_out, w_out, false);
     const double spp = (double)S / ((double)y_t * (double)x_t);
     if (dp.fused && dp.q.TC >= 32 && spp <= 0.5 && !(y_t == h_out && x_t == w_out) && check_geom(ctx, S, y_t, x_t) == TSDR_OK && y_t >= 64 && x_t >= 128) {
@@ -1644,23 +1645,23 @@ int raster_and_down_d(tsdr_ctx *ctx, const float *in, int cplx, size_t in_stride
       if (rc) return rc;
       if (did) {
         ProjLayout pl{};
-        rc = down_frames_d(ctx, in, cplx, in_stride, S, y_t, x_t, h_out, w_out, frames, down, down_stride, proj, got ? &pl : nullptr, plan_only, keys);
+        rc = down_frames_d(ctx, in, cplx, iqf, precision, in_stride, S, y_t, x_t, h_out, w_out, frames, down, down_stride, proj, got ? &pl : nullptr, plan_only, keys);
         if (rc) return rc;
         if (got) *got = pl;
         return TSDR_OK;
       }
     }
   }
-  if (raster || (ctx->precision == TSDR_FAST && cplx)) {
+  if (raster || (precision == TSDR_FAST && cplx)) {
     bool did = false;
     ProjLayout pl{};
-    int rc = raster_frames_d(ctx, in, cplx, in_stride, S, y_t, x_t, frames, raster, raster_stride, down, down_stride, h_out,
+    int rc = raster_frames_d(ctx, in, cplx, iqf, precision, in_stride, S, y_t, x_t, frames, raster, raster_stride, down, down_stride, h_out,
                              w_out, &did, proj, got ? &pl : nullptr, plan_only, keys);
     if (rc) return rc;
     if (did) { if (got) *got = pl; return TSDR_OK; }
   }
   if (plan_only) return TSDR_OK;
-  return down_frames_d(ctx, in, cplx, in_stride, S, y_t, x_t, h_out, w_out, frames, down, down_stride);
+  return down_frames_d(ctx, in, cplx, iqf, precision, in_stride, S, y_t, x_t, h_out, w_out, frames, down, down_stride);
 }
 
 }  // namespace tsdr
@@ -1683,7 +1684,7 @@ int tsdr_sig_to_image_d(tsdr_ctx *ctx, const float *sig, size_t S, int y_t, int 
   if (!ctx || !sig || !img) return TSDR_EINVAL;
   TSDR_PTR_ALIGNED(ctx, "sig_to_image", sig, 4);
   TSDR_PTR_ALIGNED(ctx, "sig_to_image", img, 4);
-  return raster_frames_d(ctx, sig, 0, S, S, y_t, x_t, 1, img, (size_t)y_t * x_t);
+  return raster_frames_d(ctx, sig, 0, IqFmt{}, TSDR_EXACT, S, S, y_t, x_t, 1, img, (size_t)y_t * x_t);
 }
 
 int tsdr_resize2d_d(tsdr_ctx *ctx, const float *img, int h_in, int w_in, int h_out, int w_out, float *out) {

@@ -824,9 +824,9 @@ __global__ __launch_bounds__(512, 2) void k_guard(GuardAllArgs a) {
 // Sync guard: frames whose FAST-mode decision was closer than g.thr are re-evaluated in the exact sequence (image, projections
 // in the reference's order, beta scan); img / keys of those frames are overwritten, everything else is left alone.
 // plan_only: report whether this geometry can be guarded at all.
-bool guard_image_plan(tsdr_ctx *ctx, size_t S, int y_t, int x_t, int h_out, int w_out, DownParams *q, size_t *lds);
+bool guard_image_plan(tsdr_ctx *ctx, IqFmt iqf, size_t S, int y_t, int x_t, int h_out, int w_out, DownParams *q, size_t *lds);
 
-int sync_guard_d(tsdr_sync *s, const float *iq, size_t S, int y_t, int x_t, int frames, float *img, size_t img_stride,
+int sync_guard_d(tsdr_sync *s, const float *iq, IqFmt iqf, size_t S, int y_t, int x_t, int frames, float *img, size_t img_stride,
                  unsigned long long *keys, float *proj, const GuardArgs &g, bool *can, bool plan_only) {
   tsdr_ctx *ctx = s->ctx;
   if (can) *can = false;
@@ -834,7 +834,7 @@ int sync_guard_d(tsdr_sync *s, const float *iq, size_t S, int y_t, int x_t, int 
   return TSDR_OK;
 #else
   GuardAllArgs a{};
-  if (!guard_image_plan(ctx, S, y_t, x_t, s->y_t, s->x_t, &a.dq, &a.lds_bytes)) return TSDR_OK;
+  if (!guard_image_plan(ctx, iqf, S, y_t, x_t, s->y_t, s->x_t, &a.dq, &a.lds_bytes)) return TSDR_OK;
   {  // the launch's dynamic LDS (exact tiles of up to 96 KiB + their column-sum scratch) plus k_guard's static arrays (list,
      // colk, ticket words: < 4 KiB) must fit what the kernel opted in to; otherwise the frame loop falls back to whole
      // buffers in TSDR_EXACT, as for geometries without a fused exact kernel
@@ -866,7 +866,7 @@ int sync_guard_d(tsdr_sync *s, const float *iq, size_t S, int y_t, int x_t, int 
     a.g.flags = g.flags + f0;
     a.frames = nf;
     // (frames are offset in bytes: an sc16 sample is one float's worth, an 8-bit one half of that)
-    a.iq = iq_at(iq, (size_t)f0 * S, iq_bytes(ctx->iq_fmt)); a.in_stride = S; a.img = img + (size_t)f0 * img_stride; a.img_stride = img_stride;
+    a.iq = iq_at(iq, (size_t)f0 * S, iq_bytes(iqf)); a.in_stride = S; a.img = img + (size_t)f0 * img_stride; a.img_stride = img_stride;
     a.tilesA = (int)(ceil_div((size_t)y, 64) * (size_t)a.dq.tiles_c);
     a.y_t = y; a.x_t = x;
     a.proj_stride = proj_floats(y, x, pl); a.ncp = pl.ncp; a.nrp = pl.nrp;
@@ -916,25 +916,21 @@ int sync_workspace(tsdr_sync *s, int frames, int slot, int nslots, const ProjLay
   return TSDR_OK;
 }
 
+// done: an event to record behind the launch (the pipeline's "tail of this buffer done"), or nullptr
 int shift_iir_d(tsdr_ctx *ctx, tsdr_sync *s, const float *img, size_t img_stride, int h, int w, int frames,
                 const unsigned long long *keys, int do_align, float alpha, float *state, float *frames_out,
-                int *sync_idx) {
+                int *sync_idx, hipEvent_t done) {
   const size_t npx = (size_t)h * w;
   IirArgs I;
   iir_args(s, img, img_stride, h, w, frames, keys, do_align, alpha, state, frames_out, sync_idx, &I);
-  if (ctx->launch_stop_ev && !ctx->prof_on) {
-    // the pipeline's "tail of this buffer done" event is this dispatch's own completion signal: no marker packet behind it
-    hipEvent_t ev = ctx->launch_stop_ev;
-    ctx->launch_stop_ev = nullptr;
-    hipExtLaunchKernelGGL(k_shift_iir, dim3((unsigned)ceil_div(npx, 256)), dim3(256), 0, ctx->launch_stream, nullptr, ev, 0, I);
+  if (done && ctx->opt_pipe_ext_event && !ctx->prof_on) {
+    // the event is this dispatch's own completion signal: no marker packet behind it
+    hipExtLaunchKernelGGL(k_shift_iir, dim3((unsigned)ceil_div(npx, 256)), dim3(256), 0, ctx->launch_stream, nullptr, done, 0, I);
     hipError_t le = hipGetLastError();
     if (le != hipSuccess) return hip_fail(ctx, le, "shift_iir");
   } else {
-    const bool rec = ctx->launch_stop_ev != nullptr;
-    hipEvent_t ev = ctx->launch_stop_ev;
-    ctx->launch_stop_ev = nullptr;
     TSDR_LAUNCH(ctx, "shift_iir", k_shift_iir, dim3((unsigned)ceil_div(npx, 256)), dim3(256), 0, I);
-    if (rec) TSDR_HIP(ctx, hipEventRecord(ev, ctx->launch_stream));
+    if (done) TSDR_HIP(ctx, hipEventRecord(done, ctx->launch_stream));
   }
   if (do_align) s->cur ^= 1;
   return TSDR_OK;

@@ -173,6 +173,81 @@ def test_generic_entry_equals_the_named_entries(ctx, tsdr, synth, precision, pip
         ctx.set_precision("fast")
 
 
+_PINNED = {}      # (fmt, want_raster) -> the capture and what one tsdr_frames_iq_d per buffer returns for it
+
+
+def _pinned_case(tsdr, synth, fmt, want_raster):
+    """4 buffers of 2 frames + 7 samples each at 2 MS/s, 1056 x 628 at 60 Hz, and their reference: one tsdr_frames_iq_d per
+    buffer on a context and a SyncXY of its own.  Computed once per (format, rasters or not), shared by the eight arrangements."""
+    if (fmt, want_raster) not in _PINNED:
+        Fs, x_t, y_t, nfr, nbuf = 2.0e6, 1056, 628, 2, 4
+        S = synth.samples_per_frame(Fs, 60.0)
+        nEch = nfr * S + 7
+        q, scale = R.quantise(synth.synth_leak(Fs, x_t, y_t, 60.0, nbuf * nEch), fmt)
+        case = dict(fmt=fmt, q=q, scale=scale, S=S, nEch=nEch, x_t=x_t, y_t=y_t, nfr=nfr, nbuf=nbuf, want_raster=want_raster)
+        ref = tsdr.Context(0)
+        try:
+            assert ref.precision == "fast"
+            case["want"] = _four_buffers(ref, tsdr, case, submit=False)
+        finally:
+            ref.close()
+        for a in case["want"] + (q,):
+            a.setflags(write=False)
+        _PINNED[(fmt, want_raster)] = case
+    return _PINNED[(fmt, want_raster)]
+
+
+def _four_buffers(ctx, tsdr, case, submit):
+    """-> (frames, rasters, sync_idx, final state) of the case's buffers through tsdr_frames_iq_d or tsdr_frames_submit_iq_d + flush"""
+    api = importlib.import_module("tempestsdr_jl_amd.api")
+    S, nEch, x_t, y_t, nfr, nbuf, fmt = (case[k] for k in ("S", "nEch", "x_t", "y_t", "nfr", "nbuf", "fmt"))
+    P, bps = x_t * y_t, R.BYTES[fmt]
+    sync = tsdr.SyncXY(ctx, 600, 800)
+    d_in, d_state = ctx.upload(case["q"]), ctx.upload(np.zeros(NPX, np.float32))
+    d_fr, d_ix = ctx.dev_alloc(nbuf * nfr * NPX * 4), ctx.dev_alloc(nbuf * nfr * 8)
+    d_ra = ctx.dev_alloc(nbuf * nfr * P * 4) if case["want_raster"] else None
+    try:
+        for b in range(nbuf):
+            n = api.frames_iq_d(ctx, sync, d_in + b * nEch * bps, fmt, case["scale"], nEch, S, y_t, x_t, np.float32(0.1), True, d_state,
+                                d_fr + b * nfr * NPX * 4, d_ra + b * nfr * P * 4 if d_ra is not None else None, d_ix + b * nfr * 8,
+                                submit=submit)
+            assert n == nfr
+        if submit:
+            api.frames_flush(ctx)
+        ctx.synchronize()
+        return (ctx.download(d_fr, (nbuf * nfr * NPX,), np.uint32),
+                ctx.download(d_ra, (nbuf * nfr * P,), np.uint32) if d_ra is not None else np.zeros(0, np.uint32),
+                ctx.download(d_ix, (nbuf * nfr * 2,), np.int32), ctx.download(d_state, (NPX,), np.uint32))
+    finally:
+        sync.close()
+        for p in (d_in, d_state, d_fr, d_ix, d_ra):
+            if p is not None:
+                ctx.dev_free(p)
+
+
+@pytest.mark.parametrize("pin", range(8))
+@pytest.mark.parametrize("want_raster", [True, False])
+@pytest.mark.parametrize("fmt", ["sc16", "uc8"])
+def test_integer_iq_through_every_pinned_arrangement(ctx, tsdr, synth, fmt, want_raster, pin):
+    """An integer format reaches the pipeline's arrangements other than the default choice only when one is pinned.  Every
+    "pipe_pin" 0...7 (one stream, image lane + tail lane on three stream pairs, two equal lanes on three pairs, three equal lanes),
+    four buffers so that the three slots wrap, FAST with do_align: tsdr_frames_submit_iq_d + flush equals one tsdr_frames_iq_d
+    per buffer on a fresh context and SyncXY, bit for bit -- frames, rasters, sync indices and the final state."""
+    case = _pinned_case(tsdr, synth, fmt, want_raster)
+    assert ctx.precision == "fast"
+    _restart_guard_window(ctx, 1)
+    ctx.set_option("pipe_pin", pin)
+    try:
+        got = _four_buffers(ctx, tsdr, case, submit=True)
+        info = ctx.pipeline_info()
+        assert info["chosen"] == pin and "pinned" in info["text"], info
+    finally:
+        ctx.set_option("pipe_pin", -1)
+    for what, a, b in zip(("frames", "raster", "sync_idx", "state"), case["want"], got):
+        assert a.size == b.size and np.array_equal(a, b), what
+    assert np.any(got[0]) and np.any(got[3]), "frames and state are not all zero"
+
+
 # (Fs, maxDelay, samples): n = min(2 * round(maxDelay * Fs), samples)
 SEARCH_LENGTHS = {
     "pow2": (1048576.0, 0.5, 1 << 20),              # n = 2^20: the power-of-two route, first pass loader
