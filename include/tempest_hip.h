@@ -257,7 +257,8 @@ int tsdr_autocorr_iq_d(tsdr_ctx *ctx, const float *iq, size_t len, double Fs, do
  * over them).  *idx is 0-based inside the window, first maximum, NaN maximal; blocking like tsdr_argmax_d. */
 int tsdr_autocorr_search_d(tsdr_ctx *ctx, const float *x, int is_iq, size_t len, double Fs, double minDelay, double maxDelay,
                            int log_scale, float *out, size_t *n_out, size_t win_lo, size_t win_cnt, size_t *idx, float *val);
-/* IQ sample formats of the generic entry points (tsdr_frames_iq_d, tsdr_frames_submit_iq_d, tsdr_autocorr_search_iq_d).
+/* IQ sample formats of the generic entry points (tsdr_frames_iq_d, tsdr_frames_submit_iq_d, tsdr_autocorr_search_iq_d, and the
+ * `_iq` forms of GetSpectrum.jl's and Demodulation.jl's functions further down).
  * One conversion rule, the same in every kernel that reads IQ, with ONE rounding per component (the product):
  *   TSDR_IQ_CF32  float re, float im (8 bytes)      the value itself; `scale` is ignored
  *   TSDR_IQ_SC16  int16 I, int16 Q   (4 bytes)      ComplexF32(f32(I) * scale, f32(Q) * scale)
@@ -302,6 +303,40 @@ int tsdr_welch_d(tsdr_ctx *ctx, const float *sig, int is_complex, size_t len, si
 /* getWaterfall(fe,sig;sizeFFT): Float64 (sizeFFT x nbSeg) linear power  GetSpectrum.jl:54-66 */
 int tsdr_waterfall(tsdr_ctx *ctx, const float *sig, int is_complex, size_t len, size_t sizeFFT, double *sMatrix);
 int tsdr_waterfall_d(tsdr_ctx *ctx, const float *sig, int is_complex, size_t len, size_t sizeFFT, double *sMatrix);
+/* ---- the same three, and Demodulation.jl's functions, on integer IQ as the SDR stored it (sc16, sc8, uc8) ----------------------
+ * `iq`, `iq_fmt` (TSDR_IQ_*) and `scale` mean what they mean in tsdr_frames_iq_d: `iq` holds the samples in that format, every
+ * component becomes (f32(code) - offset) * scale in the kernels' own loaders.  A raw ring slot (tsdr_ring_create fmt 2 / 4 / 6)
+ * or a `.dat` capture in :short layout (DatBinaryFiles.jl:44-66) goes in as it is.
+ *  1. BIT IDENTITY.  Every output equals, bit for bit, what the ComplexF32 entry point (is_complex = 1) writes for the same
+ *     samples expanded on the host with (q.astype(float32) - offset) * float32(scale): the dB spectrum, the Welch sum, the
+ *     Float64 waterfall, the demodulators' outputs and invert_am's device-reduced maximum.  No tolerance: the loaders form the
+ *     same f32 values, and everything behind them is the ComplexF32 route's arithmetic.
+ *  2. ROUTES.  TSDR_IQ_CF32 is the `_d` entry point with is_complex = 1 (scale ignored).  The transform route is chosen from the
+ *     lengths alone, so an integer buffer takes the route ComplexF32 input of that length takes, whatever its alignment.
+ *     Read as integers, never expanded in HBM: sizeFFT = 1024 (one wavefront per segment); getWelch at every other 2^a 3^b 5^c
+ *     sizeFFT <= 4096 and getWaterfall at those of them with a three-step row kernel (128 256 500 512 768 1000 1200 1280 1600
+ *     2000 2048 2500 3200 4000 4096) -- segment transforms in LDS; every 2^a 3^b 5^c length that takes two or more passes
+ *     (tsdr_fft_plan: 4096, 8192, 10000, 65536, 80000 ...; the first pass's loader converts).  Expanded first into context
+ *     workspace (8 bytes per sample, by tsdr_iq_expand_d's kernels) and then run on the ComplexF32 route: what remains -- the
+ *     transforms of ONE pass outside the LDS segment routes (lengths <= 256, single-factor lengths such as 1000 in
+ *     tsdr_spectrum_iq_d) and every length with a prime factor above 5 (Bluestein: 1031).
+ *  3. ALIGNMENT.  `iq` is aligned to ONE SAMPLE -- 4 bytes for sc16, 2 for sc8 / uc8, 8 for cf32 -- and base + k * bytes_per_sample
+ *     of a larger buffer is valid for every k and gives the bits of a fresh allocation.  y / out are float-aligned, sMatrix
+ *     8-byte aligned, tsdr_iq_expand_d's cf32_out 8-byte aligned.  A pointer that is not, or an unknown iq_fmt, is TSDR_EINVAL
+ *     with the argument's name (iq, iq_fmt, y, out, sMatrix, cf32_out) in tsdr_last_error, before anything is enqueued.
+ *  4. EDGE CASES are the ComplexF32 twin's: N == 0 / n == 0 do nothing (tsdr_invert_am_iq_d: TSDR_EINVAL, as tsdr_invert_am_d),
+ *     sizeFFT == 0 is TSDR_EINVAL, len / sizeFFT == 0 gives zeros (-Inf dB) in y and leaves sMatrix untouched; NULL as the twin.
+ *     The input is never written; nothing is written outside the documented outputs.
+ * The `name` forms (host pointers, what the Julia shim binds) upload the RAW bytes -- 2 or 4 per sample -- not expanded ones. */
+/* getSpectrum(fs,sig;N) of integer IQ                           GetSpectrum.jl:21-30 */
+int tsdr_spectrum_iq(tsdr_ctx *ctx, const void *iq, int iq_fmt, float scale, size_t N, int lin, float *y);
+/* getWelch(fe,sig;sizeFFT) of integer IQ                        GetSpectrum.jl:36-52 */
+int tsdr_welch_iq(tsdr_ctx *ctx, const void *iq, int iq_fmt, float scale, size_t len, size_t sizeFFT, int lin, float *y);
+/* getWaterfall(fe,sig;sizeFFT) of integer IQ                    GetSpectrum.jl:54-66 */
+int tsdr_waterfall_iq(tsdr_ctx *ctx, const void *iq, int iq_fmt, float scale, size_t len, size_t sizeFFT, double *sMatrix);
+/* their device-pointer forms (tsdr_spectrum_iq_d, tsdr_welch_iq_d, tsdr_waterfall_iq_d), the demodulators on integer IQ
+ * (tsdr_am_demod_iq_d, tsdr_abs2_iq_d, tsdr_invert_am_iq_d, tsdr_fm_demod_iq_d: device pointers only) and tsdr_iq_expand_d */
+#include "tempest_hip_iq.h"
 /* complex f32 FFT of arbitrary length (FFTW.jl fft / ifft semantics: forward
  * unnormalised, inverse scaled 1/n); dir<0 forward.  batch transforms, contiguous. */
 int tsdr_fft_c2c(tsdr_ctx *ctx, const float *in, float *out, size_t n, size_t batch, int dir);
@@ -487,7 +522,8 @@ int tsdr_frames_pipeline_info(tsdr_ctx *ctx, int *trials_left, int *chosen, floa
  * tsdr_ring_take_d then hands out nEch int16 pairs (cast the pointer) for tsdr_frames_sc16_d / _submit_sc16_d with the
  * same scale, and nothing expands them.  8-bit I/Q (a quarter of the PCIe bytes, 2 bytes per sample; conversion rule at
  * TSDR_IQ_*): fmt 3: int8 pairs ("sc8") expanded on the device to ComplexF32 with the same product as fmt 1; fmt 4: int8
- * pairs that stay as they are, for tsdr_frames_iq_d / _submit_iq_d / tsdr_autocorr_search_iq_d(TSDR_IQ_SC8); fmt 5: uint8
+ * pairs that stay as they are, for tsdr_frames_iq_d / _submit_iq_d / tsdr_autocorr_search_iq_d(TSDR_IQ_SC8) and the `_iq_d`
+ * spectra and demodulators (tsdr_spectrum_iq_d ... tsdr_fm_demod_iq_d); fmt 5: uint8
  * pairs ("uc8") expanded; fmt 6: uint8 pairs raw (TSDR_IQ_UC8).  Counters as print_summary (:333-341). */
 typedef struct tsdr_ring tsdr_ring;
 int tsdr_ring_create(tsdr_ctx *ctx, size_t nEch, int depth, int fmt, float scale, tsdr_ring **out);

@@ -105,6 +105,10 @@ _SIGS = {
     "tsdr_waterfall_d": (C.c_int, [vp, vp, C.c_int, c_sz, c_sz, vp]),
     "tsdr_fft_c2c": (C.c_int, [vp, vp, vp, c_sz, c_sz, C.c_int]),
     "tsdr_fft_c2c_d": (C.c_int, [vp, vp, vp, c_sz, c_sz, C.c_int]),
+    # ... and Demodulation.jl's functions on integer IQ (iq, iq_fmt, scale as tsdr_frames_iq_d)
+    "tsdr_spectrum_iq": (C.c_int, [vp, vp, C.c_int, C.c_float, c_sz, C.c_int, vp]),
+    "tsdr_welch_iq": (C.c_int, [vp, vp, C.c_int, C.c_float, c_sz, c_sz, C.c_int, vp]),
+    "tsdr_waterfall_iq": (C.c_int, [vp, vp, C.c_int, C.c_float, c_sz, c_sz, vp]),
     "tsdr_fft_plan": (C.c_int, [c_sz, vp, C.c_int]),
     # FrameSynchronisation.jl
     "tsdr_sync_create": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(vp)]),
@@ -189,10 +193,28 @@ _SIGS = {
     "tsdr_group_timing": (C.c_int, [vp, c_i, c_d]),
 }
 
+# include/tempest_hip_iq.h (the header tempest_hip.h includes): the device-pointer forms of the spectra and demodulators on integer
+# IQ, and the ring's expansion (iq, iq_fmt, scale as tsdr_frames_iq_d)
+_SIGS_IQ = {
+    "tsdr_spectrum_iq_d": (C.c_int, [vp, vp, C.c_int, C.c_float, c_sz, C.c_int, vp]),
+    "tsdr_welch_iq_d": (C.c_int, [vp, vp, C.c_int, C.c_float, c_sz, c_sz, C.c_int, vp]),
+    "tsdr_waterfall_iq_d": (C.c_int, [vp, vp, C.c_int, C.c_float, c_sz, c_sz, vp]),
+    "tsdr_am_demod_iq_d": (C.c_int, [vp, vp, C.c_int, C.c_float, c_sz, vp]),
+    "tsdr_abs2_iq_d": (C.c_int, [vp, vp, C.c_int, C.c_float, c_sz, vp]),
+    "tsdr_invert_am_iq_d": (C.c_int, [vp, vp, C.c_int, C.c_float, c_sz, vp]),
+    "tsdr_fm_demod_iq_d": (C.c_int, [vp, vp, C.c_int, C.c_float, c_sz, vp]),
+    "tsdr_iq_expand_d": (C.c_int, [vp, vp, C.c_int, C.c_float, c_sz, vp]),
+}
+
 
 def exported_names():
     """Every symbol include/tempest_hip.h declares (kept in sync by tests/test_abi.py)."""
     return sorted(_SIGS)
+
+
+def exported_names_iq():
+    """Every symbol include/tempest_hip_iq.h declares (kept in sync by tests/test_iq_spectra_host.py)."""
+    return sorted(_SIGS_IQ)
 
 
 def _share_torch_hip_runtime():
@@ -220,7 +242,7 @@ def load():
             f"{LIB_PATH} not found: build it with `python tempestsdr.jl_amd/build.py` "
             "(there is no CPU fallback)")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in _SIGS.items():
+    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_IQ.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI is incomplete
         fn.restype = res
         fn.argtypes = args

@@ -206,7 +206,31 @@ class Context:
         return out
 
     # -- Demodulation.jl ----------------------------------------------------------------
-    def amDemod(self, sig, *, dtype=None):
+    # iq_fmt "sc16" / "sc8" / "uc8" (keyword only, as autocorr_search): sig is integer IQ as the hardware stores it -- an int16 /
+    # int8 / uint8 array of 2*n interleaved components (strict about the dtype); every sample is converted with iq_scale in the
+    # kernel's loader, and the result has the bits of the same call on expand_iq(sig, iq_fmt, iq_scale).
+    def _demod_iq(self, what, sym, sig, iq_fmt, iq_scale, dtype):
+        if dtype is not None:
+            raise AssertionError(f"{what}: iq_fmt is a Float32 path (dtype must be None)")
+        a, code, n = _int_iq(sig, iq_fmt, what)
+        out = np.empty(n, np.float32)
+        if n == 0 and what != "invert_amDemod":
+            return out
+        d_in = self.upload(a) if n else 0
+        d_out = None
+        try:
+            d_out = self.dev_alloc(max(n, 1) * 4)
+            self.call(sym, C.c_void_p(d_in), code, C.c_float(iq_scale), n, C.c_void_p(d_out))
+            return self.download(d_out, (n,), np.float32)
+        finally:
+            if d_in:
+                self.dev_free(d_in)
+            if d_out is not None:
+                self.dev_free(d_out)
+
+    def amDemod(self, sig, *, dtype=None, iq_fmt=None, iq_scale=1.0):
+        if iq_fmt is not None:
+            return self._demod_iq("amDemod", "tsdr_am_demod_iq_d", sig, iq_fmt, iq_scale, dtype)
         if _is64(dtype):
             z = _c128(sig, "amDemod")
             out = np.empty(z.shape, np.float64)
@@ -217,7 +241,9 @@ class Context:
         self.call("tsdr_am_demod", _ptr(z), z.size, _ptr(out))
         return out
 
-    def invert_amDemod(self, sig, *, dtype=None):
+    def invert_amDemod(self, sig, *, dtype=None, iq_fmt=None, iq_scale=1.0):
+        if iq_fmt is not None:
+            return self._demod_iq("invert_amDemod", "tsdr_invert_am_iq_d", sig, iq_fmt, iq_scale, dtype)
         if _is64(dtype):
             z = _c128(sig, "invert_amDemod")
             out = np.empty(z.shape, np.float64)
@@ -228,7 +254,9 @@ class Context:
         self.call("tsdr_invert_am", _ptr(z), z.size, _ptr(out))
         return out
 
-    def fmDemod(self, sig, *, dtype=None):
+    def fmDemod(self, sig, *, dtype=None, iq_fmt=None, iq_scale=1.0):
+        if iq_fmt is not None:
+            return self._demod_iq("fmDemod", "tsdr_fm_demod_iq_d", sig, iq_fmt, iq_scale, dtype)
         if _is64(dtype):
             z = _c128(sig, "fmDemod")
             out = np.empty(z.shape, np.float64)
@@ -239,7 +267,9 @@ class Context:
         self.call("tsdr_fm_demod", _ptr(z), z.size, _ptr(out))
         return out
 
-    def abs2(self, sig, *, dtype=None):
+    def abs2(self, sig, *, dtype=None, iq_fmt=None, iq_scale=1.0):
+        if iq_fmt is not None:
+            return self._demod_iq("abs2", "tsdr_abs2_iq_d", sig, iq_fmt, iq_scale, dtype)
         if _is64(dtype):
             z = _c128(sig, "abs2")
             out = np.empty(z.shape, np.float64)
@@ -397,7 +427,20 @@ class Context:
             return a.astype(np.complex64, copy=False), 1
         return a.astype(np.float32, copy=False), 0
 
-    def getSpectrum(self, fs, sig, N=None, lin=False, *, dtype=None):
+    def getSpectrum(self, fs, sig, N=None, lin=False, *, dtype=None, iq_fmt=None, iq_scale=1.0):
+        """iq_fmt "sc16" / "sc8" / "uc8" (here and in getWelch / getWaterfall; keyword only): sig is integer IQ as the hardware
+        stores it -- an int16 / int8 / uint8 array of 2*n interleaved components -- uploaded as it is and converted with iq_scale
+        in the transform's loader (tsdr_spectrum_iq / tsdr_welch_iq / tsdr_waterfall_iq)."""
+        if iq_fmt is not None:
+            if dtype is not None:
+                raise AssertionError("getSpectrum: iq_fmt is a Float32 path (dtype must be None)")
+            a, code, n = _int_iq(sig, iq_fmt, "getSpectrum")
+            N = n if N is None else int(N)
+            if N > n:
+                raise IndexError("N exceeds the signal length (BoundsError in the reference)")
+            y = np.empty(N, np.float32)
+            self.call("tsdr_spectrum_iq", _ptr(a), code, C.c_float(iq_scale), N, int(lin), _ptr(y))
+            return (np.arange(N) / N - 0.5) * fs, y
         f64 = _is64(dtype)
         if f64:
             if not (isinstance(sig, np.ndarray) and sig.dtype in (np.float64, np.complex128)):
@@ -419,7 +462,14 @@ class Context:
             raise AssertionError(f"{what}: expected a float64 / complex128 array, got {getattr(sig, 'dtype', type(sig))}")
         return np.ascontiguousarray(sig), int(np.iscomplexobj(sig))
 
-    def getWelch(self, fe, sig, sizeFFT=1024, lin=False, *, dtype=None):
+    def getWelch(self, fe, sig, sizeFFT=1024, lin=False, *, dtype=None, iq_fmt=None, iq_scale=1.0):
+        if iq_fmt is not None:
+            if dtype is not None:
+                raise AssertionError("getWelch: iq_fmt is a Float32 path (dtype must be None)")
+            a, code, n = _int_iq(sig, iq_fmt, "getWelch")
+            y = np.empty(int(sizeFFT), np.float32)
+            self.call("tsdr_welch_iq", _ptr(a), code, C.c_float(iq_scale), n, int(sizeFFT), int(lin), _ptr(y))
+            return (np.arange(sizeFFT) / sizeFFT - 0.5) * fe, y
         f64 = _is64(dtype)
         a, cplx = self._sig64(sig, "getWelch") if f64 else self._sig(sig)
         y = np.empty(int(sizeFFT), np.float64 if f64 else np.float32)
@@ -427,7 +477,15 @@ class Context:
         freq = (np.arange(sizeFFT) / sizeFFT - 0.5) * fe
         return freq, y
 
-    def getWaterfall(self, fe, sig, sizeFFT=1024, *, dtype=None):
+    def getWaterfall(self, fe, sig, sizeFFT=1024, *, dtype=None, iq_fmt=None, iq_scale=1.0):
+        if iq_fmt is not None:
+            if dtype is not None:
+                raise AssertionError("getWaterfall: iq_fmt is a Float32 path (dtype must be None)")
+            a, code, n = _int_iq(sig, iq_fmt, "getWaterfall")
+            nb = n // int(sizeFFT)
+            m = np.empty((int(sizeFFT), nb), np.float64, order="F")
+            self.call("tsdr_waterfall_iq", _ptr(a), code, C.c_float(iq_scale), n, int(sizeFFT), _ptr(m))
+            return np.arange(nb) * (sizeFFT / fe), (np.arange(sizeFFT) / sizeFFT - 0.5) * fe, m
         f64 = _is64(dtype)
         a, cplx = self._sig64(sig, "getWaterfall") if f64 else self._sig(sig)
         nb = a.size // int(sizeFFT)
@@ -546,6 +604,23 @@ def expand_iq(q, fmt, scale):
         return a.view(np.complex64)
     v = (a.astype(np.float32) - np.float32(off)) * np.float32(scale)
     return v.view(np.complex64)
+
+
+def _int_iq(sig, iq_fmt, what):
+    """the `iq_fmt=` keyword of the per-function API: (contiguous component array, TSDR_IQ_* code, samples); strict about the dtype"""
+    code = iq_fmt_code(iq_fmt)
+    if code == 0:
+        raise AssertionError(f"{what}: iq_fmt is for integer IQ (sc16, sc8, uc8); ComplexF32 goes in as a complex array")
+    want = {1: np.int16, 2: np.int8, 3: np.uint8}[code]
+    if not isinstance(sig, np.ndarray) or sig.dtype != want or sig.size % 2:
+        raise AssertionError(f"{what}: iq_fmt {iq_fmt!r} takes an {np.dtype(want).name} array of 2*n interleaved components")
+    a = np.ascontiguousarray(sig)
+    return a, code, a.size // 2
+
+
+# Device-pointer forms of the spectra and demodulators on a buffer of `fmt` samples (the entry points of include/tempest_hip_iq.h):
+# iq.py, re-exported here next to frames_iq_d.
+from .iq import DEMOD_IQ, demod_iq_d, expand_iq_d, spectrum_iq_d, waterfall_iq_d, welch_iq_d  # noqa: E402
 
 
 def frames_iq_d(ctx, sync, iq, fmt, scale, nEch, S, y_t, x_t, alpha, do_align, state, frames_out=None, raster_out=None, sync_idx=None,
@@ -693,7 +768,9 @@ class StagingRing:
     fmt "cf32": ComplexF32 slots; "sc16": interleaved int16 I/Q, expanded on the device to ComplexF32 * scale; "sc16raw": int16
     slots that stay int16 on the device (take_d hands out int16 pairs for frames_sc16_d with the same scale).  8-bit I/Q, two
     bytes per sample: "sc8" (int8 pairs) / "uc8" (uint8 pairs around 127.5) expanded on the device, "sc8raw" / "uc8raw" handed
-    out as stored, for frames_iq_d and autocorr_search(iq_fmt=...) with the same scale."""
+    out as stored, for frames_iq_d and autocorr_search(iq_fmt=...) with the same scale.  Raw slots are also what spectrum_iq_d,
+    welch_iq_d, waterfall_iq_d, demod_iq_d and expand_iq_d read (fmt = ring.iq_fmt): the displays and demodulators of the buffer
+    being rastered, without an expanded copy."""
     FORMATS = {"cf32": 0, "sc16": 1, "sc16raw": 2, "sc8": 3, "sc8raw": 4, "uc8": 5, "uc8raw": 6}
     SLOT_DTYPES = {"cf32": (np.float32, np.complex64), "sc16": (np.int16,), "sc16raw": (np.int16,), "sc8": (np.int8,),
                    "sc8raw": (np.int8,), "uc8": (np.uint8,), "uc8raw": (np.uint8,)}

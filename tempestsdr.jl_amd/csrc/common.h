@@ -32,6 +32,7 @@ enum Slot {
   WS_F64_A,       // Float64 per-function entry points (*_f64): transform / staging buffers of their own, so that an f64
   WS_F64_B,       // call never moves a workspace the f32 paths hold
   WS_F64_C,
+  WS_IQX,         // integer IQ expanded to ComplexF32 for the transform routes without a loader hook (tsdr_*_iq_d)
   WS_COUNT
 };
 
@@ -218,6 +219,8 @@ int pipe_sync_lanes(tsdr_ctx *ctx);    // bounded host-side wait for the pipelin
 // ctx->opt_wait_ms.  `what` names the stage for tsdr_last_error.
 int wait_stream(tsdr_ctx *ctx, hipStream_t s, const char *what);
 int wait_event(tsdr_ctx *ctx, hipEvent_t e, const char *what);
+// ring.hip: n samples of an integer format (one-sample aligned) -> ComplexF32 at `out` (8-byte aligned), the loaders' product
+int iq_expand(tsdr_ctx *ctx, const void *iq, const IqFmt &f, size_t n, float2 *out);
 void prof_begin(tsdr_ctx *ctx, const char *name);
 void prof_end(tsdr_ctx *ctx);
 
@@ -248,6 +251,17 @@ void prof_end(tsdr_ctx *ctx);
   } while (0)
 
 static inline size_t ceil_div(size_t a, size_t b) { return (a + b - 1) / b; }
+
+// The `iq, iq_fmt, scale` arguments of the *_iq_d entry points (tempest_hip.h, TSDR_IQ_*): a known format, the pointer aligned
+// to one sample of it (8 / 4 / 2 bytes) -- else TSDR_EINVAL with the argument's name, before anything is enqueued.
+#define TSDR_IQ_ARG(ctx, fn, iq, iq_fmt, scale, f)                                                                          \
+  do {                                                                                                                       \
+    if ((iq_fmt) < TSDR_IQ_CF32 || (iq_fmt) > TSDR_IQ_UC8)                                                                    \
+      return tsdr::set_err((ctx), TSDR_EINVAL, "%s: iq_fmt %d is not a TSDR_IQ_* format", fn, (int)(iq_fmt));                \
+    (f) = tsdr::IqFmt{(iq_fmt), (iq_fmt) == TSDR_IQ_CF32 ? 1.0f : (scale)};                                                  \
+    if (reinterpret_cast<uintptr_t>(iq) % tsdr::iq_bytes(f))                                                                 \
+      return tsdr::set_err((ctx), TSDR_EINVAL, "%s: iq is not aligned to one sample of its format (%d bytes)", fn, (int)tsdr::iq_bytes(f)); \
+  } while (0)
 
 // grid for a capped, grid-strided streaming kernel of 256-thread workgroups
 static inline int stream_grid(tsdr_ctx *ctx, size_t work_items) {

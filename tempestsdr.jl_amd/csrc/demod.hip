@@ -5,6 +5,7 @@
 //   abs2           GUI.jl:70 (power fed to the configuration search)
 // Each lane moves 16-byte vectors (4 complex samples = 2 x float4 in, 1 x float4 out);
 // the grid is capped and grid-strided so a launch is a few thousand workgroups.
+// The `_iq_d` forms read int16 / int8 / uint8 pairs as stored (4 or 2 B in per sample) and convert in the loader.
 #include "common.h"
 
 namespace tsdr {
@@ -95,6 +96,101 @@ __global__ __launch_bounds__(256) void k_fm(const float2 *__restrict__ iq, size_
   }
 }
 
+// ---- the same from integer IQ storage (tsdr_*_iq_d: int16, int8 or uint8 pairs as the SDR stored them, TSDR_IQ_*) -------------
+// A sample is converted by common.h's cvt_* (one product by `scale`), then goes through demod1 / the FM product exactly as a
+// ComplexF32 sample does, so the outputs are those of the expanded buffer bit for bit.  One 16-byte load is 4 sc16 samples (one
+// float4 out) or 8 eight-bit samples (two float4 out).
+template <int IQF>
+__device__ inline float2 iq_word(unsigned w, float scale) {   // w: one sample's bits, I in the low half
+  if (IQF == IQF_SC16) return cvt_sc16(make_short2((short)(w & 0xFFFFu), (short)(w >> 16)), scale);
+  return IQF == IQF_SC8 ? cvt_sc8(w & 0xFFFFu, scale) : cvt_uc8(w & 0xFFFFu, scale);
+}
+
+template <int MODE, bool TRACK_MAX, int IQF>
+__global__ __launch_bounds__(256) void k_demod_iq(const uint4 *__restrict__ iq, size_t n, float scale, float4 *__restrict__ out,
+                                                  unsigned *__restrict__ maxbits) {
+  constexpr int SPV = IQF == IQF_SC16 ? 4 : 8;   // samples per 16-byte vector
+  const size_t nv = n / SPV;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  unsigned local = 0u;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += stride) {
+    const uint4 q = iq[i];
+    const unsigned w[4] = {q.x, q.y, q.z, q.w};
+    float r[SPV];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (SPV == 4) {
+        const float2 a = iq_word<IQF>(w[k], scale);
+        r[k] = demod1<MODE>(a.x, a.y);
+      } else {
+        const float2 a = iq_word<IQF>(w[k] & 0xFFFFu, scale), b = iq_word<IQF>(w[k] >> 16, scale);
+        r[2 * k] = demod1<MODE>(a.x, a.y);
+        r[2 * k + 1] = demod1<MODE>(b.x, b.y);
+      }
+    }
+#pragma unroll
+    for (int v = 0; v < SPV / 4; ++v) out[(SPV / 4) * i + v] = make_float4(r[4 * v], r[4 * v + 1], r[4 * v + 2], r[4 * v + 3]);
+    if (TRACK_MAX) {
+#pragma unroll
+      for (int k = 0; k < SPV; ++k) local = max(local, __float_as_uint(r[k]));
+    }
+  }
+  // tail (n not a multiple of the vector)
+  if (blockIdx.x == 0 && threadIdx.x < n - nv * SPV) {
+    const size_t i = nv * SPV + threadIdx.x;
+    const float2 a = ld_iq_as<IQF>(iq_at(reinterpret_cast<const float *>(iq), i, iq_bytes_as<IQF>(IqFmt{})), 0u, IqFmt{IQK_CF32, scale});
+    const float v = demod1<MODE>(a.x, a.y);
+    reinterpret_cast<float *>(out)[i] = v;
+    if (TRACK_MAX) local = max(local, __float_as_uint(v));
+  }
+  if (TRACK_MAX) {
+    for (int off = 32; off > 0; off >>= 1) local = max(local, (unsigned)__shfl_xor((int)local, off, 64));
+    if ((threadIdx.x & 63) == 0) atomicMax(maxbits, local);
+  }
+}
+
+// one sample per lane (a 4- or 2-byte load, a 4-byte store): any sample-aligned input, any float-aligned output
+template <int MODE, bool TRACK_MAX, int IQF>
+__global__ __launch_bounds__(256) void k_demod1_iq(const void *__restrict__ iq, size_t n, float scale, float *__restrict__ out,
+                                                   unsigned *__restrict__ maxbits) {
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  unsigned local = 0u;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const float2 a = ld_iq_as<IQF>(iq_at(reinterpret_cast<const float *>(iq), i, iq_bytes_as<IQF>(IqFmt{})), 0u, IqFmt{IQK_CF32, scale});
+    const float v = demod1<MODE>(a.x, a.y);
+    out[i] = v;
+    if (TRACK_MAX) local = max(local, __float_as_uint(v));
+  }
+  if (TRACK_MAX) {
+    for (int off = 32; off > 0; off >>= 1) local = max(local, (unsigned)__shfl_xor((int)local, off, 64));
+    if ((threadIdx.x & 63) == 0) atomicMax(maxbits, local);
+  }
+}
+
+template <int IQF>
+__global__ __launch_bounds__(256) void k_fm_iq(const void *__restrict__ iq, size_t n, float scale, float *__restrict__ out) {
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  const IqFmt f{IQK_CF32, scale};
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    if (i == 0) { out[0] = 0.0f; continue; }
+    const float *p = iq_at(reinterpret_cast<const float *>(iq), i - 1, iq_bytes_as<IQF>(f));
+    const float2 s0 = ld_iq_as<IQF>(p, 0u, f), s1 = ld_iq_as<IQF>(p, 1u, f);
+    float c = s0.x, d = -s0.y;  // conj(sig[n])
+    float re = __fsub_rn(__fmul_rn(s1.x, c), __fmul_rn(s1.y, d));
+    float im = __fadd_rn(__fmul_rn(s1.x, d), __fmul_rn(s1.y, c));
+    out[i] = atan2f(im, re);
+  }
+}
+
+#define TSDR_COMMA ,
+// launch KER<..., IQF> for the integer format of f (a macro: the kernel name carries other template arguments)
+#define TSDR_LAUNCH_IQF(ctx, kname, f, KER, grid, ...)                                                                  \
+  do {                                                                                                                  \
+    if ((f).kind == IQK_SC16) TSDR_LAUNCH(ctx, kname "_sc16", (KER IQF_SC16>), grid, dim3(256), 0, __VA_ARGS__);         \
+    else if ((f).kind == IQK_SC8) TSDR_LAUNCH(ctx, kname "_sc8", (KER IQF_SC8>), grid, dim3(256), 0, __VA_ARGS__);       \
+    else TSDR_LAUNCH(ctx, kname "_uc8", (KER IQF_UC8>), grid, dim3(256), 0, __VA_ARGS__);                                \
+  } while (0)
+
 // k_demod moves 16-byte vectors on both sides; any other element-aligned pair of pointers takes k_demod1
 static inline bool vec16(const float *iq, const float *out) {
   return ((reinterpret_cast<uintptr_t>(iq) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0;
@@ -114,6 +210,31 @@ static int demod_d(tsdr_ctx *ctx, const char *kname, const float *iq, size_t n, 
                 reinterpret_cast<const float2 *>(iq), n, out, (unsigned *)nullptr);
   }
   return TSDR_OK;
+}
+
+// am_demod / abs2 / invert_am's first launch on integer IQ: 16-byte vectors where both pointers allow, one sample per lane else
+template <int MODE, bool TRACK_MAX>
+static int demod_iq_launch(tsdr_ctx *ctx, const void *iq, const IqFmt &f, size_t n, float *out, unsigned *mx) {
+  if (vec16(reinterpret_cast<const float *>(iq), out)) {
+    const dim3 grid(stream_grid(ctx, ceil_div(n, f.kind == IQK_SC16 ? 4 : 8)));
+    TSDR_LAUNCH_IQF(ctx, "demod_iq", f, k_demod_iq<MODE TSDR_COMMA TRACK_MAX TSDR_COMMA, grid, reinterpret_cast<const uint4 *>(iq), n, f.scale,
+                    reinterpret_cast<float4 *>(out), mx);
+  } else {
+    const dim3 grid(stream_grid(ctx, n));
+    TSDR_LAUNCH_IQF(ctx, "demod1_iq", f, k_demod1_iq<MODE TSDR_COMMA TRACK_MAX TSDR_COMMA, grid, iq, n, f.scale, out, mx);
+  }
+  return TSDR_OK;
+}
+
+template <int MODE>
+static int demod_iq_d(tsdr_ctx *ctx, const char *kname, const void *iq, int iq_fmt, float scale, size_t n, float *out) {
+  if (!ctx || (n && (!iq || !out))) return TSDR_EINVAL;
+  IqFmt f;
+  TSDR_IQ_ARG(ctx, kname, iq, iq_fmt, scale, f);
+  TSDR_PTR_ALIGNED(ctx, kname, out, 4);
+  if (iq_fmt == TSDR_IQ_CF32) return demod_d<MODE>(ctx, MODE == DM_ABS ? "am_demod" : "abs2", reinterpret_cast<const float *>(iq), n, out);
+  if (n == 0) return TSDR_OK;
+  return demod_iq_launch<MODE, false>(ctx, iq, f, n, out, nullptr);
 }
 
 }  // namespace tsdr
@@ -149,6 +270,38 @@ int tsdr_fm_demod_d(tsdr_ctx *ctx, const float *iq, size_t n, float *out) {
   TSDR_PTR_ALIGNED(ctx, "fm_demod", out, 4);
   if (n == 0) return TSDR_OK;
   TSDR_LAUNCH(ctx, "fm_demod", k_fm, dim3(stream_grid(ctx, n)), dim3(256), 0, reinterpret_cast<const float2 *>(iq), n, out);
+  return TSDR_OK;
+}
+
+int tsdr_am_demod_iq_d(tsdr_ctx *ctx, const void *iq, int iq_fmt, float scale, size_t n, float *out) {
+  return demod_iq_d<DM_ABS>(ctx, "am_demod_iq", iq, iq_fmt, scale, n, out);
+}
+int tsdr_abs2_iq_d(tsdr_ctx *ctx, const void *iq, int iq_fmt, float scale, size_t n, float *out) {
+  return demod_iq_d<DM_ABS2>(ctx, "abs2_iq", iq, iq_fmt, scale, n, out);
+}
+
+int tsdr_invert_am_iq_d(tsdr_ctx *ctx, const void *iq, int iq_fmt, float scale, size_t n, float *out) {
+  if (!ctx || n == 0 || !iq || !out) return TSDR_EINVAL;  // as tsdr_invert_am_d: maximum() of an empty collection throws
+  IqFmt f;
+  TSDR_IQ_ARG(ctx, "invert_am_iq", iq, iq_fmt, scale, f);
+  TSDR_PTR_ALIGNED(ctx, "invert_am_iq", out, 4);
+  if (iq_fmt == TSDR_IQ_CF32) return tsdr_invert_am_d(ctx, reinterpret_cast<const float *>(iq), n, out);
+  unsigned *mx = (unsigned *)ctx->scratch(WS_MISC, 16);
+  if (!mx) return TSDR_ENOMEM;
+  TSDR_HIP(ctx, hipMemsetAsync(mx, 0, 4, ctx->stream));
+  if (int rc = demod_iq_launch<DM_ABS, true>(ctx, iq, f, n, out, mx)) return rc;
+  TSDR_LAUNCH(ctx, "invert_am_scale", k_invert, dim3(stream_grid(ctx, n)), dim3(256), 0, out, n, (const unsigned *)mx);
+  return TSDR_OK;
+}
+
+int tsdr_fm_demod_iq_d(tsdr_ctx *ctx, const void *iq, int iq_fmt, float scale, size_t n, float *out) {
+  if (!ctx || (n && (!iq || !out))) return TSDR_EINVAL;
+  IqFmt f;
+  TSDR_IQ_ARG(ctx, "fm_demod_iq", iq, iq_fmt, scale, f);
+  TSDR_PTR_ALIGNED(ctx, "fm_demod_iq", out, 4);
+  if (iq_fmt == TSDR_IQ_CF32) return tsdr_fm_demod_d(ctx, reinterpret_cast<const float *>(iq), n, out);
+  if (n == 0) return TSDR_OK;
+  TSDR_LAUNCH_IQF(ctx, "fm_demod_iq", f, k_fm_iq<, dim3(stream_grid(ctx, n)), iq, n, f.scale, out);
   return TSDR_OK;
 }
 

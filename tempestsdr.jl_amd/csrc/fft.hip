@@ -362,7 +362,8 @@ int fft_pow2(tsdr_ctx *ctx, const float2 *in, float2 *out, int logN, size_t batc
   d.src_mode = SRC_C2C;
   d.src_n = 0;
   d.keep = keep ? keep : N;
-  if ((src_mode != SRC_C2C || epi) && (batch != 1 || logN <= 8)) return set_err(ctx, TSDR_EINVAL, "fft: fused loader / epilogue needs one multi-pass transform");
+  // (the integer IQ loaders are element-wise like SRC_C2C: any batch, as long as there is a strided pass to load through)
+  if ((src_mode != SRC_C2C || epi) && ((batch != 1 && (epi || !src_is_cplx_int(src_mode))) || logN <= 8)) return set_err(ctx, TSDR_EINVAL, "fft: fused loader / epilogue needs one multi-pass transform");
   d.src_aux = src_aux;
   d.src_w8 = src_is_int_iq(src_mode) ? (double)src_scale : 0.0;
   if (p == 1) {
@@ -556,6 +557,28 @@ int fft_any(tsdr_ctx *ctx, const float *x, int is_complex, float2 *out, size_t n
   TSDR_LAUNCH(ctx, "blu_post", k_blu_post, dim3(stream_grid(ctx, n * batch)), dim3(256), 0, (const float2 *)a, n, L, batch,
               (const float2 *)pl->chirp, inv, scale, out);
   return TSDR_OK;
+}
+
+// Forward transforms of `batch` rows of n integer IQ samples (format f, not IQK_CF32) on the route ComplexF32 input takes in
+// fft_any: the whole-row kernel's or the first pass's loader converts; the lengths without a loader hook (one-launch lengths,
+// Bluestein; 1024-point rows, which getWelch / getWaterfall never bring here) expand into WS_IQX and run fft_any itself.
+int fft_any_iq(tsdr_ctx *ctx, const void *iq, const IqFmt &f, float2 *out, size_t n, size_t batch) {
+  if (n == 0 || batch == 0) return TSDR_OK;
+  const float2 *x = reinterpret_cast<const float2 *>(iq);
+  bool expand = batch > 1 && n == 1024;
+  if (!expand && batch > 1) {
+    bool did = false;
+    int rcr = fft_rows_store(ctx, x, out, n, batch, -1, 1.0f, &did, &f);
+    if (rcr || did) return rcr;
+  }
+  if (!expand && is_pow2(n) && ilog2(n) > 8) return fft_pow2(ctx, x, out, ilog2(n), batch, -1, 1.0f, src_of_iq(f), 0, 0, nullptr, nullptr, f.scale);
+  if (!expand && !is_pow2(n) && fft_mixed_ok(n) && fft_mixed_passes(ctx, n, batch) >= 2)
+    return fft_mixed(ctx, x, out, n, batch, -1, 1.0f, src_of_iq(f), 0, 0, nullptr, nullptr, f.scale);
+  float2 *e = (float2 *)ctx->scratch(WS_IQX, n * batch * sizeof(float2));
+  if (!e) return TSDR_ENOMEM;
+  int rc = iq_expand(ctx, iq, f, n * batch, e);
+  if (rc) return rc;
+  return fft_any(ctx, reinterpret_cast<const float *>(e), 1, out, n, batch, -1);
 }
 
 }  // namespace tsdr

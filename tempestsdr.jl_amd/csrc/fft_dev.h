@@ -151,6 +151,9 @@ __device__ inline float2 conj_if(float2 v, unsigned smask) {  // smask = 0x80000
 //   SRC_IQPOW_SC16 / _SC8 / _UC8  the same from integer IQ storage (int16, int8, uint8 pairs): every sample is converted by
 //             common.h's cvt_* (the one product by `scale`, which arrives in the loader-parameter slot), then abs2_c.
 //             The two samples of g are one 8-byte (sc16) or 4-byte (8-bit) load: the base must be aligned to that.
+//   SRC_IQ_SC16 / _SC8 / _UC8  in[g] read from integer IQ storage (one sample-aligned load, converted by common.h's cvt_* with
+//             the scale in the loader-parameter slot): ComplexF32 input of getSpectrum / getWelch / getWaterfall as the SDR
+//             stored it.  Element-wise like SRC_C2C, so these also serve batched transforms (g runs over the whole batch).
 //   SRC_POWER Y[g] of the autocorrelation: `in` = Z, the length-src_n transform of a packed real
 //             sequence; Y is the packed spectrum whose inverse transform (times 1/2) is the real sequence with
 //             spectrum |X|^2 (see k_ac_power, which this loader replaces: one launch and a 2 x 8*Mc-byte round
@@ -160,8 +163,11 @@ __device__ inline float2 conj_if(float2 v, unsigned smask) {  // smask = 0x80000
 //   SRC_RE0   (x[g], 0): a real f32 sequence as complex input (getSpectrum of a real signal) -- k_r2c without its pass
 //   SRC_MULH  in[g] * aux[g], aux = ComplexF64 (double2 behind the float2 pointer): the resampler's frequency-domain filter
 //             applied while the inverse transform loads -- evaluated in f64 and rounded to ComplexF32 (Resampler.jl:51-53)
-enum { SRC_C2C = 0, SRC_REAL = 1, SRC_IQPOW = 2, SRC_POWER = 3, SRC_STUFF = 4, SRC_MULH = 5, SRC_RE0 = 6, SRC_IQPOW_SC16 = 7, SRC_IQPOW_SC8 = 8, SRC_IQPOW_UC8 = 9 };
-inline bool src_is_int_iq(int src_mode) { return src_mode >= SRC_IQPOW_SC16 && src_mode <= SRC_IQPOW_UC8; }
+enum { SRC_C2C = 0, SRC_REAL = 1, SRC_IQPOW = 2, SRC_POWER = 3, SRC_STUFF = 4, SRC_MULH = 5, SRC_RE0 = 6, SRC_IQPOW_SC16 = 7, SRC_IQPOW_SC8 = 8, SRC_IQPOW_UC8 = 9,
+       SRC_IQ_SC16 = 10, SRC_IQ_SC8 = 11, SRC_IQ_UC8 = 12 };
+inline bool src_is_int_iq(int src_mode) { return src_mode >= SRC_IQPOW_SC16 && src_mode <= SRC_IQ_UC8; }
+inline bool src_is_cplx_int(int src_mode) { return src_mode >= SRC_IQ_SC16 && src_mode <= SRC_IQ_UC8; }
+inline int src_of_iq(const IqFmt &f) { return f.kind == IQK_SC16 ? SRC_IQ_SC16 : f.kind == IQK_SC8 ? SRC_IQ_SC8 : f.kind == IQK_UC8 ? SRC_IQ_UC8 : SRC_C2C; }
 
 // inv_m8 is the loader's one f64 parameter: 8/M for SRC_POWER with M not a power of two, the f32 scale for integer IQ, else 0
 // tw_frac below (needed by the SRC_POWER loader when M = 2*Mc is not a power of two)
@@ -194,6 +200,11 @@ __device__ inline float2 fft_load(const float2 *__restrict__ in, int src_mode, u
     const float sum = P0 + P1, dif = P0 - P1;
     return make_float2(sum + dif * W.y, dif * W.x);  // (P + P') + i conj(W) (P - P')
   }
+  if (src_mode >= SRC_IQ_SC16) {
+    if (src_mode == SRC_IQ_SC16) return cvt_sc16(reinterpret_cast<const short2 *>(in)[g], (float)inv_m8);
+    const unsigned v = reinterpret_cast<const unsigned short *>(in)[g];
+    return src_mode == SRC_IQ_SC8 ? cvt_sc8(v, (float)inv_m8) : cvt_uc8(v, (float)inv_m8);
+  }
   const unsigned long long i0 = 2ull * g;
   if (i0 >= src_n) return make_float2(0.f, 0.f);  // zero padding is never read
   if (src_mode == SRC_REAL) {
@@ -215,6 +226,15 @@ __device__ inline float2 fft_load(const float2 *__restrict__ in, int src_mode, u
     else { a = cvt_uc8(v & 0xFFFFu, sc); b = cvt_uc8(v >> 16, sc); }
   }
   return make_float2(abs2_c(a.x, a.y), i0 + 1 < src_n ? abs2_c(b.x, b.y) : 0.f);
+}
+
+// one element of a whole-row kernel's input (MixDesc::rows_real): 0 ComplexF32, 1 real f32, 2 + IQK_* integer IQ (the scale in
+// MixDesc::src_w8).  `e` is the element's index from the buffer's start.
+enum { ROWS_CF32 = 0, ROWS_REAL = 1, ROWS_IQ = 1 };   // integer IQ of kind k: ROWS_IQ + k (k = IQK_SC16 ..)
+__device__ inline float2 rows_load_int(const float2 *__restrict__ in, int rows_real, size_t e, float scale) {
+  if (rows_real == ROWS_IQ + IQK_SC16) return cvt_sc16(reinterpret_cast<const short2 *>(in)[e], scale);
+  const unsigned v = reinterpret_cast<const unsigned short *>(in)[e];
+  return rows_real == ROWS_IQ + IQK_SC8 ? cvt_sc8(v, scale) : cvt_uc8(v, scale);
 }
 
 // exp(-2*pi*i*e/N) for any N: inv_n8 = 8/N in f64, 0 <= e < N.  The phase e/N is formed in f64 (relative error
@@ -314,10 +334,15 @@ int fft_mixed(tsdr_ctx *ctx, const float2 *in, float2 *out, size_t N, size_t bat
 int fft_mixed_autocorr(tsdr_ctx *ctx, const float2 *x, int src_mode, size_t src_n, size_t Mc, float2 *Zbuf, float2 *zbuf,
                        float scale, size_t keep, const FftEpilogue *epi, bool *done, float src_scale = 1.0f);
 unsigned fft_rows_welch_parts(tsdr_ctx *ctx);
-int fft_rows_welch(tsdr_ctx *ctx, const float *sig, int is_complex, size_t N, size_t nbSeg, float *part, unsigned *nparts, bool *did);
+// (iq != nullptr: the rows are integer IQ of that format, read by the row loader itself; is_complex is then 1)
+int fft_rows_welch(tsdr_ctx *ctx, const float *sig, int is_complex, size_t N, size_t nbSeg, float *part, unsigned *nparts, bool *did,
+                   const IqFmt *iq = nullptr);
 int fft_rows1024(tsdr_ctx *ctx, const float2 *in, float2 *out, size_t batch, int dir, float scale);   // spectrum.hip
-int fft_rows_store(tsdr_ctx *ctx, const float2 *in, float2 *out, size_t N, size_t batch, int dir, float scale, bool *did);
-int fft_rows_waterfall(tsdr_ctx *ctx, const float *sig, int is_complex, size_t N, size_t nbSeg, double *wf, bool *did);
+int fft_rows_store(tsdr_ctx *ctx, const float2 *in, float2 *out, size_t N, size_t batch, int dir, float scale, bool *did,
+                   const IqFmt *iq = nullptr);
+int fft_rows_waterfall(tsdr_ctx *ctx, const float *sig, int is_complex, size_t N, size_t nbSeg, double *wf, bool *did,
+                       const IqFmt *iq = nullptr);
+int fft_mixed_passes(tsdr_ctx *ctx, size_t N, size_t batch);   // passes fft_mixed takes for `batch` transforms of N points (0: not its length)
 bool fft_mixed_ok(size_t N);
 int fft_passes(size_t N);
 int ensure_tw_small(tsdr_ctx *ctx);  // builds ctx->tw_small: W_4096^e for e < 4096  // launches a length-N transform takes (0: not a 2^a 3^b 5^c length)

@@ -52,7 +52,8 @@ struct MixDesc {
   FftEpilogue epi;                   // last pass: autocorrelation epilogue when epi.out != nullptr
   // rows mode as getWelch's accumulator (GetSpectrum.jl:36-52): nothing is stored per transform; every workgroup walks
   // tiles blockIdx.x, blockIdx.x + gridDim.x, ... of `rows` segments, adds abs2 of every spectrum it forms in registers and
-  // leaves ONE partial power spectrum, acc[blockIdx.x * R + k] (natural frequency order).  rows_real: the rows are real f32.
+  // leaves ONE partial power spectrum, acc[blockIdx.x * R + k] (natural frequency order).  rows_real: the rows are real f32
+  // (1) or integer IQ (fft_dev.h:ROWS_IQ + kind, converted by the row loader with the scale in src_w8).
   float *acc;
   int rows_real;
   // ... or getWaterfall's writer (GetSpectrum.jl:54-66; three-step kernels only): Float64(abs2) of every spectrum straight from
@@ -245,7 +246,8 @@ __global__ __launch_bounds__(256, 4) void k_fft_mix(const float2 *__restrict__ i
           const unsigned w = min(w0 + 256 * u, work - 1u);
           const unsigned t = (unsigned)(((float)w + 0.5f) * invR), j = w - t * R;
           const size_t row = row0 + t;
-          if (d.rows_real) v[u] = row < d.rows ? make_float2(reinterpret_cast<const float *>(in)[row * R + j], 0.f) : make_float2(0.f, 0.f);
+          if (d.rows_real > ROWS_REAL) v[u] = row < d.rows ? rows_load_int(in, d.rows_real, row * R + j, (float)d.src_w8) : make_float2(0.f, 0.f);
+          else if (d.rows_real) v[u] = row < d.rows ? make_float2(reinterpret_cast<const float *>(in)[row * R + j], 0.f) : make_float2(0.f, 0.f);
           else v[u] = row < d.rows ? in[row * R + j] : make_float2(0.f, 0.f);
         }
 #pragma unroll
@@ -875,7 +877,9 @@ struct Mix3Geom {
 // MODE: FFT_STRIDED / FFT_LAST = passes of a multi-pass transform; the three whole-row modes below = rows of R points, T per
 // tile, walked by persistent workgroups (separate instantiations: as run-time branches of one kernel the row store's conjugations
 // and the writers' extra live values cost the accumulator 15-60 %)
-enum { M3_ACC = 10, M3_WF = 11, M3_ROWS = 12 };   // getWelch's accumulator | getWaterfall's writer | batched row transforms
+enum { M3_ACC = 10, M3_WF = 11, M3_ROWS = 12,     // getWelch's accumulator | getWaterfall's writer | batched row transforms
+       M3_ACC_IQ = 13, M3_WF_IQ = 14, M3_ROWS_IQ = 15 };   // the same three on integer IQ rows (MixDesc::rows_real = ROWS_IQ + kind): instantiations
+                                                           // of their own, so that the ComplexF32 / real ones keep their registers and occupancy
 template <int RA, int RB, int RC, int LOGT, int MODE>
 __global__ __launch_bounds__((Mix3Geom<RA, RB, RC, LOGT>::NT)) void k_fft_mix3(const float2 *__restrict__ in, float2 *__restrict__ out, MixDesc d) {
   using G = Mix3Geom<RA, RB, RC, LOGT>;
@@ -888,6 +892,8 @@ __global__ __launch_bounds__((Mix3Geom<RA, RB, RC, LOGT>::NT)) void k_fft_mix3(c
   for (int e = tid; e < R; e += NT) twR[e] = tw_q32(phase_q32((unsigned)e, d.r_hi, d.r_lo));
   const unsigned bid = blockIdx.x;
   float2 v[G::VMAX];
+  constexpr bool IQROWS = MODE >= M3_ACC_IQ;
+  constexpr int BM = IQROWS ? MODE - (M3_ACC_IQ - M3_ACC) : MODE;   // the mode without the input format
   if (MODE >= M3_ACC) {
     // ---- getWelch's accumulator (see MixDesc::acc): rows = segments, T of them per tile, nothing stored per transform.
     // A thread's step-3 slot (kk, t3) is the same for every tile, so abs2 of its RC outputs accumulates in registers.
@@ -900,14 +906,19 @@ __global__ __launch_bounds__((Mix3Geom<RA, RB, RC, LOGT>::NT)) void k_fft_mix3(c
     for (unsigned tile = bid; tile < ntiles; tile += gridDim.x) {
       const unsigned row1 = (tile << LOGT) + (unsigned)t1;
       const bool ok1 = tid < G::S1 && row1 < d.rows;
-      if (d.rows_real) {
+      if (IQROWS) {   // integer IQ rows: a wavefront still reads one row contiguously (2 or 4 bytes per lane)
+        const size_t e0 = (size_t)row1 * R + r23;
+        const float sc = (float)d.src_w8;
+#pragma unroll
+        for (int n1 = 0; n1 < RA; ++n1) v[n1] = ok1 ? rows_load_int(in, d.rows_real, e0 + n1 * R23, sc) : make_float2(0.f, 0.f);
+      } else if (d.rows_real) {
         const float *src = reinterpret_cast<const float *>(in) + (size_t)row1 * R + r23;
 #pragma unroll
         for (int n1 = 0; n1 < RA; ++n1) v[n1] = ok1 ? make_float2(src[n1 * R23], 0.f) : make_float2(0.f, 0.f);
       } else {
         const float2 *src = in + (size_t)row1 * R + r23;
 #pragma unroll
-        for (int n1 = 0; n1 < RA; ++n1) v[n1] = ok1 ? (MODE == M3_ROWS ? conj_if(src[n1 * R23], smask) : src[n1 * R23]) : make_float2(0.f, 0.f);
+        for (int n1 = 0; n1 < RA; ++n1) v[n1] = ok1 ? (BM == M3_ROWS ? conj_if(src[n1 * R23], smask) : src[n1 * R23]) : make_float2(0.f, 0.f);
       }
       __syncthreads();  // twR (first trip); the previous tile's step-3 reads (later trips)
       if (tid < G::S1) {
@@ -941,12 +952,12 @@ __global__ __launch_bounds__((Mix3Geom<RA, RB, RC, LOGT>::NT)) void k_fft_mix3(c
 #pragma unroll
         for (int n3 = 0; n3 < RC; ++n3) v[n3] = p[n3 * T + (t3 ^ G::swz(n3))];
         dft_nat<RC>(v);
-        if (MODE == M3_ROWS) {
+        if (BM == M3_ROWS) {
           float2 *row = d.rows_out + (size_t)((tile << LOGT) + (unsigned)t3) * R;
 #pragma unroll
           for (int k3 = 0; k3 < RC; ++k3)
             row[kk + RA * RB * k3] = conj_if(make_float2(v[k3].x * d.scale, v[k3].y * d.scale), smask);
-        } else if (MODE == M3_WF) {
+        } else if (BM == M3_WF) {
           double *row = d.wf + (size_t)((tile << LOGT) + (unsigned)t3) * R;
 #pragma unroll
           for (int k3 = 0; k3 < RC; ++k3) {
@@ -960,7 +971,7 @@ __global__ __launch_bounds__((Mix3Geom<RA, RB, RC, LOGT>::NT)) void k_fft_mix3(c
         }
       }
     }
-    if (MODE != M3_ACC) return;
+    if (BM != M3_ACC) return;
     // the T segments of a tile sit in T adjacent lanes: added by a fixed xor tree, lane t3 = 0 stores
 #pragma unroll
     for (int k3 = 0; k3 < RC; ++k3) {
@@ -1079,11 +1090,12 @@ __global__ __launch_bounds__((Mix3Geom<RA, RB, RC, LOGT>::NT)) void k_fft_mix3(c
 }
 
 typedef void (*mix3_fn)(const float2 *, float2 *, MixDesc);
-struct Mix3Entry { unsigned R; int logT, nt; size_t lds; mix3_fn strided, last, acc, wf, rows; };
+struct Mix3Entry { unsigned R; int logT, nt; size_t lds; mix3_fn strided, last, acc, wf, rows, acc_iq, wf_iq, rows_iq; };
 #define MIX3(RA_, RB_, RC_, LT_)                                                                                            \
   { RA_ * RB_ * RC_, LT_, Mix3Geom<RA_, RB_, RC_, LT_>::NT, Mix3Geom<RA_, RB_, RC_, LT_>::LDS,                               \
     k_fft_mix3<RA_, RB_, RC_, LT_, FFT_STRIDED>, k_fft_mix3<RA_, RB_, RC_, LT_, FFT_LAST>, k_fft_mix3<RA_, RB_, RC_, LT_, M3_ACC>, \
-    k_fft_mix3<RA_, RB_, RC_, LT_, M3_WF>, k_fft_mix3<RA_, RB_, RC_, LT_, M3_ROWS> }
+    k_fft_mix3<RA_, RB_, RC_, LT_, M3_WF>, k_fft_mix3<RA_, RB_, RC_, LT_, M3_ROWS>, k_fft_mix3<RA_, RB_, RC_, LT_, M3_ACC_IQ>,         \
+    k_fft_mix3<RA_, RB_, RC_, LT_, M3_WF_IQ>, k_fft_mix3<RA_, RB_, RC_, LT_, M3_ROWS_IQ> }
 // 8000-point tiles (64 KiB of LDS + the twiddle table): 1000 x 8 columns, 2000 x 4; 500 x 8 (4000 points)
 // (tiles half as wide -- 32-byte runs -- measured 25.8 / 22.9 us per pass against 18.5 / 19.9 at 2e6 points)
 static const Mix3Entry kMix3[] = {MIX3(10, 10, 10, 3), MIX3(20, 10, 10, 2), MIX3(5, 10, 10, 3)};
@@ -1100,7 +1112,8 @@ static const Mix3Entry *mix3_lookup(unsigned R) {
 // generic kernel: 108 against 88 us); everything else: the generic LDS-stage kernel
 #define WELCH3(RA_, RB_, RC_, LT_)                                                                                          \
   { RA_ * RB_ * RC_, LT_, Mix3Geom<RA_, RB_, RC_, LT_>::NT, Mix3Geom<RA_, RB_, RC_, LT_>::LDS, nullptr, nullptr,             \
-    k_fft_mix3<RA_, RB_, RC_, LT_, M3_ACC>, k_fft_mix3<RA_, RB_, RC_, LT_, M3_WF>, k_fft_mix3<RA_, RB_, RC_, LT_, M3_ROWS> }
+    k_fft_mix3<RA_, RB_, RC_, LT_, M3_ACC>, k_fft_mix3<RA_, RB_, RC_, LT_, M3_WF>, k_fft_mix3<RA_, RB_, RC_, LT_, M3_ROWS>,         \
+    k_fft_mix3<RA_, RB_, RC_, LT_, M3_ACC_IQ>, k_fft_mix3<RA_, RB_, RC_, LT_, M3_WF_IQ>, k_fft_mix3<RA_, RB_, RC_, LT_, M3_ROWS_IQ> }
 static const Mix3Entry kWelch3[] = {
     WELCH3(16, 16, 8, 1), WELCH3(16, 16, 16, 0), WELCH3(8, 8, 8, 3), WELCH3(8, 8, 4, 3), WELCH3(8, 4, 4, 4),   // 2048 4096 512 256 128
     WELCH3(10, 10, 10, 2), WELCH3(5, 10, 10, 2),                                                               // 1000 500 on half the pass kernels' tiles: row / waterfall modes
@@ -1118,7 +1131,7 @@ static const Mix3Entry *welch3_lookup(unsigned R, bool accumulator) {
 }
 // kernels above 64 KiB of dynamic LDS have to be opted in once
 static int mix3_prepare(tsdr_ctx *ctx, const Mix3Entry *e) {
-  for (mix3_fn f : {e->strided, e->last, e->acc, e->wf, e->rows}) {
+  for (mix3_fn f : {e->strided, e->last, e->acc, e->wf, e->rows, e->acc_iq, e->wf_iq, e->rows_iq}) {
     if (!f) continue;
     int rc = lds_opt_in(ctx, (const void *)f, e->lds);
     if (rc) return rc;
@@ -1423,6 +1436,7 @@ int fft_passes(size_t N) {
   return fft_mixed_plan(N, &pl) ? pl.p : 0;
 }
 
+int fft_mixed_passes(tsdr_ctx *ctx, size_t N, size_t batch);
 bool fft_mixed_ok(size_t N) {
   MixPlan pl;
   return fft_mixed_plan(N, &pl);
@@ -1472,6 +1486,11 @@ static bool fft_big_ok(tsdr_ctx *ctx, size_t total_points) {
   return ctx->opt_fft_big && !ctx->opt_fft_no_mix2 && total_points <= (size_t(1) << 22);
 }
 
+int fft_mixed_passes(tsdr_ctx *ctx, size_t N, size_t batch) {   // the plan fft_mixed_ex makes for this call
+  MixPlan pl;
+  return fft_mixed_plan(N, &pl, fft_big_ok(ctx, N * batch)) ? pl.p : 0;
+}
+
 // in/out may alias.  Uses WS_FFT_B when more than one pass is needed (callers must not hand WS_FFT_B buffers in).
 // src_mode/src_n: fused first-pass loader (fft_dev.h), batch == 1 and p > 1 only; keep: complex outputs per
 // transform the caller will look at (0 = all).
@@ -1489,7 +1508,8 @@ static int fft_mixed_ex(tsdr_ctx *ctx, const float2 *in, float2 *out, size_t N, 
   if (batch == 0) return TSDR_OK;
   if (N * batch >= (size_t(1) << 40)) return set_err(ctx, TSDR_EINVAL, "fft: batch too large");
   const int p = pl.p;
-  if (src_mode != SRC_C2C && (batch != 1 || p == 1)) return set_err(ctx, TSDR_EINVAL, "fft: fused loader needs one multi-pass transform");
+  // (the integer IQ loaders are element-wise like SRC_C2C: any batch)
+  if (src_mode != SRC_C2C && ((batch != 1 && !src_is_cplx_int(src_mode)) || p == 1)) return set_err(ctx, TSDR_EINVAL, "fft: fused loader needs one multi-pass transform");
   MixDesc d{};
   d.dir = dir < 0 ? -1 : 1;
   d.N = N;
@@ -1610,7 +1630,8 @@ static int fft_mixed_ex(tsdr_ctx *ctx, const float2 *in, float2 *out, size_t N, 
 // getWelch's accumulation for any 2^a 3^b 5^c segment length up to 4096 without writing a segment spectrum: *nparts partial
 // power spectra of N floats each (natural order) land in `part` (room for fft_rows_welch_parts() of them)
 unsigned fft_rows_welch_parts(tsdr_ctx *ctx) { return (unsigned)(ctx->cu_count > 0 ? ctx->cu_count : 256) * 3u; }
-int fft_rows_welch(tsdr_ctx *ctx, const float *sig, int is_complex, size_t N, size_t nbSeg, float *part, unsigned *nparts, bool *did) {
+int fft_rows_welch(tsdr_ctx *ctx, const float *sig, int is_complex, size_t N, size_t nbSeg, float *part, unsigned *nparts, bool *did,
+                   const IqFmt *iq) {
   *did = false;
   if (N < 2 || N > 4096 || nbSeg == 0 || nbSeg >= (size_t(1) << 31)) return TSDR_OK;
   // the whole segment as ONE factor of the generic LDS-stage kernel (the pass planner caps factors at 256 / 2000: its costs
@@ -1638,6 +1659,7 @@ int fft_rows_welch(tsdr_ctx *ctx, const float *sig, int is_complex, size_t N, si
   d.rows = (unsigned)nbSeg;
   d.acc = part;
   d.rows_real = is_complex ? 0 : 1;
+  if (iq && iq->kind != IQK_CF32) { d.rows_real = ROWS_IQ + iq->kind; d.src_w8 = (double)iq->scale; }
   if (const Mix3Entry *m3 = ctx->opt_fft_no_mix2 ? nullptr : welch3_lookup(d.R, true)) {
     // 500 / 1000 / 2000 (and 256 / 512 / 2048 / 4096 / 4000): the three-register-step kernel, 8 (4, 2, 1) segments per workgroup
     int rc3 = mix3_prepare(ctx, m3);
@@ -1650,7 +1672,7 @@ int fft_rows_welch(tsdr_ctx *ctx, const float *sig, int is_complex, size_t N, si
     // workgroups on a CU)
     const unsigned per_cu3 = (unsigned)std::max<size_t>(1, std::min<size_t>(3, (size_t)(160 * 1024) / m3->lds));
     const unsigned grid3 = std::min({ntiles3, (unsigned)(ctx->cu_count > 0 ? ctx->cu_count : 256) * per_cu3, fft_rows_welch_parts(ctx)});
-    TSDR_LAUNCH(ctx, "welch_rows_acc3", m3->acc, dim3(grid3), dim3(m3->nt), m3->lds, reinterpret_cast<const float2 *>(sig), (float2 *)nullptr, d);
+    TSDR_LAUNCH(ctx, "welch_rows_acc3", d.rows_real > ROWS_REAL ? m3->acc_iq : m3->acc, dim3(grid3), dim3(m3->nt), m3->lds, reinterpret_cast<const float2 *>(sig), (float2 *)nullptr, d);
     *nparts = grid3;
     *did = true;
     return TSDR_OK;
@@ -1672,7 +1694,7 @@ int fft_rows_welch(tsdr_ctx *ctx, const float *sig, int is_complex, size_t N, si
 // Batched row transforms (tsdr_fft_c2c with batch > 1) of the lengths the three-step kernels serve, in ONE launch: a row never
 // leaves the chip between its steps.  (The pass engines split a 512 .. 4096-point row into two passes whose strided one has only
 // 16-64 columns to work on: 67-197 us for 1e7 points against 35-50 us here; rows up to 256 points are one pass there already.)
-int fft_rows_store(tsdr_ctx *ctx, const float2 *in, float2 *out, size_t N, size_t batch, int dir, float scale, bool *did) {
+int fft_rows_store(tsdr_ctx *ctx, const float2 *in, float2 *out, size_t N, size_t batch, int dir, float scale, bool *did, const IqFmt *iq) {
   *did = false;
   if (N <= 256 || N > 4096 || batch < 2 || batch >= (size_t(1) << 31) || ctx->opt_fft_no_mix2) return TSDR_OK;
   const Mix3Entry *m3 = welch3_lookup((unsigned)N, false);
@@ -1686,12 +1708,13 @@ int fft_rows_store(tsdr_ctx *ctx, const float2 *in, float2 *out, size_t N, size_
   d.logT = m3->logT;
   d.rows = (unsigned)batch;
   d.rows_out = out;
+  if (iq && iq->kind != IQK_CF32) { d.rows_real = ROWS_IQ + iq->kind; d.src_w8 = (double)iq->scale; }   // (forward only: no conjugation on the way in)
   int rc = mix3_prepare(ctx, m3);
   if (rc) return rc;
   const unsigned ntiles = (unsigned)ceil_div(batch, (size_t)1 << d.logT);
   const unsigned per_cu = (unsigned)std::max<size_t>(1, std::min<size_t>(3, (size_t)(160 * 1024) / m3->lds));
   const unsigned grid = std::min(ntiles, (unsigned)(ctx->cu_count > 0 ? ctx->cu_count : 256) * per_cu);
-  TSDR_LAUNCH(ctx, "fft_rows3", m3->rows, dim3(grid), dim3(m3->nt), m3->lds, in, (float2 *)nullptr, d);
+  TSDR_LAUNCH(ctx, "fft_rows3", d.rows_real > ROWS_REAL ? m3->rows_iq : m3->rows, dim3(grid), dim3(m3->nt), m3->lds, in, (float2 *)nullptr, d);
   *did = true;
   return TSDR_OK;
 }
@@ -1699,7 +1722,7 @@ int fft_rows_store(tsdr_ctx *ctx, const float2 *in, float2 *out, size_t N, size_
 // getWaterfall for the segment lengths the three-step kernels serve (1024 has k_seg1024): segments -> Float64 power spectra,
 // fftshifted, in ONE launch -- the segment spectra never reach HBM (the route through a batched FFT + k_waterfall writes and
 // re-reads them: 109-250 us per C2 buffer at 512 .. 4096 against 40-60 us here)
-int fft_rows_waterfall(tsdr_ctx *ctx, const float *sig, int is_complex, size_t N, size_t nbSeg, double *wf, bool *did) {
+int fft_rows_waterfall(tsdr_ctx *ctx, const float *sig, int is_complex, size_t N, size_t nbSeg, double *wf, bool *did, const IqFmt *iq) {
   *did = false;
   if (N < 2 || N > 4096 || nbSeg == 0 || nbSeg >= (size_t(1) << 31) || ctx->opt_fft_no_mix2) return TSDR_OK;
   const Mix3Entry *m3 = welch3_lookup((unsigned)N, false);
@@ -1714,12 +1737,13 @@ int fft_rows_waterfall(tsdr_ctx *ctx, const float *sig, int is_complex, size_t N
   d.rows = (unsigned)nbSeg;
   d.wf = wf;
   d.rows_real = is_complex ? 0 : 1;
+  if (iq && iq->kind != IQK_CF32) { d.rows_real = ROWS_IQ + iq->kind; d.src_w8 = (double)iq->scale; }
   int rc = mix3_prepare(ctx, m3);
   if (rc) return rc;
   const unsigned ntiles = (unsigned)ceil_div(nbSeg, (size_t)1 << d.logT);
   const unsigned per_cu = (unsigned)std::max<size_t>(1, (size_t)(160 * 1024) / m3->lds);
   const unsigned grid = std::min(ntiles, (unsigned)(ctx->cu_count > 0 ? ctx->cu_count : 256) * per_cu);
-  TSDR_LAUNCH(ctx, "waterfall_rows3", m3->wf, dim3(grid), dim3(m3->nt), m3->lds, reinterpret_cast<const float2 *>(sig), (float2 *)nullptr, d);
+  TSDR_LAUNCH(ctx, "waterfall_rows3", d.rows_real > ROWS_REAL ? m3->wf_iq : m3->wf, dim3(grid), dim3(m3->nt), m3->lds, reinterpret_cast<const float2 *>(sig), (float2 *)nullptr, d);
   *did = true;
   return TSDR_OK;
 }

@@ -12,7 +12,8 @@
 // Slots may hold ComplexF32 (what recv! returns in the reference) or interleaved int16 I/Q as SDR hardware
 // delivers it (half the PCIe bytes; expanded to ComplexF32 on the device with a caller-given scale), or 8-bit I/Q --
 // int8 (HackRF, UHD sc8) or uint8 around 127.5 (RTL-SDR) -- at a quarter of the bytes.  The integer formats either
-// expand on the device or stay as they are for the loaders of tsdr_frames_iq_d / tsdr_autocorr_search_iq_d.
+// expand on the device or stay as they are for the loaders of tsdr_frames_iq_d / tsdr_autocorr_search_iq_d and of the `_iq_d`
+// spectra and demodulators.  The expansion itself is public as tsdr_iq_expand_d (any sample-aligned pointer).
 #include <chrono>
 #include <condition_variable>
 #include <cstring>
@@ -80,6 +81,36 @@ __global__ __launch_bounds__(256) void k_iq8_to_cf32(const unsigned *__restrict_
   }
 }
 
+// The same one sample per lane (a 2-byte load, an 8-byte store): for the pointers the pair kernel's dword loads and float4
+// stores cannot take -- an 8-bit buffer that starts at an odd sample of a larger one, an output at an odd ComplexF32.  The ring
+// itself only ever passes aligned slots; tsdr_iq_expand_d takes either.  Same cvt_*, same bits.
+template <bool UC>
+__global__ __launch_bounds__(256) void k_iq8_to_cf32_1(const unsigned short *__restrict__ in, size_t n, float scale, float2 *__restrict__ out) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const unsigned v = in[i];
+    out[i] = UC ? cvt_uc8(v, scale) : cvt_sc8(v, scale);
+  }
+}
+
+int iq_expand(tsdr_ctx *ctx, const void *iq, const IqFmt &f, size_t n, float2 *out) {
+  if (n == 0) return TSDR_OK;
+  if (f.kind == IQK_SC16) {
+    TSDR_LAUNCH(ctx, "iq_expand_sc16", k_sc16_to_cf32, dim3((unsigned)stream_grid(ctx, n)), dim3(256), 0, (const short2 *)iq, n, f.scale, out);
+    return TSDR_OK;
+  }
+  const bool uc = f.kind == IQK_UC8;
+  if ((reinterpret_cast<uintptr_t>(iq) & 3u) == 0 && (reinterpret_cast<uintptr_t>(out) & 15u) == 0) {
+    const dim3 grid((unsigned)stream_grid(ctx, (n + 1) / 2));
+    if (uc) TSDR_LAUNCH(ctx, "iq_expand_uc8", k_iq8_to_cf32<true>, grid, dim3(256), 0, (const unsigned *)iq, n, f.scale, (float4 *)out);
+    else TSDR_LAUNCH(ctx, "iq_expand_sc8", k_iq8_to_cf32<false>, grid, dim3(256), 0, (const unsigned *)iq, n, f.scale, (float4 *)out);
+  } else {
+    const dim3 grid((unsigned)stream_grid(ctx, n));
+    if (uc) TSDR_LAUNCH(ctx, "iq_expand_uc8_1", k_iq8_to_cf32_1<true>, grid, dim3(256), 0, (const unsigned short *)iq, n, f.scale, out);
+    else TSDR_LAUNCH(ctx, "iq_expand_sc8_1", k_iq8_to_cf32_1<false>, grid, dim3(256), 0, (const unsigned short *)iq, n, f.scale, out);
+  }
+  return TSDR_OK;
+}
+
 inline bool ring_fmt_raw(int fmt) { return fmt == 0 || fmt == 2 || fmt == 4 || fmt == 6; }   // the slot's bytes are what the consumer reads
 inline size_t ring_fmt_bytes(int fmt) { return fmt == 0 ? 8 : fmt <= 2 ? 4 : 2; }              // per sample
 
@@ -111,6 +142,19 @@ static int ring_stage(tsdr_ring *r, int slot, int d) {
 using namespace tsdr;
 
 extern "C" {
+
+int tsdr_iq_expand_d(tsdr_ctx *ctx, const void *iq, int iq_fmt, float scale, size_t n, float *cf32_out) {
+  if (!ctx || (n && (!iq || !cf32_out))) return TSDR_EINVAL;
+  IqFmt f;
+  TSDR_IQ_ARG(ctx, "iq_expand", iq, iq_fmt, scale, f);
+  TSDR_PTR_ALIGNED(ctx, "iq_expand", cf32_out, 8);
+  if (n == 0) return TSDR_OK;
+  if (iq_fmt == TSDR_IQ_CF32) {   // the samples themselves
+    if ((const void *)cf32_out != iq) TSDR_HIP(ctx, hipMemcpyAsync(cf32_out, iq, n * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    return TSDR_OK;
+  }
+  return iq_expand(ctx, iq, f, n, reinterpret_cast<float2 *>(cf32_out));
+}
 
 int tsdr_ring_create(tsdr_ctx *ctx, size_t nEch, int depth, int fmt, float scale, tsdr_ring **out) {
   if (!ctx || !out || nEch == 0 || depth < 2 || fmt < 0 || fmt > 6) return TSDR_EINVAL;

@@ -1,6 +1,7 @@
 // spectrum.hip -- GetSpectrum.jl on gfx950 (getSpectrum :21-30, getWelch :36-52,
 // getWaterfall :54-66) and the init_resampler closure of Resampler.jl:26-99.
-// All transforms go through the hand-written FFT engine (fft.hip).
+// All transforms go through the hand-written FFT engine (fft.hip).  The `_iq` entry points take integer IQ (TSDR_IQ_*) on the same
+// routes: the format is a parameter of the loaders, never of the route.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -13,6 +14,7 @@ namespace tsdr {
 int fft64_d(tsdr_ctx *ctx, double2 *data, double2 *scratch, size_t N, int dir);
 
 int fft_any(tsdr_ctx *ctx, const float *x, int is_complex, float2 *out, size_t n, size_t batch, int dir);
+int fft_any_iq(tsdr_ctx *ctx, const void *iq, const IqFmt &f, float2 *out, size_t n, size_t batch);   // fft.hip
 
 // fftshift: output j takes input (j + ceil(N/2)) mod N
 __device__ inline size_t shift_src(size_t j, size_t N) {
@@ -115,8 +117,18 @@ constexpr bool kSegPrefetch = true;
 // KIND: what leaves the registers -- 0 getWelch's accumulation, 1 getWaterfall's Float64 power spectra, 2 the spectra themselves
 // (batched 1024-point row transforms, tsdr_fft_c2c: rows[seg * 1024 + k] = scale * X[k]; inverse by conjugating on the way in
 // and out; may alias the input: a wavefront stores segment s after it has loaded s and s + 1, and segments belong to one wavefront)
+// IQF (common.h: IQF_CF32 / IQF_SC16 / IQF_SC8 / IQF_UC8, CPLX only): the segments as the SDR stored them -- int16 or 8-bit pairs,
+// `scale` then being the samples' factor (tsdr_welch_iq_d / tsdr_waterfall_iq_d).  A lane keeps the 16 raw words of the
+// prefetched segment (16 VGPRs instead of 32) and converts them when the segment's turn comes: the same f32 values the
+// expansion kernels write, then the ComplexF32 instantiation's arithmetic.  A wave-instruction still reads one contiguous run
+// (256 B of sc16, 128 B of 8-bit samples).  The ComplexF32 / real instantiations are untouched by the parameter.
+template <int IQF>
+__device__ inline float2 seg_cvt(unsigned w, float scale) {
+  if (IQF == IQF_SC16) return cvt_sc16(make_short2((short)(w & 0xFFFFu), (short)(w >> 16)), scale);
+  return IQF == IQF_SC8 ? cvt_sc8(w, scale) : cvt_uc8(w, scale);
+}
 enum { SEG_WELCH = 0, SEG_WATERFALL = 1, SEG_ROWS = 2 };
-template <int KIND, bool CPLX>
+template <int KIND, bool CPLX, int IQF = IQF_CF32>
 __global__ __launch_bounds__(64 * kSegWaves, kSegOcc) void k_seg1024(const float *__restrict__ sig, size_t nbSeg,
                                                             unsigned nwaves, float *__restrict__ part,
                                                             double *__restrict__ wf, float2 *__restrict__ rows = nullptr,
@@ -141,9 +153,21 @@ __global__ __launch_bounds__(64 * kSegWaves, kSegOcc) void k_seg1024(const float
   for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
   const int ka2 = lane & 15, l0 = lane >> 4;
   // the next segment's samples are requested before the current one is transformed: HBM latency under the arithmetic
-  float2 nx[16];
+  constexpr bool INTQ = IQF != IQF_CF32;
+  float2 nx[INTQ ? 1 : 16];
+  unsigned nraw[INTQ ? 16 : 1];
   auto fetch = [&](size_t seg) {
-    if (CPLX) {
+    if constexpr (INTQ) {
+      if (IQF == IQF_SC16) {
+        const unsigned *x = reinterpret_cast<const unsigned *>(sig) + seg * kSegN + lane;
+#pragma unroll
+        for (int m = 0; m < 16; ++m) nraw[m] = x[64 * m];
+      } else {
+        const unsigned short *x = reinterpret_cast<const unsigned short *>(sig) + seg * kSegN + lane;
+#pragma unroll
+        for (int m = 0; m < 16; ++m) nraw[m] = x[64 * m];
+      }
+    } else if constexpr (CPLX) {
       const float2 *x = reinterpret_cast<const float2 *>(sig) + seg * kSegN + lane;
 #pragma unroll
       for (int m = 0; m < 16; ++m) nx[m] = x[64 * m];
@@ -158,7 +182,7 @@ __global__ __launch_bounds__(64 * kSegWaves, kSegOcc) void k_seg1024(const float
     float2 v[16];
     if (!kSegPrefetch) fetch(seg);
 #pragma unroll
-    for (int m = 0; m < 16; ++m) v[m] = KIND == SEG_ROWS ? conj_if(nx[m], smask) : nx[m];
+    for (int m = 0; m < 16; ++m) v[m] = INTQ ? seg_cvt<IQF>(nraw[INTQ ? m : 0], scale) : KIND == SEG_ROWS ? conj_if(nx[INTQ ? 0 : m], smask) : nx[INTQ ? 0 : m];
     if (kSegPrefetch && seg + 1 < seg1) fetch(seg + 1);
     reg_dft<16>(v);
 #pragma unroll
@@ -435,8 +459,10 @@ __global__ __launch_bounds__(256) void k_resample4096(const float *__restrict__ 
   for (int m = 0; m < 16; ++m) out[tid + 256 * m] = gain * (v[m].x * inv);  // real(conj(.)) = real(.): ifft scale, then 2*up
 }
 
-static int spectrum_d(tsdr_ctx *ctx, const float *sig, int is_complex, size_t N, int lin, float *y) {
+// f: the samples' format when they are integer IQ (is_complex = 1), else IQK_CF32
+static int spectrum_d(tsdr_ctx *ctx, const float *sig, int is_complex, size_t N, int lin, float *y, const IqFmt &f = IqFmt{}) {
   if (N == 0) return TSDR_OK;
+  const bool intq = f.kind != IQK_CF32;
   // (Round 5, built and dropped: ONE launch for short signals -- N = R1 * R2, workgroup k1 forms sum_n1 x[R2 n1 + n2] W_R1^(n1 k1)
   // by direct summation and runs one R2-point LDS transform: no second pass, no grid barrier.  Correct on every size tried, and
   // 41-56 us at N = 80 000 against the two passes' 14.9: the work per THREAD is N / 1024 terms whatever R1 is (grid = R1), and
@@ -453,22 +479,25 @@ static int spectrum_d(tsdr_ctx *ctx, const float *sig, int is_complex, size_t N,
     epi.k0 = N / 2;
     epi.log_scale = !lin;
     const float2 *x = reinterpret_cast<const float2 *>(sig);
-    const int sm = is_complex ? SRC_C2C : SRC_RE0;
-    return is_pow2(N) ? fft_pow2(ctx, x, X, ilog2(N), 1, -1, 1.0f, sm, 0, 0, &epi) : fft_mixed(ctx, x, X, N, 1, -1, 1.0f, sm, 0, 0, &epi);
+    const int sm = intq ? src_of_iq(f) : is_complex ? SRC_C2C : SRC_RE0;
+    return is_pow2(N) ? fft_pow2(ctx, x, X, ilog2(N), 1, -1, 1.0f, sm, 0, 0, &epi, nullptr, f.scale)
+                      : fft_mixed(ctx, x, X, N, 1, -1, 1.0f, sm, 0, 0, &epi, nullptr, f.scale);
   }
-  int rc = fft_any(ctx, sig, is_complex, X, N, 1, -1);
+  // (one-launch and Bluestein lengths: integer samples are expanded into the workspace first, fft_any_iq)
+  int rc = intq ? fft_any_iq(ctx, sig, f, X, N, 1) : fft_any(ctx, sig, is_complex, X, N, 1, -1);
   if (rc) return rc;
   TSDR_LAUNCH(ctx, "spectrum_out", k_spec_out, dim3(stream_grid(ctx, N)), dim3(256), 0, (const float2 *)X, N, lin, y);
   return TSDR_OK;
 }
 
 static int segments_fft(tsdr_ctx *ctx, const float *sig, int is_complex, size_t len, size_t sizeFFT, float2 **X,
-                        size_t *nbSeg) {
+                        size_t *nbSeg, const IqFmt &f = IqFmt{}) {
   if (sizeFFT == 0) return set_err(ctx, TSDR_EINVAL, "sizeFFT must be positive");
   *nbSeg = len / sizeFFT;
   *X = (float2 *)ctx->scratch(WS_FFT_A, (*nbSeg ? *nbSeg : 1) * sizeFFT * sizeof(float2));
   if (!*X) return TSDR_ENOMEM;
   if (*nbSeg == 0) return TSDR_OK;
+  if (f.kind != IQK_CF32) return fft_any_iq(ctx, sig, f, *X, sizeFFT, *nbSeg);
   return fft_any(ctx, sig, is_complex, *X, sizeFFT, *nbSeg, -1);
 }
 
@@ -483,6 +512,21 @@ int tsdr_spectrum_d(tsdr_ctx *ctx, const float *sig, int is_complex, size_t N, i
   TSDR_PTR_ALIGNED(ctx, "spectrum", sig, is_complex ? 8 : 4);
   TSDR_PTR_ALIGNED(ctx, "spectrum", y, 4);
   return spectrum_d(ctx, sig, is_complex, N, lin, y);
+}
+
+int tsdr_spectrum_iq_d(tsdr_ctx *ctx, const void *iq, int iq_fmt, float scale, size_t N, int lin, float *y) {
+  if (!ctx || (N && (!iq || !y))) return TSDR_EINVAL;
+  IqFmt f;
+  TSDR_IQ_ARG(ctx, "spectrum_iq", iq, iq_fmt, scale, f);
+  TSDR_PTR_ALIGNED(ctx, "spectrum_iq", y, 4);
+  return spectrum_d(ctx, reinterpret_cast<const float *>(iq), 1, N, lin, y, f);
+}
+
+int tsdr_spectrum_iq(tsdr_ctx *ctx, const void *iq, int iq_fmt, float scale, size_t N, int lin, float *y) {
+  if (!ctx) return TSDR_EINVAL;
+  if (iq_fmt < TSDR_IQ_CF32 || iq_fmt > TSDR_IQ_UC8) return set_err(ctx, TSDR_EINVAL, "spectrum_iq: iq_fmt %d is not a TSDR_IQ_* format", iq_fmt);
+  return host_map(ctx, iq, N * iq_bytes(IqFmt{iq_fmt, scale}), y, N * 4,
+                  [&](void *i, void *o) { return tsdr_spectrum_iq_d(ctx, i, iq_fmt, scale, N, lin, (float *)o); });
 }
 
 int tsdr_spectrum(tsdr_ctx *ctx, const float *sig, int is_complex, size_t N, int lin, float *y) {
@@ -515,17 +559,23 @@ int fft_rows1024(tsdr_ctx *ctx, const float2 *in, float2 *out, size_t batch, int
 }  // namespace tsdr
 extern "C" {
 
-int tsdr_welch_d(tsdr_ctx *ctx, const float *sig, int is_complex, size_t len, size_t sizeFFT, int lin, float *y) {
-  if (!ctx || !y || (len && !sig)) return TSDR_EINVAL;
-  TSDR_PTR_ALIGNED(ctx, "welch", sig, is_complex ? 8 : 4);
-  TSDR_PTR_ALIGNED(ctx, "welch", y, 4);
+}  // extern "C"
+// getWelch on checked arguments.  f: the samples' format when they are integer IQ (is_complex = 1), else IQK_CF32; every branch
+// below is taken on (len, sizeFFT) alone, so a format takes the route ComplexF32 takes.
+static int welch_d(tsdr_ctx *ctx, const float *sig, int is_complex, const IqFmt &f, size_t len, size_t sizeFFT, int lin, float *y) {
+  const bool intq = f.kind != IQK_CF32;
   if (sizeFFT == (size_t)kSegN && len / sizeFFT > 0 && len / sizeFFT < (size_t(1) << 31)) {
     const size_t nbSeg = len / sizeFFT;
     unsigned blocks = 0;
     const unsigned nwaves = seg_waves(ctx, nbSeg, &blocks);
     float *part = (float *)ctx->scratch(WS_FFT_A, (size_t)blocks * kSegN * 4);
     if (!part) return TSDR_ENOMEM;
-    if (is_complex) {
+    if (intq) {
+      const dim3 g(blocks), b(64 * kSegWaves);
+      if (f.kind == IQK_SC16) TSDR_LAUNCH(ctx, "welch_seg1024_sc16", (k_seg1024<SEG_WELCH, true, IQF_SC16>), g, b, 0, sig, nbSeg, nwaves, part, (double *)nullptr, (float2 *)nullptr, 0u, f.scale);
+      else if (f.kind == IQK_SC8) TSDR_LAUNCH(ctx, "welch_seg1024_sc8", (k_seg1024<SEG_WELCH, true, IQF_SC8>), g, b, 0, sig, nbSeg, nwaves, part, (double *)nullptr, (float2 *)nullptr, 0u, f.scale);
+      else TSDR_LAUNCH(ctx, "welch_seg1024_uc8", (k_seg1024<SEG_WELCH, true, IQF_UC8>), g, b, 0, sig, nbSeg, nwaves, part, (double *)nullptr, (float2 *)nullptr, 0u, f.scale);
+    } else if (is_complex) {
       TSDR_LAUNCH(ctx, "welch_seg1024", (k_seg1024<SEG_WELCH, true>), dim3(blocks), dim3(64 * kSegWaves), 0, sig, nbSeg, nwaves, part,
                   (double *)nullptr);
     } else {
@@ -543,7 +593,7 @@ int tsdr_welch_d(tsdr_ctx *ctx, const float *sig, int is_complex, size_t len, si
     if (!part) return TSDR_ENOMEM;
     unsigned nparts = 0;
     bool did = false;
-    int rc = fft_rows_welch(ctx, sig, is_complex, sizeFFT, len / sizeFFT, part, &nparts, &did);
+    int rc = fft_rows_welch(ctx, sig, is_complex, sizeFFT, len / sizeFFT, part, &nparts, &did, intq ? &f : nullptr);
     if (rc) return rc;
     if (did) {
       TSDR_LAUNCH(ctx, "welch_sum", k_welch_sum, dim3((unsigned)ceil_div(sizeFFT, 16)), dim3(256), 0, (const float *)part, sizeFFT, nparts, lin, y);
@@ -552,7 +602,7 @@ int tsdr_welch_d(tsdr_ctx *ctx, const float *sig, int is_complex, size_t len, si
   }
   float2 *X;
   size_t nbSeg;
-  int rc = segments_fft(ctx, sig, is_complex, len, sizeFFT, &X, &nbSeg);
+  int rc = segments_fft(ctx, sig, is_complex, len, sizeFFT, &X, &nbSeg, f);
   if (rc) return rc;
   if (nbSeg == 0) {  // sum over no segments: zeros (-Inf dB), as the reference's zero-initialised accumulator gives
     TSDR_LAUNCH(ctx, "welch_sum", k_welch_sum, dim3((unsigned)ceil_div(sizeFFT, 16)), dim3(256), 0, (const float *)nullptr, sizeFFT, 0u, lin,
@@ -570,21 +620,50 @@ int tsdr_welch_d(tsdr_ctx *ctx, const float *sig, int is_complex, size_t len, si
   return TSDR_OK;
 }
 
+extern "C" {
+
+int tsdr_welch_d(tsdr_ctx *ctx, const float *sig, int is_complex, size_t len, size_t sizeFFT, int lin, float *y) {
+  if (!ctx || !y || (len && !sig)) return TSDR_EINVAL;
+  TSDR_PTR_ALIGNED(ctx, "welch", sig, is_complex ? 8 : 4);
+  TSDR_PTR_ALIGNED(ctx, "welch", y, 4);
+  return welch_d(ctx, sig, is_complex, IqFmt{}, len, sizeFFT, lin, y);
+}
+
+int tsdr_welch_iq_d(tsdr_ctx *ctx, const void *iq, int iq_fmt, float scale, size_t len, size_t sizeFFT, int lin, float *y) {
+  if (!ctx || !y || (len && !iq)) return TSDR_EINVAL;
+  IqFmt f;
+  TSDR_IQ_ARG(ctx, "welch_iq", iq, iq_fmt, scale, f);
+  TSDR_PTR_ALIGNED(ctx, "welch_iq", y, 4);
+  return welch_d(ctx, reinterpret_cast<const float *>(iq), 1, f, len, sizeFFT, lin, y);
+}
+
+int tsdr_welch_iq(tsdr_ctx *ctx, const void *iq, int iq_fmt, float scale, size_t len, size_t sizeFFT, int lin, float *y) {
+  if (!ctx) return TSDR_EINVAL;
+  if (iq_fmt < TSDR_IQ_CF32 || iq_fmt > TSDR_IQ_UC8) return set_err(ctx, TSDR_EINVAL, "welch_iq: iq_fmt %d is not a TSDR_IQ_* format", iq_fmt);
+  return host_map(ctx, iq, len * iq_bytes(IqFmt{iq_fmt, scale}), y, sizeFFT * 4, [&](void *i, void *o) {   // the raw bytes go up, not expanded ones
+    return tsdr_welch_iq_d(ctx, i, iq_fmt, scale, len, sizeFFT, lin, (float *)o);
+  });
+}
+
 int tsdr_welch(tsdr_ctx *ctx, const float *sig, int is_complex, size_t len, size_t sizeFFT, int lin, float *y) {
   return host_map(ctx, sig, len * (is_complex ? 8 : 4), y, sizeFFT * 4, [&](void *i, void *o) {
     return tsdr_welch_d(ctx, (const float *)i, is_complex, len, sizeFFT, lin, (float *)o);
   });
 }
 
-int tsdr_waterfall_d(tsdr_ctx *ctx, const float *sig, int is_complex, size_t len, size_t sizeFFT, double *sMatrix) {
-  if (!ctx || (len && !sig)) return TSDR_EINVAL;
-  TSDR_PTR_ALIGNED(ctx, "waterfall", sig, is_complex ? 8 : 4);
-  TSDR_PTR_ALIGNED(ctx, "waterfall", sMatrix, 8);
+}  // extern "C"
+static int waterfall_d(tsdr_ctx *ctx, const float *sig, int is_complex, const IqFmt &f, size_t len, size_t sizeFFT, double *sMatrix) {
+  const bool intq = f.kind != IQK_CF32;
   if (sizeFFT == (size_t)kSegN && len / sizeFFT > 0 && len / sizeFFT < (size_t(1) << 31) && sMatrix) {
     const size_t nbSeg = len / sizeFFT;
     unsigned blocks = 0;
     const unsigned nwaves = seg_waves(ctx, nbSeg, &blocks);
-    if (is_complex) {
+    if (intq) {
+      const dim3 g(blocks), b(64 * kSegWaves);
+      if (f.kind == IQK_SC16) TSDR_LAUNCH(ctx, "waterfall_seg1024_sc16", (k_seg1024<SEG_WATERFALL, true, IQF_SC16>), g, b, 0, sig, nbSeg, nwaves, (float *)nullptr, sMatrix, (float2 *)nullptr, 0u, f.scale);
+      else if (f.kind == IQK_SC8) TSDR_LAUNCH(ctx, "waterfall_seg1024_sc8", (k_seg1024<SEG_WATERFALL, true, IQF_SC8>), g, b, 0, sig, nbSeg, nwaves, (float *)nullptr, sMatrix, (float2 *)nullptr, 0u, f.scale);
+      else TSDR_LAUNCH(ctx, "waterfall_seg1024_uc8", (k_seg1024<SEG_WATERFALL, true, IQF_UC8>), g, b, 0, sig, nbSeg, nwaves, (float *)nullptr, sMatrix, (float2 *)nullptr, 0u, f.scale);
+    } else if (is_complex) {
       TSDR_LAUNCH(ctx, "waterfall_seg1024", (k_seg1024<SEG_WATERFALL, true>), dim3(blocks), dim3(64 * kSegWaves), 0, sig, nbSeg, nwaves,
                   (float *)nullptr, sMatrix);
     } else {
@@ -595,18 +674,44 @@ int tsdr_waterfall_d(tsdr_ctx *ctx, const float *sig, int is_complex, size_t len
   }
   if (sizeFFT && sMatrix && len / sizeFFT > 0) {
     bool did = false;
-    int rcw = fft_rows_waterfall(ctx, sig, is_complex, sizeFFT, len / sizeFFT, sMatrix, &did);
+    int rcw = fft_rows_waterfall(ctx, sig, is_complex, sizeFFT, len / sizeFFT, sMatrix, &did, intq ? &f : nullptr);
     if (rcw || did) return rcw;
   }
   float2 *X;
   size_t nbSeg;
-  int rc = segments_fft(ctx, sig, is_complex, len, sizeFFT, &X, &nbSeg);
+  int rc = segments_fft(ctx, sig, is_complex, len, sizeFFT, &X, &nbSeg, f);
   if (rc) return rc;
   if (nbSeg == 0) return TSDR_OK;
   if (!sMatrix) return TSDR_EINVAL;
   TSDR_LAUNCH(ctx, "waterfall_out", k_waterfall, dim3(stream_grid(ctx, sizeFFT * nbSeg)), dim3(256), 0, (const float2 *)X,
               sizeFFT, nbSeg, sMatrix);
   return TSDR_OK;
+}
+
+extern "C" {
+
+int tsdr_waterfall_d(tsdr_ctx *ctx, const float *sig, int is_complex, size_t len, size_t sizeFFT, double *sMatrix) {
+  if (!ctx || (len && !sig)) return TSDR_EINVAL;
+  TSDR_PTR_ALIGNED(ctx, "waterfall", sig, is_complex ? 8 : 4);
+  TSDR_PTR_ALIGNED(ctx, "waterfall", sMatrix, 8);
+  return waterfall_d(ctx, sig, is_complex, IqFmt{}, len, sizeFFT, sMatrix);
+}
+
+int tsdr_waterfall_iq_d(tsdr_ctx *ctx, const void *iq, int iq_fmt, float scale, size_t len, size_t sizeFFT, double *sMatrix) {
+  if (!ctx || (len && !iq)) return TSDR_EINVAL;
+  IqFmt f;
+  TSDR_IQ_ARG(ctx, "waterfall_iq", iq, iq_fmt, scale, f);
+  TSDR_PTR_ALIGNED(ctx, "waterfall_iq", sMatrix, 8);
+  return waterfall_d(ctx, reinterpret_cast<const float *>(iq), 1, f, len, sizeFFT, sMatrix);
+}
+
+int tsdr_waterfall_iq(tsdr_ctx *ctx, const void *iq, int iq_fmt, float scale, size_t len, size_t sizeFFT, double *sMatrix) {
+  if (!ctx || sizeFFT == 0) return TSDR_EINVAL;
+  if (iq_fmt < TSDR_IQ_CF32 || iq_fmt > TSDR_IQ_UC8) return set_err(ctx, TSDR_EINVAL, "waterfall_iq: iq_fmt %d is not a TSDR_IQ_* format", iq_fmt);
+  const size_t nb = len / sizeFFT;
+  return host_map(ctx, iq, len * iq_bytes(IqFmt{iq_fmt, scale}), sMatrix, nb * sizeFFT * 8, [&](void *i, void *o) {
+    return tsdr_waterfall_iq_d(ctx, i, iq_fmt, scale, len, sizeFFT, (double *)o);
+  });
 }
 
 int tsdr_waterfall(tsdr_ctx *ctx, const float *sig, int is_complex, size_t len, size_t sizeFFT, double *sMatrix) {

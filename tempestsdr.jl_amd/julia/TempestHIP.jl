@@ -18,6 +18,7 @@ export amDemod, invert_amDemod, fmDemod
 export sig_to_image, downgradeImage, naiveResampler, init_resampler
 export calculate_autocorrelation, zoom_autocorr
 export getSpectrum, getWelch, getWaterfall
+export hip_welch_d, hip_waterfall_d                                   # getWelch / getWaterfall of a device buffer in any IQ format (a raw ring slot)
 export SyncXY, vsync
 export hip_frames!, hip_frames_submit!, hip_frames_submit_sc16!, hip_frames_submit_iq!, hip_frames_flush, hip_synchronize   # fused GUI.jl:163-178 loop body (optional fast path; pipelined form)
 export hip_extract_configuration, sync_guard_stats, sync_guard_auto, wait_stats   # fused GUI.jl:67-81 search; counters of the FAST loop's sync guard
@@ -285,6 +286,34 @@ function getWaterfall(fe, sig::AbstractVector{<:Union{Float64,ComplexF64}}; size
     return ((0:nbSeg-1) * (sizeFFT / fe), collect(((0:sizeFFT-1) ./ sizeFFT .- 0.5) .* fe), m)
 end
 getWaterfall(sig; sizeFFT = 1024) = getWaterfall(1, sig; sizeFFT = sizeFFT)
+# Integer IQ as the SDR stored it -- Complex{Int16} (a `:short` capture, DatBinaryFiles.jl:44-66; sc16), Complex{Int8} (sc8),
+# Complex{UInt8} (uc8, around 127.5) --: the `_iq` entry points upload the raw 4 or 2 bytes per sample and convert in the
+# transform's loader, every component (Float32(code) - offset) * scale.  Float32 out, the axes as above.
+const IntIQ = Union{Complex{Int16},Complex{Int8},Complex{UInt8}}
+_iq_code(::AbstractVector{Complex{Int16}}) = Cint(1)    # TSDR_IQ_SC16
+_iq_code(::AbstractVector{Complex{Int8}}) = Cint(2)     # TSDR_IQ_SC8
+_iq_code(::AbstractVector{Complex{UInt8}}) = Cint(3)    # TSDR_IQ_UC8
+function getSpectrum(fs, sig::AbstractVector{<:IntIQ}; N = nothing, scale::Float32 = 1f0)
+    isnothing(N) && (N = length(sig))
+    N <= length(sig) || throw(BoundsError(sig, N))
+    a = _dense(sig); y = Vector{Float32}(undef, N); c = ctx()
+    check(c, ccall((:tsdr_spectrum_iq, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cfloat, Csize_t, Cint, Ptr{Float32}),
+                   c.h, a, _iq_code(a), scale, N, 0, y), "getSpectrum")
+    return (collect(((0:N-1) ./ N .- 0.5) * fs), y)
+end
+function getWelch(fe, sig::AbstractVector{<:IntIQ}; sizeFFT = 1024, scale::Float32 = 1f0)
+    a = _dense(sig); y = Vector{Float32}(undef, sizeFFT); c = ctx()
+    check(c, ccall((:tsdr_welch_iq, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cfloat, Csize_t, Csize_t, Cint, Ptr{Float32}),
+                   c.h, a, _iq_code(a), scale, length(a), sizeFFT, 0, y), "getWelch")
+    return (collect(((0:sizeFFT-1) ./ sizeFFT .- 0.5) * fe), y)
+end
+function getWaterfall(fe, sig::AbstractVector{<:IntIQ}; sizeFFT = 1024, scale::Float32 = 1f0)
+    a = _dense(sig); nbSeg = length(a) ÷ sizeFFT
+    m = Matrix{Float64}(undef, sizeFFT, nbSeg); c = ctx()
+    check(c, ccall((:tsdr_waterfall_iq, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cfloat, Csize_t, Csize_t, Ptr{Float64}),
+                   c.h, a, _iq_code(a), scale, length(a), sizeFFT, m), "getWaterfall")
+    return ((0:nbSeg-1) * (sizeFFT / fe), collect(((0:sizeFFT-1) ./ sizeFFT .- 0.5) .* fe), m)
+end
 
 # ---- FrameSynchronisation.jl ------------------------------------------------------------------
 mutable struct SyncXY{T}                                                      # FrameSynchronisation.jl:25-48
@@ -663,5 +692,9 @@ function take_d!(r::HipRing; timeout_ms = -1)
     check(r.c, ccall((:tsdr_ring_take_d, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Ptr{Cfloat}}), r.h, timeout_ms, d), "take_d!")
     return d[]
 end
+
+# Integer IQ through the device-pointer `_iq_d` entry points (include/tempest_hip_iq.h): amDemod / invert_amDemod of
+# Complex{Int16} / Complex{Int8} / Complex{UInt8} vectors, hip_welch_d / hip_waterfall_d of a raw ring slot
+include("TempestHIP_iq.jl")
 
 end # module
