@@ -264,13 +264,14 @@ static inline size_t ceil_div(size_t a, size_t b) { return (a + b - 1) / b; }
   } while (0)
 
 // grid for a capped, grid-strided streaming kernel of 256-thread workgroups
-static inline int stream_grid(tsdr_ctx *ctx, size_t work_items) {
+static inline int stream_blocks(int cu_count, size_t work_items) {
   size_t blocks = ceil_div(work_items, 256);
-  size_t cap = (size_t)(ctx->cu_count > 0 ? ctx->cu_count : 256) * 8;
+  size_t cap = (size_t)(cu_count > 0 ? cu_count : 256) * 8;
   if (blocks > cap) blocks = cap;
   if (blocks < 1) blocks = 1;
   return (int)blocks;
 }
+static inline int stream_grid(tsdr_ctx *ctx, size_t work_items) { return stream_blocks(ctx->cu_count, work_items); }
 
 // Host-pointer wrapper: stage `in` to the device, run the device-pointer core on the
 // context's stream, copy `out` back, synchronise.  run(din, dout) returns a tsdr_status.

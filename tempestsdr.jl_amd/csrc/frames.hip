@@ -15,18 +15,16 @@
 
 #include "common.h"
 #include "guard.h"
+#include "image_plan.h"
 #include "sync_layout.h"
 
 struct tsdr_sync;
 
 namespace tsdr {
-// proj != nullptr: the kernel may also leave the projection partial sums of every (h_out, w_out) image there
-// (TSDR_FAST in-walk sums) and clear the two argmax keys of every frame in `keys`; *got then describes the sums
-// (ncp == 0: nothing was produced, keys untouched).  plan_only: no launch, only report in *got what a real call would
-// produce.
-int raster_and_down_d(tsdr_ctx *ctx, const float *in, int cplx, IqFmt iqf, int precision, size_t in_stride, size_t S, int y_t, int x_t,
-                      int h_out, int w_out, int frames, float *raster, size_t raster_stride, float *down, size_t down_stride,
-                      float *proj, ProjLayout *got, bool plan_only, unsigned long long *keys);
+// resample.hip: launch what image_plan.h:plan_images decided.  Where the plan says so (plan.sums.ncp != 0) the image kernel
+// also leaves the projection partial sums of every image in `proj` and clears the two argmax keys of every frame in `keys`.
+int launch_images(tsdr_ctx *ctx, const ImagePlan &plan, const float *in, float *raster, size_t raster_stride, float *down,
+                  size_t down_stride, float *proj, unsigned long long *keys);
 int sync_scan_d(tsdr_sync *s, const float *img, size_t img_stride, int frames, unsigned long long *keys, float *proj,
                 const ProjLayout *have, uint2 *top2);
 void sync_beta_blocks(const tsdr_sync *s, int *nbx, int *nby);
@@ -84,8 +82,8 @@ struct FrameJob {
   // job_prepare:
   int precision = TSDR_FAST;                       // the context's, or TSDR_EXACT for this buffer alone
   GuardPlan gp;
-  float *proj = nullptr;                           // projection partial sums
-  ProjLayout plan{}, sums{};                       // their layout as planned (sizes the workspace) / as job_images left them
+  float *proj = nullptr;                           // projection partial sums (layout: images.sums)
+  ImagePlan images;                                // what job_images will launch, and what that produces
 };
 
 // the adaptive route's decision (common.h): evaluated over windows of at least kGuardAutoWindow frames, from the per-call
@@ -191,32 +189,39 @@ static int guard_plan(FrameJob &j) {
 // The loop body for one buffer of F frames, as four steps over a FrameJob.  Every arrangement of the loop is a schedule over
 // them -- which stream a step goes to, which events sit between two steps: one call per buffer on the context's stream
 // (frames_scan, then tsdr_frames_combine_d) and the pipeline's equal lanes and image lane + tail lane (frames_submit).
-//   job_prepare  everything that may allocate or grow a workspace: guard plan (and with it the buffer's precision), the image
-//                call's plan, the sync workspace.  Launches nothing.
-//   job_images   stage R: raster (optional) + 600x800 image of every frame in one launch; in TSDR_FAST mode the same kernel
-//                also forms the images' projection partial sums on the fly, so no kernel re-reads the images for them
+//   job_prepare  every decision, and everything that may allocate or grow a workspace: guard plan (and with it the buffer's
+//                precision), the image plan (image_plan.h: which kernels, grids, parameters -- a geometry that cannot be
+//                planned is refused here, before anything is enqueued), the raster workspace of its per-frame fallback,
+//                the sync workspace sized by the plan's projection sums.  Launches nothing.
+//   job_images   stage R: launches the image plan -- raster (optional) + 600x800 image of every frame in one launch; in
+//                TSDR_FAST mode the same kernel also forms the images' projection partial sums on the fly, so no kernel
+//                re-reads the images for them
 //   job_stats    stage S: vsync statistics (two argmax keys per frame), in TSDR_FAST mode followed by the sync guard
 //   job_combine  shift + IIR; `done`: an event recorded behind it, or nullptr
 constexpr size_t kNpx = (size_t)TSDR_RENDER_H * TSDR_RENDER_W;
 
-static int job_images_call(FrameJob &j, float *proj, ProjLayout *got, bool plan_only, unsigned long long *keys) {
-  return raster_and_down_d(j.ctx, j.iq, 1, j.fmt, j.precision, j.S, j.S, j.y_t, j.x_t, TSDR_RENDER_H, TSDR_RENDER_W, j.F, j.raster_out,
-                           (size_t)j.y_t * j.x_t, j.img, kNpx, proj, got, plan_only, keys);
-}
-
 static int job_prepare(FrameJob &j) {
   int rc = guard_plan(j);
-  if (rc || !j.do_align) return rc;
-  rc = job_images_call(j, nullptr, &j.plan, /*plan_only=*/true, nullptr);
   if (rc) return rc;
-  return sync_workspace(j.sync, j.F, j.slot, j.nslots, j.plan.ncp ? &j.plan : nullptr, &j.proj, nullptr);
+  ImageReq r;
+  r.iqf = j.fmt; r.precision = j.precision; r.S = r.in_stride = j.S; r.y_t = j.y_t; r.x_t = j.x_t;
+  r.h_out = TSDR_RENDER_H; r.w_out = TSDR_RENDER_W; r.frames = j.F;
+  r.raster = j.raster_out != nullptr; r.images = true; r.sums = j.do_align != 0;   // (the sums serve the vsync statistics only)
+  r.raster_addr = reinterpret_cast<uintptr_t>(j.raster_out); r.raster_stride = (size_t)j.y_t * j.x_t;
+  j.images = plan_images(plan_opts(j.ctx), r);
+  if (j.images.status) return set_err(j.ctx, j.images.status, "%s", j.images.err);
+  if (j.images.fallback && !j.ctx->scratch(WS_RASTER, j.images.ws_raster)) return TSDR_ENOMEM;
+  if (!j.do_align) return TSDR_OK;
+  return sync_workspace(j.sync, j.F, j.slot, j.nslots, j.images.sums.ncp ? &j.images.sums : nullptr, &j.proj, nullptr);
 }
 
-static int job_images(FrameJob &j) { return job_images_call(j, j.proj, &j.sums, /*plan_only=*/false, j.keys); }
+static int job_images(FrameJob &j) {
+  return launch_images(j.ctx, j.images, j.iq, j.raster_out, (size_t)j.y_t * j.x_t, j.img, kNpx, j.proj, j.keys);
+}
 
 static int job_stats(FrameJob &j) {
   if (!j.do_align) return TSDR_OK;
-  int rc = sync_scan_d(j.sync, j.img, kNpx, j.F, j.keys, j.proj, j.sums.ncp ? &j.sums : nullptr, j.gp.on ? j.gp.top2 : nullptr);
+  int rc = sync_scan_d(j.sync, j.img, kNpx, j.F, j.keys, j.proj, j.images.sums.ncp ? &j.images.sums : nullptr, j.gp.on ? j.gp.top2 : nullptr);
   if (rc || !j.gp.on) return rc;
   return sync_guard_d(j.sync, j.iq, j.fmt, j.S, j.y_t, j.x_t, j.F, j.img, kNpx, j.keys, j.proj, j.gp.g, nullptr, false);
 }

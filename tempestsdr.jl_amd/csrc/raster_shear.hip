@@ -18,24 +18,13 @@
 // lane from f64, one 64-bit add per pixel), |IQ| by v_sqrt_f32 (abs_iq<false>), pixel = (1-t) a + t b as two f32 FMAs:
 // within ~2 ulp of TSDR_EXACT (tests assert 6e-7).  SHEAR = false is the same kernel with o(p) = 0: the unsheared control
 // of the A/B (identical instruction stream, misaligned stores).
+#include <cassert>
+
 #include "common.h"
 #include "down_fused.h"
+#include "image_plan.h"
 
 namespace tsdr {
-
-struct ShearParams {
-  unsigned S;
-  int y_t, x_t, frames;
-  int W, rows;            // staged samples per row, staged rows (64 + 31 with SHEAR)
-  int tiles_p, tiles_l;
-  int c;                  // y_t mod 32
-  unsigned out_mis;       // (out address / 4) mod 32
-  double sf;
-  long long XA, XB;       // 32.32 increments per column: sf (1 + delta x_t) for delta = -c and 32 - c
-  float inv_W;
-};
-
-constexpr int kShearTP = 128;   // pixel columns per workgroup: 4 wavefronts x 32
 
 // dword store with a wave-uniform 64-bit base in SGPRs and a 32-bit per-lane byte offset
 __device__ __forceinline__ void store_saddr_f(float *base_uniform, unsigned lane_off_bytes, float v) {
@@ -165,38 +154,16 @@ __global__ __launch_bounds__(256) void k_raster_shear(const float2 *__restrict__
   }
 }
 
-// plan_only: nothing is launched, *did says whether a real call would
-int raster_shear_d(tsdr_ctx *ctx, const float *in, size_t in_stride, size_t S, int y_t, int x_t, int frames, float *out,
-                   size_t out_stride, bool shear, bool *did, bool plan_only) {
-  *did = false;
-  const double sf = (double)S / ((double)y_t * (double)x_t);
-  if (sf > 0.5 || y_t < 64 || x_t < kShearTP || frames <= 0 || frames > 65535) return TSDR_OK;
-  if ((reinterpret_cast<uintptr_t>(out) & 3u) != 0) return TSDR_OK;
-  ShearParams q{};
-  q.S = (unsigned)S; q.y_t = y_t; q.x_t = x_t; q.frames = frames; q.sf = sf;
-  q.c = y_t & 31;
-  if (q.c == 0 && (out_stride & 31) == 0 && (reinterpret_cast<uintptr_t>(out) & 127u) == 0) shear = false;   // already on the grid
-  q.rows = shear ? 95 : 64;
-  q.W = (int)((double)(kShearTP - 1) * sf) + 5;
-  q.inv_W = 1.0f / (float)q.W;
-  q.tiles_p = (int)ceil_div((size_t)x_t, (size_t)kShearTP);
-  q.tiles_l = (int)ceil_div((size_t)y_t + (shear ? 31 : 0), 64);
-  q.out_mis = (unsigned)((reinterpret_cast<uintptr_t>(out) >> 2) & 31u);
-  const double xt = (double)x_t;
-  q.XA = (long long)floor(sf * (1.0 - (shear ? (double)q.c * xt : 0.0)) * 4294967296.0);
-  q.XB = (long long)floor(sf * (1.0 + (double)(32 - q.c) * xt) * 4294967296.0);
-  const size_t lds = ((size_t)q.rows * (size_t)(q.W | 1) + (size_t)q.rows) * 4;
-  if (lds > 60 * 1024 || q.tiles_l > 65535) return TSDR_OK;
-  if (plan_only) { *did = true; return TSDR_OK; }
-  const dim3 grid((unsigned)q.tiles_p, (unsigned)q.tiles_l, (unsigned)frames);
-  if (shear) {
-    TSDR_LAUNCH(ctx, "raster_sheared_iq", k_raster_shear<true>, grid, dim3(256), lds, reinterpret_cast<const float2 *>(in), in_stride, q, out,
-                out_stride);
+// the launch of an IK_SHEAR step (image_plan.h:plan_shear decided it; resample.hip:launch_images calls this)
+int launch_shear(tsdr_ctx *ctx, const ImageStep &s, const float *in, size_t in_stride, float *out, size_t out_stride) {
+  const dim3 grid(s.grid[0], s.grid[1], s.grid[2]);
+  // (the shear was planned from the raster pointer's address bits: a plan is launched with the pointer it was made for)
+  assert((unsigned)((reinterpret_cast<uintptr_t>(out) >> 2) & 31u) == s.sq.out_mis);
+  if (s.shear) {
+    TSDR_LAUNCH(ctx, s.name, k_raster_shear<true>, grid, dim3(s.block), s.lds, reinterpret_cast<const float2 *>(in), in_stride, s.sq, out, out_stride);
   } else {
-    TSDR_LAUNCH(ctx, "raster_unsheared_iq", k_raster_shear<false>, grid, dim3(256), lds, reinterpret_cast<const float2 *>(in), in_stride, q,
-                out, out_stride);
+    TSDR_LAUNCH(ctx, s.name, k_raster_shear<false>, grid, dim3(s.block), s.lds, reinterpret_cast<const float2 *>(in), in_stride, s.sq, out, out_stride);
   }
-  *did = true;
   return TSDR_OK;
 }
 

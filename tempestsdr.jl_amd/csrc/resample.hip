@@ -24,10 +24,12 @@
 // vertically adjacent tiles share 128-byte lines, which then merge in that XCD's L2 instead of reaching HBM as
 // two partial writes.
 #include <algorithm>
+#include <cassert>
 #include <cstdlib>
 
 #include "common.h"
 #include "down_fused.h"
+#include "image_plan.h"
 #include "sync_layout.h"
 
 namespace tsdr {
@@ -39,22 +41,6 @@ __device__ inline float load_sample(const float *__restrict__ src, unsigned k, c
     return abs_iq<EXACT>(z.x, z.y);
   }
   return src[k];
-}
-
-// ---- FAST coordinate: exact rational, incremental ---------------------------------------------------------
-struct FastAx {
-  unsigned S, P, D;       // D = 2P
-  unsigned qstep, rstep;  // 2S = qstep*D + rstep : advance of (k, r) per output sample
-  double invDd;           // 1/D
-};
-
-static inline FastAx fast_axis(size_t S, size_t P) {
-  FastAx f;
-  f.S = (unsigned)S; f.P = (unsigned)P; f.D = (unsigned)(2 * P);
-  f.qstep = (unsigned)((2 * S) / (2 * P));
-  f.rstep = (unsigned)((2 * S) % (2 * P));
-  f.invDd = 1.0 / (double)(2 * P);
-  return f;
 }
 
 // floor division of num = (2*flat+1)*S - P by D (num may be negative for the first pixels of a frame)
@@ -73,28 +59,6 @@ __device__ inline void fast_pos(const FastAx &f, unsigned flat, int &k, unsigned
 // DOWN: tiles overlap by one line / one pixel (63 x TP-1 owned); the tile's raster values are kept in LDS and
 // the 600x800 output pixels whose top-left tap falls in the owned area are produced by the same workgroup.
 // ------------------------------------------------------------------------------------------------------------
-struct TileParams {
-  unsigned S;
-  int y_t, x_t;
-  int TP, W;            // pixels per tile, LDS row capacity (samples)
-  int tiles_l, tiles_p; // tiles per frame
-  int frames;
-  int own_l, own_p;     // owned lines / pixels per tile (64/TP, or 63/TP-1 with DOWN)
-  int h_out, w_out;     // DOWN only
-  int NR, NC;           // DOWN: candidate output rows / columns per tile
-  int lpl_log;          // log2(lanes per line) of the staging loop
-  int cs;               // k_raster_fast: consecutive samples per staging lane (<= 4)
-  int xcd_group;        // neighbouring pixel strips dealt to the same XCD
-  int xcd_group_log;    // log2(xcd_group)
-  float inv_tiles_p;    // 1/tiles_p (unit -> frame, strip without an integer division)
-  RsAxis ax, ay, axx;   // sig->raster, raster lines->rows, raster pixels->columns (host-computed)
-  double inv_sfy, inv_sfx;
-  float *proj;          // k_raster_fast<DOWN>: projection partial sums of the (h_out, w_out) images, or null
-  size_t proj_stride;   // floats per frame: colpart[tiles_l][w_out] | rowpart[tiles_p][h_out]
-  unsigned long long *keys;  // with proj: two vsync argmax keys per frame, cleared here for k_beta's atomicMax
-  IqFmt iqf;            // CPLX input: ComplexF32 or int16 pairs (common.h)
-};
-
 template <bool CPLX, bool DOWN>
 __global__ __launch_bounds__(256) void k_raster_tile(const float *__restrict__ in, size_t in_stride, TileParams q,
                                                      float *__restrict__ out, size_t out_stride,
@@ -320,31 +284,6 @@ __global__ __launch_bounds__(256) void k_raster_tile(const float *__restrict__ i
 // The inverse maps (raster line -> output row, raster pixel -> output column) need source/destination ratios
 // strictly above 1 on both axes, so that a line (pixel) is the top-left tap of at most one row (column).
 // ------------------------------------------------------------------------------------------------------------
-struct FastInc {
-  unsigned qL, rL;    // advance of (k, r) per raster line       : 2*x_t*S       = qL*D + rL
-  unsigned qTL, rTL;  // per tile row (own_l lines)
-  unsigned qTP, rTP;  // per tile column (own_p pixels)
-  int k00;            // position of pixel 0 of a frame: floor((S - P)/D) ...
-  unsigned r00;       // ... and remainder
-  float invD;
-};
-
-static inline FastInc fast_inc(size_t S, size_t P, int x_t, int own_l, int own_p) {
-  FastInc n;
-  const long long D = 2 * (long long)P;
-  auto split = [&](long long delta, unsigned &q, unsigned &r) { q = (unsigned)(delta / D); r = (unsigned)(delta % D); };
-  split(2LL * x_t * (long long)S, n.qL, n.rL);
-  split(2LL * x_t * (long long)S * own_l, n.qTL, n.rTL);
-  split(2LL * (long long)S * own_p, n.qTP, n.rTP);
-  const long long num = (long long)S - (long long)P;
-  long long q = num / D;
-  if (num % D < 0) --q;
-  n.k00 = (int)q;
-  n.r00 = (unsigned)(num - q * D);
-  n.invD = 1.0f / (float)D;
-  return n;
-}
-
 // (k, r) += m*(q, rr) with r kept in [0, D); needs r + m*rr < 2^32 (host-checked) and D < 2^24
 __device__ inline void adv32(int &k, unsigned &r, unsigned m, unsigned q, unsigned rr, unsigned D, float invD) {
   const unsigned t = r + m * rr;
@@ -1102,8 +1041,6 @@ __global__ __launch_bounds__(256) void k_raster_direct(const float *__restrict__
 }
 
 // grid = (tiles, frames)
-// (256 threads per 64 x 64-pixel tile: 512 threads measured 55.9 us, 512 threads on 64 x 128 58.5 us, 128 threads 70.4 us, against 54.3 us)
-constexpr int kDownNT = 256;
 template <bool CPLX, int MODE, int SUMS = DS_NONE, int LD = 4, int IQF = (MODE == DM_EXACT ? IQF_RT : IQF_CF32)>
 __global__ __launch_bounds__(kDownNT) void k_down_fused(const float *__restrict__ in, size_t in_stride, DownParams q,
                                                     float *__restrict__ out, size_t out_stride, size_t lds_main) {
@@ -1167,269 +1104,122 @@ __global__ __launch_bounds__(256) void k_naive(const float *__restrict__ in, siz
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// host-side tiling plans
+// launch_images: the walk over an ImagePlan (image_plan.h).  The planner decided everything; here each step's template
+// arguments select the instantiation, the pointers are filled in and the kernel is launched.  One helper per kernel family.
 // ------------------------------------------------------------------------------------------------------------
-static int check_geom(tsdr_ctx *ctx, size_t S, int y_t, int x_t) {
-  if (y_t <= 0 || x_t <= 0) return set_err(ctx, TSDR_EINVAL, "y_t and x_t must be positive");
-  const size_t P = (size_t)y_t * (size_t)x_t;
-  if (S >= (size_t(1) << 31) || P >= (size_t(1) << 31)) return set_err(ctx, TSDR_EINVAL, "frame larger than 2^31 samples/pixels");
-  if (S != P && S < 2) return set_err(ctx, TSDR_EINVAL, "imresize needs at least 2 input samples");
-  return TSDR_OK;
-}
+struct StepPtrs {   // what a step reads and writes: one frame's worth in the per-frame fallback, else the whole buffer's
+  const float *in; size_t in_stride;
+  float *out; size_t out_stride;      // raster (or the image buffer, ImageStep::to_images)
+  float *down; size_t down_stride;
+};
+#define TILE_ARGS p.in, p.in_stride, q, p.out, p.out_stride, p.down, p.down_stride
+#define FAST_ARGS p.in, p.in_stride, q, s.fa, s.fi, p.out, p.out_stride, p.down, p.down_stride
+#define DOWN_ARGS p.in, p.in_stride, q, p.down, p.down_stride, s.lds_main
+#define STEP_GRID dim3(s.grid[0], s.grid[1], s.grid[2])
 
-template <bool CPLX, bool DOWN>
-static int launch_tile(tsdr_ctx *ctx, const char *name, const float *in, size_t in_stride, const TileParams &q,
-                       size_t lds, float *out, size_t out_stride, float *down, size_t down_stride) {
-  const size_t units = (size_t)q.frames * q.tiles_p;
-  const size_t G = (size_t)q.xcd_group;
-  const size_t upx = ceil_div(units, 8 * G) * G;  // units per XCD slot
-  if (upx > 65535 || (size_t)q.tiles_l > 65535 || units >= (size_t(1) << 20))
-    return set_err(ctx, TSDR_EINVAL, "raster: too many tiles for one launch (split the buffer)");
-  TSDR_LAUNCH(ctx, name, (k_raster_tile<CPLX, DOWN>), dim3(8, (unsigned)q.tiles_l, (unsigned)upx), dim3(256), lds, in,
-              in_stride, q, out, out_stride, down, down_stride);
-  return TSDR_OK;
-}
-
-// sig_to_image for `frames` consecutive frames (raster `out`, may be null when only `down` is wanted and the
-// tile kernel applies) and, when `down` != null, the (h_out,w_out) image of each frame from the same launch.
-// Returns TSDR_OK and sets *did_down when the down image was produced here.
-// proj / got / plan_only: see raster_and_down_d.
-int raster_frames_d(tsdr_ctx *ctx, const float *in, int cplx, IqFmt iqf, int precision, size_t in_stride, size_t S, int y_t, int x_t,
-                    int frames, float *out, size_t out_stride, float *down = nullptr, size_t down_stride = 0, int h_out = 0,
-                    int w_out = 0, bool *did_down = nullptr, float *proj = nullptr, ProjLayout *got = nullptr,
-                    bool plan_only = false, unsigned long long *keys = nullptr) {
-  if (did_down) *did_down = false;
-  int rc = check_geom(ctx, S, y_t, x_t);
-  if (rc) return rc;
-  if (frames <= 0) return TSDR_OK;
-  const size_t P = (size_t)y_t * x_t;
-  const double sf = (double)S / (double)P;
-  // TSDR_FAST exists for the steady-state frame loop (tsdr_frames*), whose input is IQ; the per-function entry
-  // points (real input) always run the oracle's operation sequence
-  const bool exact = precision == TSDR_EXACT || !cplx || P >= (size_t(1) << 30);
-  // fused downgrade in the raster launch: only when both axes shrink (<= 66 x 130 candidates per tile)
-  const bool want_down = down && !(y_t == h_out && x_t == w_out) && y_t >= 2 * 64 && x_t >= 2 * 128 &&
-                         (double)y_t / h_out >= 1.0 && (double)x_t / w_out >= 1.0;
-  TileParams q{};
-  q.S = (unsigned)S; q.y_t = y_t; q.x_t = x_t; q.frames = frames;
-  if (cplx) q.iqf = iqf;
-  // pairs of strips.  Measured on C2 -- round 2 (16-byte sample records, 3 workgroups per CU): G=1 0.138 ms, G=4 0.132 ms, G=41 0.146 ms;
-  // round 4 (f32 samples, 4 per CU), the launch alone on two boxes: G=1 115.3, G=2 110.9 / 114.9, G=4 113.7 / 117.4, G=8 118.4, G=16 120.5 us
-  // (C3: no difference; C5: G=2 1 % behind G=4).  The EXACT tile kernel (two workgroups per CU fewer) keeps four: 146.5 against 148.3 us
-  q.xcd_group_log = exact ? 2 : 1;
-  q.xcd_group = 1 << q.xcd_group_log;
-  q.ax = rs_axis(S, (size_t)y_t * x_t);
-  if (h_out > 0 && w_out > 0) {
-    q.ay = rs_axis((size_t)y_t, (size_t)h_out); q.axx = rs_axis((size_t)x_t, (size_t)w_out);
-    q.inv_sfy = 1.0 / q.ay.sf; q.inv_sfx = 1.0 / q.axx.sf;
-  }
-  bool tiled = false;
-  // EXACT with the downgrade fused in: 64-pixel tiles, because the raster tile kept in LDS then costs 16.6 KiB
-  // instead of 33 KiB, which doubles the resident workgroups per CU.  FAST keeps no raster tile (k_raster_fast).
-  int tp_max = (want_down && exact) ? 64 : 128;
-  // staged-sample budget per tile: EXACT 4 B/sample (<= 48 KiB), FAST 16 B/sample (<= 47 samples per line = 47 KiB;
-  // only down-sampling ratios get near it, up-sampling tiles stage ~11-18 samples per line)
-  // (FAST with plain f32 samples -- REC4, k_raster_fast: the f32 walk with the in-walk downgrade -- 4 B/sample: <= 94 samples
-  // per line, i.e. C3's 1.15 samples per raster pixel get 64-pixel tiles, and with them the in-walk projection sums)
-  const bool rec4_ok = !exact && want_down && ctx->opt_raster_rec4 != 0 && 2 * P < (size_t(1) << 32) && y_t > h_out && x_t > w_out;
-  auto pick_tp = [&](long w_cap) {
-    tiled = false;
-    for (int TP = tp_max; TP >= 4; TP >>= 1) {
-      const long W = (long)((double)(TP - 1) * sf) + 4;
-      if (W <= w_cap) { tiled = true; q.TP = TP; q.W = (int)W; break; }
-    }
-  };
-  pick_tp(exact ? 191 : rec4_ok ? 94 : 47);
-  if (rec4_ok && tiled && q.W > 47) {
-    // the wider budget only holds for the plan REC4 serves: the in-walk downgrade (TP >= 32)
-    if (q.TP < 32) pick_tp(47);
-  }
-  if (tiled && !exact) {  // FAST: k_raster_fast
-    // the in-walk downgrade needs ratios strictly above 1 (a line / pixel is then the top-left tap of at most one
-    // output row / column); otherwise the raster is produced here and the caller downgrades separately
-    const bool dn = want_down && q.TP >= 32 && y_t > h_out && x_t > w_out;
-    // wavefronts stacked vertically per workgroup (see k_raster_fast).  Measured on C2: 1 -> 0.121 ms, 2 -> 0.118 ms,
-    // 4 (1024 threads, 77 KiB LDS) -> 0.131 ms; again with f32 samples (REC4, 12 KiB): 130 / 124 / 138 us for the launch
-    // round 6: four lines per lane (k_raster_fast4) wherever the f32-sample walk with the in-walk image writes rasters from
-    // 128-pixel tiles -- C2's route: a quarter fewer write requests for the same bytes (option "raster_v4", default on)
-    const bool v4 = ctx->opt_raster_v4 > 0 && rec4_ok && dn && q.TP == 128 && out != nullptr && 2 * P < (size_t(1) << 24) && y_t >= 512 &&
-                    x_t <= 127 * 128 && ctx->opt_raster_split == 0 &&
-                    (q.iqf.kind == IQK_CF32 || q.iqf.kind == IQK_SC16);   // (k_raster_fast4 exists for those two formats only)
-    int VW = v4 ? 1 : y_t >= 2 * 64 ? 2 : 1;
-    const int lstep = dn ? 63 : 64, NL = v4 ? 256 : lstep * (VW - 1) + 64;
-    q.own_l = v4 ? 255 : lstep * VW;
-    q.own_p = dn ? q.TP - 1 : q.TP;
-    q.tiles_l = dn ? (y_t - 2) / q.own_l + 1 : (int)ceil_div((size_t)y_t, (size_t)q.own_l);
-    q.tiles_p = dn ? (x_t - 2) / q.own_p + 1 : (int)ceil_div((size_t)x_t, (size_t)q.TP);
-    q.inv_tiles_p = 1.0f / (float)q.tiles_p;
-    if (!dn && !out) return TSDR_OK;  // nothing to do here; caller falls back to k_down_fused
-    // f32 walk and 32-bit position advance: D = 2P < 2^24 and few enough tiles that the advances stay below 2^32
-    const bool w32 = 2 * P < (size_t(1) << 24) && q.tiles_l <= 128 && q.tiles_p <= 128;
-    // Staged samples as plain f32 (REC4, k_raster_fast) instead of 16-byte records wherever the f32 walk with the in-walk
-    // downgrade runs: C3's tiles (39 samples x 127 lines) were 79 KB of records, ONE 512-thread workgroup per CU with nothing
-    // to cover its staging (357 -> 244 us per buffer with 20 KB of samples); C2's 42 KB -> 14 KB is worth 4-6 % of its
-    // store-bound launch.  One more sample per line: a pixel reads (k, k + 1).
-    const bool rec4 = rec4_ok && dn;
-    if (!rec4 && q.W > 47) return set_err(ctx, TSDR_EINVAL, "raster: tile plan needs the f32-sample walk");  // (pick_tp above rules it out)
-    if (rec4) q.W += 1;
-    // staging lanes per line: the power of two that wastes the fewest lane slots with <= 4 samples per lane
-    int best = -1; long best_slots = 1L << 60;
-    for (int lg = 2; lg <= 6; ++lg) {
-      const long lpl = 1L << lg, cs = (long)ceil_div((size_t)q.W, (size_t)lpl);
-      if (cs > 4) continue;
-      const long slots = cs * lpl;
-      if (slots < best_slots || (slots == best_slots && lg > best)) { best = lg; best_slots = slots; }
-    }
-    q.lpl_log = best;
-    q.cs = (int)ceil_div((size_t)q.W, (size_t)1 << best);
-    size_t lds = rec4 ? (((size_t)NL * (size_t)(q.W | 1) * 4 + 15) & ~(size_t)15) + 16 : (size_t)NL * (size_t)(q.W | 1) * 16 + 16;
-    const int v4pw = ctx->opt_raster_v4 == 32 ? 32 : 16;
-    if (v4) lds += (size_t)(128 / v4pw) * NL * 4;   // the wavefronts' image-row scratch (down_event4)
-    // the images' projection partial sums come out of the same walk when the caller has room for them
-    // (with narrower tiles -- down-sampling ratios such as C3's -- the per-workgroup part of the sums is spread over
-    // four times as many workgroups and costs more than the separate pass over the images: 0.382 vs 0.354 ms)
-    const bool pj = dn && q.TP >= 64 && got != nullptr && ((proj != nullptr && keys != nullptr) || plan_only);
-    if (dn) {
-      q.h_out = h_out; q.w_out = w_out;
-      lds += (size_t)(NL + q.TP + 1) * 12 + 16;
-      if (pj) {
-        lds = std::max(lds, (size_t)2 * 256 * VW * 4);  // the sums reuse the sample region after the walk
-        got->ncp = q.tiles_l;
-        got->nrp = q.tiles_p;
-        q.proj = proj;
-        q.keys = keys;
-        q.proj_stride = proj_floats(h_out, w_out, *got);
-      }
-    }
-    if (plan_only) { if (did_down) *did_down = dn; return TSDR_OK; }
-    const FastAx fa = fast_axis(S, P);
-    const FastInc fi = fast_inc(S, P, x_t, q.own_l, q.own_p);
-    const size_t units = (size_t)q.frames * q.tiles_p;
-    const size_t G = (size_t)q.xcd_group;
-    const size_t upx = ceil_div(units, 8 * G) * G;  // units per XCD slot
-    if (upx > 65535 || (size_t)q.tiles_l > 65535 || units >= (size_t(1) << 20))
-      return set_err(ctx, TSDR_EINVAL, "raster: too many tiles for one launch (split the buffer)");
-    const dim3 grid(8, (unsigned)q.tiles_l, (unsigned)upx);
-    if (v4) {
-      if (v4pw == 32) {
-        if (q.iqf.sc16()) {
-          TSDR_LAUNCH(ctx, "raster_down_iq", (k_raster_fast4<IQF_SC16, 32>), grid, dim3(256), lds, in, in_stride, q, fa, fi, out, out_stride, down, down_stride);
-        } else {
-          TSDR_LAUNCH(ctx, "raster_down_iq", (k_raster_fast4<IQF_CF32, 32>), grid, dim3(256), lds, in, in_stride, q, fa, fi, out, out_stride, down, down_stride);
-        }
-      } else if (q.iqf.sc16()) {
-        TSDR_LAUNCH(ctx, "raster_down_iq", (k_raster_fast4<IQF_SC16, 16>), grid, dim3(512), lds, in, in_stride, q, fa, fi, out, out_stride, down, down_stride);
-      } else {
-        TSDR_LAUNCH(ctx, "raster_down_iq", (k_raster_fast4<IQF_CF32, 16>), grid, dim3(512), lds, in, in_stride, q, fa, fi, out, out_stride, down, down_stride);
-      }
-      if (did_down) *did_down = true;
-      return TSDR_OK;
-    }
-#define FASTK2(C, W32, D, PW, VWK, NAME)                                                                              \
-  do {                                                                                                                \
-    if (out) {                                                                                                        \
-      TSDR_LAUNCH(ctx, NAME, (k_raster_fast<C, W32, D, PW, true, VWK>), grid, dim3(256 * VWK), lds, in, in_stride, q, fa,   \
-                  fi, out, out_stride, down, down_stride);                                                             \
-    } else {                                                                                                          \
-      TSDR_LAUNCH(ctx, "down_walk_iq", (k_raster_fast<C, W32, D, PW, false, VWK>), grid,                                \
-                  dim3(256 * VWK), lds, in, in_stride, q, fa, fi, out, out_stride, down, down_stride);                   \
-    }                                                                                                                 \
-  } while (0)
-#define FASTK2RF(W32, PW, VWK, IQFK)                                                                                  \
-  do {                                                                                                                \
-    if (out) {                                                                                                        \
-      TSDR_LAUNCH(ctx, "raster_down_iq", (k_raster_fast<true, W32, true, PW, true, VWK, true, IQFK>), grid, dim3(256 * VWK), lds, in,   \
-                  in_stride, q, fa, fi, out, out_stride, down, down_stride);                                          \
-    } else {                                                                                                          \
-      TSDR_LAUNCH(ctx, "down_walk_iq", (k_raster_fast<true, W32, true, PW, false, VWK, true, IQFK>), grid, dim3(256 * VWK), lds, in,    \
-                  in_stride, q, fa, fi, out, out_stride, down, down_stride);                                          \
-    }                                                                                                                 \
-  } while (0)
-#define FASTK2R(W32, PW, VWK)                                                                                         \
-  do {                                                                                                                \
-    if (q.iqf.kind == IQK_SC16) FASTK2RF(W32, PW, VWK, IQF_SC16);                                                     \
-    else if (q.iqf.kind == IQK_SC8) FASTK2RF(W32, PW, VWK, IQF_SC8);                                                  \
-    else if (q.iqf.kind == IQK_UC8) FASTK2RF(W32, PW, VWK, IQF_UC8);                                                  \
-    else FASTK2RF(W32, PW, VWK, IQF_CF32);                                                                            \
-  } while (0)
-#define FASTK1(C, W32, D, PW, NAME)                                                                                   \
-  do {                                                                                                                \
-    if (rec4 && D && (PW == 8 || PW == 16 || PW == 32)) { if (VW == 2) FASTK2R(W32, PW, 2); else FASTK2R(W32, PW, 1); } \
-    else if (VW == 2) FASTK2(C, W32, D, PW, 2, NAME);                                                                 \
-    else FASTK2(C, W32, D, PW, 1, NAME);                                                                              \
-  } while (0)
-#define FASTK(C, W32, D, NAME)                                                                                        \
-  do {                                                                                                                \
-    switch (q.TP) {                                                                                                   \
-      case 128: FASTK1(C, W32, D, 32, NAME); break;                                                                   \
-      case 64: FASTK1(C, W32, D, 16, NAME); break;                                                                    \
-      case 32: FASTK1(C, W32, D, 8, NAME); break;                                                                     \
-      case 16: FASTK1(C, W32, D, 4, NAME); break;                                                                     \
-      case 8: FASTK1(C, W32, D, 2, NAME); break;                                                                      \
-      default: FASTK1(C, W32, D, 1, NAME); break;                                                                     \
-    }                                                                                                                 \
-  } while (0)
-    if (dn) {
-      if (w32) { FASTK(true, true, true, "raster_down_iq"); } else { FASTK(true, false, true, "raster_down_iq"); }
-      if (did_down) *did_down = true;
-    } else {
-      if (w32) { FASTK(true, true, false, "raster_iq"); } else { FASTK(true, false, false, "raster_iq"); }
-    }
-#undef FASTK1
-#undef FASTK2
-#undef FASTK2R
-#undef FASTK2RF
-#undef FASTK
-    return TSDR_OK;
-  }
-  if (plan_only) return TSDR_OK;  // only k_raster_fast produces projection sums
-  if (tiled) {
-    const bool dn = want_down && q.TP >= 32;
-    q.own_l = dn ? 63 : 64;
-    q.own_p = dn ? q.TP - 1 : q.TP;
-    q.tiles_l = dn ? (y_t - 2) / 63 + 1 : (int)ceil_div((size_t)y_t, 64);
-    q.tiles_p = dn ? (x_t - 2) / q.own_p + 1 : (int)ceil_div((size_t)x_t, (size_t)q.TP);
-    q.inv_tiles_p = 1.0f / (float)q.tiles_p;
-    // staging lanes per line: a lane issues its loads four at a time, lpl samples apart -- the power of two that wastes the
-    // fewest of the ceil(W / 4 lpl) * 4 lpl load slots of a line (see plan_down)
-    int best = 0; long best_slots = 1L << 60;
-    for (int lg = 2; lg <= 6; ++lg) {
-      const long chunk = 4L << lg, slots = (long)ceil_div((size_t)q.W, (size_t)chunk) * chunk;
-      if (slots < best_slots || (slots == best_slots && lg > best)) { best = lg; best_slots = slots; }
-    }
-    q.lpl_log = best;
-    size_t lds = (size_t)64 * (size_t)(q.W | 1) * 4 + 16 + 64 * 4 + 16;
-    if (dn) {
-      q.h_out = h_out; q.w_out = w_out;
-      q.NR = (int)ceil(64.0 / ((double)y_t / h_out)) + 5;
-      q.NC = (int)ceil((double)q.TP / ((double)x_t / w_out)) + 5;
-      if (q.NR > 128 || q.NC > 192) return set_err(ctx, TSDR_EINVAL, "raster: candidate table overflow");
-      lds += (size_t)q.TP * 65 * 4 + (size_t)(q.NR + q.NC + 4) * 4 + (size_t)(q.NR + q.NC) * 8;
-    }
-#define TILE(C, D, NAME) launch_tile<C, D>(ctx, NAME, in, in_stride, q, lds, out, out_stride, down, down_stride)
-    if (dn) {
-      if (cplx) rc = TILE(true, true, "raster_down_iq_exact");
-      else rc = TILE(false, true, "raster_down_f32_exact");
-      if (!rc && did_down) *did_down = true;
-    } else {
-      if (!out) return TSDR_OK;  // nothing to do here; caller falls back to k_down_fused
-      if (cplx) rc = TILE(true, false, "raster_iq_exact");
-      else rc = TILE(false, false, "raster_f32_exact");
-    }
-#undef TILE
-    return rc;
-  }
-  if (!out) return TSDR_OK;
-  dim3 grid((unsigned)stream_grid(ctx, ceil_div((size_t)y_t, 64) * 64 * (size_t)x_t), (unsigned)frames);
-  if (cplx) {
-    TSDR_LAUNCH(ctx, "raster_direct_iq", (k_raster_direct<true>), grid, dim3(256), 0, in, in_stride, (unsigned)S, y_t, x_t,
-                out, out_stride, iqf);
+template <bool W32, bool D, int PW, bool OUT, int VW>
+static int fast_k(tsdr_ctx *ctx, const ImageStep &s, const TileParams &q, const StepPtrs &p) {
+  const dim3 grid = STEP_GRID, block(s.block);
+  if (!s.rec4) {
+    TSDR_LAUNCH(ctx, s.name, (k_raster_fast<true, W32, D, PW, OUT, VW>), grid, block, s.lds, FAST_ARGS);
+  } else if (s.iqf == IQF_SC16) {
+    TSDR_LAUNCH(ctx, s.name, (k_raster_fast<true, W32, true, PW, OUT, VW, true, IQF_SC16>), grid, block, s.lds, FAST_ARGS);
+  } else if (s.iqf == IQF_SC8) {
+    TSDR_LAUNCH(ctx, s.name, (k_raster_fast<true, W32, true, PW, OUT, VW, true, IQF_SC8>), grid, block, s.lds, FAST_ARGS);
+  } else if (s.iqf == IQF_UC8) {
+    TSDR_LAUNCH(ctx, s.name, (k_raster_fast<true, W32, true, PW, OUT, VW, true, IQF_UC8>), grid, block, s.lds, FAST_ARGS);
   } else {
-    TSDR_LAUNCH(ctx, "raster_direct_f32", (k_raster_direct<false>), grid, dim3(256), 0, in, in_stride, (unsigned)S, y_t, x_t,
-                out, out_stride, IqFmt{});
+    TSDR_LAUNCH(ctx, s.name, (k_raster_fast<true, W32, true, PW, OUT, VW, true, IQF_CF32>), grid, block, s.lds, FAST_ARGS);
   }
   return TSDR_OK;
 }
+template <bool W32, bool D, int PW>
+static int fast_pw(tsdr_ctx *ctx, const ImageStep &s, const TileParams &q, const StepPtrs &p) {
+  if (s.out) return s.vw == 2 ? fast_k<W32, D, PW, true, 2>(ctx, s, q, p) : fast_k<W32, D, PW, true, 1>(ctx, s, q, p);
+  return s.vw == 2 ? fast_k<W32, D, PW, false, 2>(ctx, s, q, p) : fast_k<W32, D, PW, false, 1>(ctx, s, q, p);
+}
+template <bool W32, bool D>
+static int fast_wd(tsdr_ctx *ctx, const ImageStep &s, const TileParams &q, const StepPtrs &p) {
+  switch (s.pw) {
+    case 32: return fast_pw<W32, D, 32>(ctx, s, q, p);
+    case 16: return fast_pw<W32, D, 16>(ctx, s, q, p);
+    case 8: return fast_pw<W32, D, 8>(ctx, s, q, p);
+    case 4: return fast_pw<W32, D, 4>(ctx, s, q, p);
+    case 2: return fast_pw<W32, D, 2>(ctx, s, q, p);
+    default: return fast_pw<W32, D, 1>(ctx, s, q, p);
+  }
+}
+static int launch_fast(tsdr_ctx *ctx, const ImageStep &s, const TileParams &q, const StepPtrs &p) {
+  if (s.f32w) return s.down ? fast_wd<true, true>(ctx, s, q, p) : fast_wd<true, false>(ctx, s, q, p);
+  return s.down ? fast_wd<false, true>(ctx, s, q, p) : fast_wd<false, false>(ctx, s, q, p);
+}
+
+// (k_raster_fast4 exists for ComplexF32 and sc16 only: the planner chooses it for no other format)
+static int launch_fast4(tsdr_ctx *ctx, const ImageStep &s, const TileParams &q, const StepPtrs &p) {
+  const dim3 grid = STEP_GRID, block(s.block);
+  if (s.pw == 32) {
+    if (s.iqf == IQF_SC16) { TSDR_LAUNCH(ctx, s.name, (k_raster_fast4<IQF_SC16, 32>), grid, block, s.lds, FAST_ARGS); }
+    else { TSDR_LAUNCH(ctx, s.name, (k_raster_fast4<IQF_CF32, 32>), grid, block, s.lds, FAST_ARGS); }
+  } else if (s.iqf == IQF_SC16) {
+    TSDR_LAUNCH(ctx, s.name, (k_raster_fast4<IQF_SC16, 16>), grid, block, s.lds, FAST_ARGS);
+  } else {
+    TSDR_LAUNCH(ctx, s.name, (k_raster_fast4<IQF_CF32, 16>), grid, block, s.lds, FAST_ARGS);
+  }
+  return TSDR_OK;
+}
+
+static int launch_tile(tsdr_ctx *ctx, const ImageStep &s, const TileParams &q, const StepPtrs &p) {
+  const dim3 grid = STEP_GRID, block(s.block);
+  if (s.cplx) {
+    if (s.down) { TSDR_LAUNCH(ctx, s.name, (k_raster_tile<true, true>), grid, block, s.lds, TILE_ARGS); }
+    else { TSDR_LAUNCH(ctx, s.name, (k_raster_tile<true, false>), grid, block, s.lds, TILE_ARGS); }
+  } else if (s.down) {
+    TSDR_LAUNCH(ctx, s.name, (k_raster_tile<false, true>), grid, block, s.lds, TILE_ARGS);
+  } else {
+    TSDR_LAUNCH(ctx, s.name, (k_raster_tile<false, false>), grid, block, s.lds, TILE_ARGS);
+  }
+  return TSDR_OK;
+}
+
+static int launch_direct(tsdr_ctx *ctx, const ImageStep &s, const StepPtrs &p) {
+  const dim3 grid = STEP_GRID, block(s.block);
+  if (s.cplx) {
+    TSDR_LAUNCH(ctx, s.name, (k_raster_direct<true>), grid, block, 0, p.in, p.in_stride, s.q.S, s.q.y_t, s.q.x_t, p.out, p.out_stride, s.q.iqf);
+  } else {
+    TSDR_LAUNCH(ctx, s.name, (k_raster_direct<false>), grid, block, 0, p.in, p.in_stride, s.q.S, s.q.y_t, s.q.x_t, p.out, p.out_stride, IqFmt{});
+  }
+  return TSDR_OK;
+}
+
+// the FAST modes of k_down_fused (IQ input), once per input format
+template <int M, int SUMS, int LD>
+static int down_k(tsdr_ctx *ctx, const ImageStep &s, const DownParams &q, const StepPtrs &p) {
+  const dim3 grid = STEP_GRID, block(s.block);
+  if (s.iqf == IQF_SC16) { TSDR_LAUNCH(ctx, s.name, (k_down_fused<true, M, SUMS, LD, IQF_SC16>), grid, block, s.lds, DOWN_ARGS); }
+  else if (s.iqf == IQF_SC8) { TSDR_LAUNCH(ctx, s.name, (k_down_fused<true, M, SUMS, LD, IQF_SC8>), grid, block, s.lds, DOWN_ARGS); }
+  else if (s.iqf == IQF_UC8) { TSDR_LAUNCH(ctx, s.name, (k_down_fused<true, M, SUMS, LD, IQF_UC8>), grid, block, s.lds, DOWN_ARGS); }
+  else { TSDR_LAUNCH(ctx, s.name, (k_down_fused<true, M, SUMS, LD>), grid, block, s.lds, DOWN_ARGS); }
+  return TSDR_OK;
+}
+template <int M>
+static int down_m(tsdr_ctx *ctx, const ImageStep &s, const DownParams &q, const StepPtrs &p) {
+  if (s.sums) return s.ld == 16 ? down_k<M, DS_PSUM, 16>(ctx, s, q, p) : down_k<M, DS_PSUM, 4>(ctx, s, q, p);
+  return s.ld == 16 ? down_k<M, DS_NONE, 16>(ctx, s, q, p) : down_k<M, DS_NONE, 4>(ctx, s, q, p);
+}
+static int launch_down(tsdr_ctx *ctx, const ImageStep &s, const DownParams &q, const StepPtrs &p) {
+  if (s.mode == DM_FAST_FX) return down_m<DM_FAST_FX>(ctx, s, q, p);
+  if (s.mode == DM_FAST_F32) return down_m<DM_FAST_F32>(ctx, s, q, p);
+  const dim3 grid = STEP_GRID, block(s.block);
+  if (s.cplx) { TSDR_LAUNCH(ctx, s.name, (k_down_fused<true, DM_EXACT, DS_NONE, 4>), grid, block, s.lds, DOWN_ARGS); }
+  else { TSDR_LAUNCH(ctx, s.name, (k_down_fused<false, DM_EXACT, DS_NONE, 4>), grid, block, s.lds, DOWN_ARGS); }
+  return TSDR_OK;
+}
+#undef DOWN_ARGS
+#undef TILE_ARGS
+#undef FAST_ARGS
+#undef STEP_GRID
+
+int launch_shear(tsdr_ctx *ctx, const ImageStep &s, const float *in, size_t in_stride, float *out, size_t out_stride);   // raster_shear.hip
 
 int resize2d_d(tsdr_ctx *ctx, const float *img, int h_in, int w_in, int h_out, int w_out, float *out) {
   if (h_in <= 0 || w_in <= 0 || h_out <= 0 || w_out <= 0) return set_err(ctx, TSDR_EINVAL, "resize2d: sizes must be positive");
@@ -1440,152 +1230,49 @@ int resize2d_d(tsdr_ctx *ctx, const float *img, int h_in, int w_in, int h_out, i
   return TSDR_OK;
 }
 
-struct DownPlan { bool fused; int mode; DownParams q; size_t lds; };
-int raster_shear_d(tsdr_ctx *ctx, const float *in, size_t in_stride, size_t S, int y_t, int x_t, int frames, float *out,
-                   size_t out_stride, bool shear, bool *did, bool plan_only);
-
-static DownPlan plan_down(size_t S, int y_t, int x_t, int h_out, int w_out, bool exact, bool wide_exact = false, bool guard_tiles = false) {
-  DownPlan pl;
-  pl.fused = false;
-  pl.lds = 0;
-  pl.mode = DM_EXACT;
-  const double sf = (double)S / ((double)y_t * (double)x_t);
-  const double sfy = (double)y_t / (double)h_out, sfx = (double)x_t / (double)w_out;
-  const long NLd = (long)(63.0 * sfy) + 3;
-  // FAST: above a vertical ratio of ~2 the lines between an output row's two tap lines are more than half of the tile's
-  // span: stage just the 2 x 64 tap lines (C5: 128 instead of 239)
-  const bool sparse = !exact && NLd > 128;
-  const long NL = sparse ? 128 : NLd;
-  // 64-column tiles (4096 pixels per 256-thread workgroup) with f32 staging: measured at C2 against the former preference
-  // (32 columns at most, {a, slope} f64 pairs when they fit 32 KiB -- which held the tile to 16 columns): 50 vs 65 us for the
-  // FAST kernel; 128 columns: 58 us.  The EXACT tiling is the sync guard's as well and stays as it was.
-  static const int cand_fast[] = {64, 32, 16, 8, 4}, cand_exact[] = {32, 16, 8, 4, 0};
-  const int *cand = (exact && !wide_exact) ? cand_exact : cand_fast;   // wide_exact: the EXACT frame path (not the sync guard's tiles)
-  for (int pass = 1; pass < 3 && !pl.fused; ++pass) {
-    const int sb = 4;
-    // (the sync guard's kernel runs one workgroup per CU and opts in to a large LDS: the widest tile that fits 96 KiB -- at C3
-    // 32 columns instead of 16, i.e. one round of image tiles per flagged frame instead of two)
-    const size_t cap = guard_tiles ? 96 * 1024 : pass == 2 ? 60 * 1024 : 32 * 1024;
-    for (int ci = 0; ci < 5 && cand[ci] > 0; ++ci) {
-      const int TC = cand[ci];
-      const long DPX = (long)((double)(TC - 1) * sfx) + 2;
-      const long W = (long)((double)DPX * sf) + 4 + (exact ? 0 : (sf <= 0.5 ? 2 : 1));
-      const size_t lds = (((size_t)NL * (size_t)(W | 1) * sb + 15) & ~(size_t)15) + (size_t)TC * 20 + (size_t)NL * 4;
-      if (lds <= cap && W < (1 << 20)) {
-        pl.fused = true;
-        pl.lds = lds;
-        // FAST: fixed-point taps where a raster pixel spans at most half a sample (the second tap of a line then lies in the
-        // first one's three-sample window); one more staged sample for that window
-        pl.mode = exact ? DM_EXACT : (sf <= 0.5 ? DM_FAST_FX : DM_FAST_F32);
-        pl.q.S = (unsigned)S; pl.q.y_t = y_t; pl.q.x_t = x_t; pl.q.h_out = h_out; pl.q.w_out = w_out;
-        pl.q.sparse = sparse ? 1 : 0;
-        pl.q.TC = TC; pl.q.NL = (int)NL; pl.q.W = (int)W; pl.q.tiles_c = (int)ceil_div((size_t)w_out, (size_t)TC);
-        // staging lanes per line: a lane issues its loads four at a time, lpl samples apart, so a line costs
-        // ceil(W / 4 lpl) * 4 lpl load slots -- the power of two that wastes the fewest (round 4: the former rule counted
-        // ceil(W / lpl) * lpl and, for W = 29, chose 32 lanes per line: three of every four loads were clamped duplicates)
-        // wide rows (many samples per raster pixel): 16 loads in flight per lane, 8 lanes per line
-        const long LD = (!exact && W >= 48) ? 16 : 4;
-        pl.q.ld16 = LD == 16 ? 1 : 0;
-        int best = 2; long best_slots = 1L << 60;
-        for (int lg = 2; lg <= 6; ++lg) {
-          const long chunk = LD << lg, slots = (long)ceil_div((size_t)W, (size_t)chunk) * chunk;
-          if (slots < best_slots || (slots == best_slots && lg > best)) { best = lg; best_slots = slots; }
-        }
-        pl.q.lpl_log = best;
-        break;
-      }
+static int launch_step(tsdr_ctx *ctx, const ImageStep &s, const StepPtrs &p, float *proj, unsigned long long *keys) {
+  switch (s.kernel) {
+    case IK_FAST: case IK_FAST4: case IK_TILE: {
+      TileParams q = s.q;
+      if (s.sums) { q.proj = proj; q.keys = keys; }
+      return s.kernel == IK_FAST ? launch_fast(ctx, s, q, p) : s.kernel == IK_FAST4 ? launch_fast4(ctx, s, q, p) : launch_tile(ctx, s, q, p);
     }
+    case IK_DIRECT: return launch_direct(ctx, s, p);
+    case IK_DOWN: {
+      DownParams q = s.dq;
+      if (s.sums) { q.proj = proj; q.keys = keys; }
+      return launch_down(ctx, s, q, p);
+    }
+    case IK_SHEAR: return launch_shear(ctx, s, p.in, p.in_stride, p.out, p.out_stride);
+    case IK_RESIZE2D: return resize2d_d(ctx, p.out, s.rs[0], s.rs[1], s.rs[2], s.rs[3], p.down);
+    default: assert(!"a plan step names a kernel"); return TSDR_EINVAL;
   }
-  return pl;
 }
 
-// sig_to_image |> downgradeImage for `frames` frames, straight from the signal (no raster in HBM)
-// proj / got / keys (FAST, IQ input): the kernel also leaves the images' projection partial sums (layout in *got) and clears the
-// frames' argmax keys; plan_only: nothing is launched, *got says what a real call would produce (ncp == 0: nothing).
-int down_frames_d(tsdr_ctx *ctx, const float *in, int cplx, IqFmt iqf, int precision, size_t in_stride, size_t S, int y_t, int x_t,
-                  int h_out, int w_out, int frames, float *out, size_t out_stride, float *proj = nullptr, ProjLayout *got = nullptr,
-                  bool plan_only = false, unsigned long long *keys = nullptr) {
-  int rc = check_geom(ctx, S, y_t, x_t);
-  if (rc) return rc;
-  if (h_out <= 0 || w_out <= 0) return set_err(ctx, TSDR_EINVAL, "output size must be positive");
-  const bool same2 = (y_t == h_out && x_t == w_out);
-  if (!same2 && (y_t < 2 || x_t < 2)) return set_err(ctx, TSDR_EINVAL, "imresize needs at least a 2x2 raster");
-  if (frames <= 0) return TSDR_OK;
-  // imresize returns a copy when the sizes already match: the raster IS the result
-  if (same2) return plan_only ? TSDR_OK : raster_frames_d(ctx, in, cplx, iqf, precision, in_stride, S, y_t, x_t, frames, out, out_stride);
-  const size_t P = (size_t)y_t * x_t;
-  const bool exact = precision == TSDR_EXACT || !cplx;
-  DownPlan pl = plan_down(S, y_t, x_t, h_out, w_out, exact, true);
-  if (cplx) pl.q.iqf = iqf;
-  if (pl.fused) {
-    const bool psum = !exact && got != nullptr && (plan_only || (proj != nullptr && keys != nullptr));
-    if (psum) {
-      got->ncp = (int)ceil_div((size_t)h_out, 64);
-      got->nrp = pl.q.tiles_c;
-    }
-    if (plan_only) return TSDR_OK;
-    dim3 grid((unsigned)(ceil_div((size_t)h_out, 64) * (size_t)pl.q.tiles_c), (unsigned)frames);
-    if (ctx->opt_down_xcd && !exact) {
-      pl.q.xcd_tiles = (int)grid.x;
-      pl.q.xcd_tpx = (int)ceil_div((size_t)grid.x, 8);
-      grid = dim3((unsigned)(8 * pl.q.xcd_tpx * frames), 1);
-    }
-    const size_t lds_main = (pl.lds + 15) & ~(size_t)15;
-  // (the FAST kernels exist once per input format -- ComplexF32 or int16 pairs -- the EXACT one reads either)
-#define DOWNKL(C, M, SUMS, LDN, NAME, LDS)                                                                                         \
-  do {                                                                                                                             \
-    if (M != DM_EXACT && pl.q.iqf.kind == IQK_SC16) {                                                                              \
-      TSDR_LAUNCH(ctx, NAME, (k_down_fused<C, M, SUMS, LDN, (M == DM_EXACT ? IQF_RT : IQF_SC16)>), grid, dim3(kDownNT), LDS, in,   \
-                  in_stride, pl.q, out, out_stride, lds_main);                                                                     \
-    } else if (M != DM_EXACT && pl.q.iqf.kind == IQK_SC8) {                                                                        \
-      TSDR_LAUNCH(ctx, NAME, (k_down_fused<C, M, SUMS, LDN, (M == DM_EXACT ? IQF_RT : IQF_SC8)>), grid, dim3(kDownNT), LDS, in,    \
-                  in_stride, pl.q, out, out_stride, lds_main);                                                                     \
-    } else if (M != DM_EXACT && pl.q.iqf.kind == IQK_UC8) {                                                                        \
-      TSDR_LAUNCH(ctx, NAME, (k_down_fused<C, M, SUMS, LDN, (M == DM_EXACT ? IQF_RT : IQF_UC8)>), grid, dim3(kDownNT), LDS, in,    \
-                  in_stride, pl.q, out, out_stride, lds_main);                                                                     \
-    } else {                                                                                                                       \
-      TSDR_LAUNCH(ctx, NAME, (k_down_fused<C, M, SUMS, LDN>), grid, dim3(kDownNT), LDS, in, in_stride, pl.q, out, out_stride,     \
-                  lds_main);                                                                                                       \
-    }                                                                                                                              \
-  } while (0)
-#define DOWNK(C, M, SUMS, NAME, LDS) DOWNKL(C, M, SUMS, 4, NAME, LDS)
-#define DOWNK16(C, M, SUMS, NAME, LDS) DOWNKL(C, M, SUMS, 16, NAME, LDS)
-    const size_t lds_ps = lds_main + (kDownNT + (size_t)pl.q.TC) * 4;
-    if (cplx) {
-      if (pl.mode == DM_EXACT) { DOWNK(true, DM_EXACT, DS_NONE, "down_fused_iq_exact", pl.lds); }
-      else if (psum) {
-        pl.q.proj = proj; pl.q.proj_stride = proj_floats(h_out, w_out, *got); pl.q.keys = keys;
-        if (pl.mode == DM_FAST_FX) {
-          if (pl.q.ld16) { DOWNK16(true, DM_FAST_FX, DS_PSUM, "down_fused_iq_sums", lds_ps); } else { DOWNK(true, DM_FAST_FX, DS_PSUM, "down_fused_iq_sums", lds_ps); }
-        } else {
-          if (pl.q.ld16) { DOWNK16(true, DM_FAST_F32, DS_PSUM, "down_fused_iq_sums", lds_ps); } else { DOWNK(true, DM_FAST_F32, DS_PSUM, "down_fused_iq_sums", lds_ps); }
-        }
-      }
-      else if (pl.mode == DM_FAST_FX) {
-        if (pl.q.ld16) { DOWNK16(true, DM_FAST_FX, DS_NONE, "down_fused_iq", pl.lds); } else { DOWNK(true, DM_FAST_FX, DS_NONE, "down_fused_iq", pl.lds); }
-      }
-      else if (pl.q.ld16) { DOWNK16(true, DM_FAST_F32, DS_NONE, "down_fused_iq", pl.lds); }
-      else { DOWNK(true, DM_FAST_F32, DS_NONE, "down_fused_iq", pl.lds); }
-    } else {
-      DOWNK(false, DM_EXACT, DS_NONE, "down_fused_f32_exact", pl.lds);
-    }
-#undef DOWNK16
-#undef DOWNK
-#undef DOWNKL
-    return TSDR_OK;
+// Launch what plan_images decided.  proj / keys: room for the projection partial sums the plan says it forms (plan.sums) and the
+// frames' argmax keys, which the same kernel clears.
+int launch_images(tsdr_ctx *ctx, const ImagePlan &pl, const float *in, float *raster, size_t raster_stride, float *down,
+                  size_t down_stride, float *proj, unsigned long long *keys) {
+  if (pl.status) return set_err(ctx, pl.status, "%s", pl.err);
+  assert(!pl.sums.ncp || (proj && keys));   // a plan that forms projection sums is launched with room for them
+  const int whole = pl.nsteps - (pl.fallback ? 2 : 0);
+  for (int i = 0; i < whole; ++i) {
+    const ImageStep &s = pl.step[i];
+    const StepPtrs p{in, pl.in_stride, s.to_images ? down : raster, s.to_images ? down_stride : raster_stride, down, down_stride};
+    if (int rc = launch_step(ctx, s, p, proj, keys)) return rc;
   }
-  if (plan_only) return TSDR_OK;
-  // fallback: materialise each raster in workspace, then the generic 2-D resize
+  if (!pl.fallback) return TSDR_OK;
+  // per frame: the raster into workspace, then the generic 2-D resize
   // (one raster per pipeline lane: two submissions of tsdr_frames_submit_d may be walking this loop side by side)
-  float *ras = (float *)ctx->scratch(WS_RASTER, 4 * P * 4);
+  const ImageStep &rs = pl.step[whole], &ds = pl.step[whole + 1];
+  const size_t P = (size_t)ds.rs[0] * (size_t)ds.rs[1];
+  float *ras = (float *)ctx->scratch(WS_RASTER, pl.ws_raster);
   if (!ras) return TSDR_ENOMEM;
   ras += (size_t)(ctx->pipe_lane & 3) * P;
-  for (int f = 0; f < frames; ++f) {
-    rc = raster_frames_d(ctx, cplx ? iq_at(in, (size_t)f * in_stride, iq_bytes(iqf)) : in + (size_t)f * in_stride, cplx, iqf, precision,
-                         in_stride, S, y_t, x_t, 1, ras, P);
-    if (rc) return rc;
-    rc = resize2d_d(ctx, ras, y_t, x_t, h_out, w_out, out + (size_t)f * out_stride);
-    if (rc) return rc;
+  for (int f = 0; f < pl.frames; ++f) {
+    const float *in_f = rs.cplx ? iq_at(in, (size_t)f * pl.in_stride, iq_bytes(rs.q.iqf)) : in + (size_t)f * pl.in_stride;
+    if (int rc = launch_step(ctx, rs, StepPtrs{in_f, pl.in_stride, ras, P, nullptr, 0}, nullptr, nullptr)) return rc;
+    if (int rc = launch_step(ctx, ds, StepPtrs{nullptr, 0, ras, P, down + (size_t)f * down_stride, 0}, nullptr, nullptr)) return rc;
   }
   return TSDR_OK;
 }
@@ -1593,75 +1280,14 @@ int down_frames_d(tsdr_ctx *ctx, const float *in, int cplx, IqFmt iqf, int preci
 // Sync guard (guard.h): the tiling of the EXACT raster-free kernel for this geometry, whose workgroup body the guard's
 // kernel (sync.hip) runs on the frames it flags.  false: this geometry has no fused exact kernel.
 bool guard_image_plan(tsdr_ctx *ctx, IqFmt iqf, size_t S, int y_t, int x_t, int h_out, int w_out, DownParams *q, size_t *lds) {
-  if (check_geom(ctx, S, y_t, x_t)) return false;
+  if (const char *e = geom_error(S, y_t, x_t)) { set_err(ctx, TSDR_EINVAL, "%s", e); return false; }
   if ((y_t == h_out && x_t == w_out) || y_t < 2 || x_t < 2) return false;
-  DownPlan pl = plan_down(S, y_t, x_t, h_out, w_out, /*exact=*/true, false, /*guard_tiles=*/true);
+  DownPlan pl = plan_down_tiles(S, y_t, x_t, h_out, w_out, /*exact=*/true, false, /*guard_tiles=*/true);
   if (!pl.fused) return false;
   pl.q.iqf = iqf;
   *q = pl.q;
   *lds = pl.lds;
   return true;
-}
-
-// raster (optional) + (h_out,w_out) image for every frame with as few passes over IQ as possible.
-// proj != nullptr: room for the projection partial sums of every (h_out, w_out) image (layout: sync_layout.h); when the
-// FAST tile kernel runs it leaves them there and describes them in *got (ncp == 0: not produced -- the caller then
-// forms the projections from the images).  plan_only: nothing is launched, *got says what a real call would produce.
-int raster_and_down_d(tsdr_ctx *ctx, const float *in, int cplx, IqFmt iqf, int precision, size_t in_stride, size_t S, int y_t, int x_t, int h_out,
-                      int w_out, int frames, float *raster, size_t raster_stride, float *down, size_t down_stride,
-                      float *proj, ProjLayout *got, bool plan_only, unsigned long long *keys) {
-  if (got) *got = ProjLayout{};
-  // FAST without a raster to write: k_down_fused re-derives the four taps of every output pixel from 64 x 64-pixel tiles of
-  // staged samples and leaves the projection partial sums itself (round 3: 54 us at C2 against the walk's 77 us with
-  // out == null -- the walk evaluates all 2.9 M raster pixels of a frame for the 1.8 M that are taps).  Other geometries
-  // fall through to the walk, then to the raster + resize fallback.
-  if (!raster && precision == TSDR_FAST && cplx && !ctx->opt_fast_walk_only) {
-    ProjLayout pl{};
-    const DownPlan dp = plan_down(S, y_t, x_t, h_out, w_out, false);
-    // ... where a tile of at least 32 columns fits (C2: 0.115 samples per raster pixel, 64 columns, 0.102 vs 0.123 ms per buffer
-    // in round 3; C5: 0.084, 0.138 vs 0.279 ms), or, above 0.5 samples per raster pixel, one of 16 (C3: 1.15 samples per pixel --
-    // the walk won there, 0.420 vs 0.461 ms, while the tap kernel staged its 121-sample rows four loads at a time: a chain of
-    // dependent round trips, 28 us per tile.  With 16 loads in flight per lane: 186 us against the walk's 323 + k_proj's 24,
-    // 0.243 vs 0.403 ms per buffer).  Option "down_spp_max_pct" (default 200) bounds the ratio; the walk keeps the rest.
-    const double spp = (double)S / ((double)y_t * (double)x_t);   // samples per raster pixel
-    if (dp.fused && dp.q.TC >= (spp > 0.5 ? 16 : 32) && spp <= (double)ctx->opt_down_spp_max_pct * 0.01 && !(y_t == h_out && x_t == w_out) &&
-        check_geom(ctx, S, y_t, x_t) == TSDR_OK && y_t >= 2 && x_t >= 2) {
-      int rc = down_frames_d(ctx, in, cplx, iqf, precision, in_stride, S, y_t, x_t, h_out, w_out, frames, down, down_stride, proj, got ? &pl : nullptr,
-                             plan_only, keys);
-      if (rc) return rc;
-      if (got) *got = pl;
-      return TSDR_OK;
-    }
-  }
-  // FAST with a raster (option "raster_split"; A/B of round 4): the rasters by the store-aligned ("sheared") raster-only
-  // kernel of raster_shear.hip, the images + projection sums by the raster-free kernel -- two launches, IQ read twice,
-  // instead of the one walk that produces raster, image and sums with misaligned column stores
-  if (raster && precision == TSDR_FAST && cplx && ctx->opt_raster_split && iqf.kind == IQK_CF32) {   // (the A/B kernel reads ComplexF32 only)
-    const DownPlan dp = plan_down(S, y_t, x_t, h_out, w_out, false);
-    const double spp = (double)S / ((double)y_t * (double)x_t);
-    if (dp.fused && dp.q.TC >= 32 && spp <= 0.5 && !(y_t == h_out && x_t == w_out) && check_geom(ctx, S, y_t, x_t) == TSDR_OK && y_t >= 64 && x_t >= 128) {
-      bool did = false;
-      int rc = raster_shear_d(ctx, in, in_stride, S, y_t, x_t, frames, raster, raster_stride, ctx->opt_raster_split == 1, &did, plan_only);
-      if (rc) return rc;
-      if (did) {
-        ProjLayout pl{};
-        rc = down_frames_d(ctx, in, cplx, iqf, precision, in_stride, S, y_t, x_t, h_out, w_out, frames, down, down_stride, proj, got ? &pl : nullptr, plan_only, keys);
-        if (rc) return rc;
-        if (got) *got = pl;
-        return TSDR_OK;
-      }
-    }
-  }
-  if (raster || (precision == TSDR_FAST && cplx)) {
-    bool did = false;
-    ProjLayout pl{};
-    int rc = raster_frames_d(ctx, in, cplx, iqf, precision, in_stride, S, y_t, x_t, frames, raster, raster_stride, down, down_stride, h_out,
-                             w_out, &did, proj, got ? &pl : nullptr, plan_only, keys);
-    if (rc) return rc;
-    if (did) { if (got) *got = pl; return TSDR_OK; }
-  }
-  if (plan_only) return TSDR_OK;
-  return down_frames_d(ctx, in, cplx, iqf, precision, in_stride, S, y_t, x_t, h_out, w_out, frames, down, down_stride);
 }
 
 }  // namespace tsdr
@@ -1684,7 +1310,9 @@ int tsdr_sig_to_image_d(tsdr_ctx *ctx, const float *sig, size_t S, int y_t, int 
   if (!ctx || !sig || !img) return TSDR_EINVAL;
   TSDR_PTR_ALIGNED(ctx, "sig_to_image", sig, 4);
   TSDR_PTR_ALIGNED(ctx, "sig_to_image", img, 4);
-  return raster_frames_d(ctx, sig, 0, IqFmt{}, TSDR_EXACT, S, S, y_t, x_t, 1, img, (size_t)y_t * x_t);
+  ImageReq r;
+  r.cplx = 0; r.precision = TSDR_EXACT; r.S = r.in_stride = S; r.y_t = y_t; r.x_t = x_t; r.frames = 1; r.raster = true;
+  return launch_images(ctx, plan_images(plan_opts(ctx), r), sig, img, (size_t)y_t * x_t, nullptr, 0, nullptr, nullptr);
 }
 
 int tsdr_resize2d_d(tsdr_ctx *ctx, const float *img, int h_in, int w_in, int h_out, int w_out, float *out) {

@@ -26,8 +26,11 @@ done | xargs -P "${JOBS:-8}" -L 1 bash -c '
   '"$HIPCC $FLAGS"' -w --cuda-device-only --no-gpu-bundle-output -c '"$TMP"'/$0/tempestsdr.jl_amd/csrc/$1.hip -o $e
   for s in text rodata; do '"$LLVM"'/llvm-objcopy -O binary --only-section=.$s $e $e.$s; done'
 figures() {  # kernel symbols with their sizes, then each kernel's resource figures from the code object's metadata note
-  "$LLVM/llvm-readelf" -sW "$1" | awk '$4 == "FUNC" || $4 == "OBJECT" { print $8, $3 }' | sort
-  "$LLVM/llvm-readelf" --notes "$1" | grep -E '^ +\.(name|sgpr_count|vgpr_count|agpr_count|sgpr_spill_count|vgpr_spill_count|group_segment_fixed_size|private_segment_fixed_size|kernarg_segment_size|max_flat_workgroup_size):' | sed 's/^ *//'
+  # (both sorted by name: a host-side change may move the order in which kernels are emitted; the per-source id symbol
+  # __hip_cuid_* differs whenever the source text does)
+  "$LLVM/llvm-readelf" -sW "$1" | awk '($4 == "FUNC" || $4 == "OBJECT") && $8 !~ /^__hip_cuid_/ { print $8, $3 }' | sort
+  "$LLVM/llvm-readelf" --notes "$1" | grep -E '^ +\.(name|sgpr_count|vgpr_count|agpr_count|sgpr_spill_count|vgpr_spill_count|group_segment_fixed_size|private_segment_fixed_size|kernarg_segment_size|max_flat_workgroup_size):' | sed 's/^ *//' |
+    awk '{ k = $1 } k in seen { print name, rec; delete seen; rec = "" } { seen[k] = 1; if (k == ".name:") name = $2; else rec = rec " " $1 $2 } END { if (rec != "") print name, rec }' | sort
 }
 bad=0
 for f in "$TMP"/new/tempestsdr.jl_amd/csrc/*.hip; do
@@ -40,7 +43,7 @@ for f in "$TMP"/new/tempestsdr.jl_amd/csrc/*.hip; do
   if [ $same = 0 ]; then
     bad=1
     figures "$TMP/o/old.$n.elf" > "$TMP/o/$n.old.fig"; figures "$TMP/o/new.$n.elf" > "$TMP/o/$n.new.fig"
-    if diff "$TMP/o/$n.old.fig" "$TMP/o/$n.new.fig"; then echo "  $n: $(grep -c '^\.name:' "$TMP/o/$n.new.fig") kernels, same symbols, sizes and register / LDS / scratch figures"; fi
+    if diff "$TMP/o/$n.old.fig" "$TMP/o/$n.new.fig"; then echo "  $n: $(grep -c ' \.sgpr_count:' "$TMP/o/$n.new.fig") kernels, same symbols, sizes and register / LDS / scratch figures"; fi
   fi
 done
 exit $bad
