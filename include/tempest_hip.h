@@ -291,6 +291,10 @@ int tsdr_zoom_bounds(size_t N, double Fs, double rate_min, double rate_max, size
  * synchronisation, whose wake-up costs 0.1-0.4 ms once the work queued before it is longer than a few hundred
  * microseconds; everything enqueued on the context's stream before the call has completed when it returns. */
 int tsdr_argmax_d(tsdr_ctx *ctx, const float *v, size_t n, size_t *idx, float *val);
+/* calculate_autocorrelation of COMPLEX input (ComplexF32, ComplexF64, integer IQ as stored): the coherent autocorrelation of the
+ * IQ samples themselves -- host and device forms, the search twin, their contract (SEMANTICS / BIT IDENTITY / ROUTES / ALIGNMENT /
+ * EDGE CASES) */
+#include "tempest_hip_cplx.h"
 
 /* ---- GetSpectrum.jl --------------------------------------------------------------- */
 /* getSpectrum(fs,sig;N): y = 10log10(abs2(fftshift(fft(sig[1:N]))))  GetSpectrum.jl:21-30

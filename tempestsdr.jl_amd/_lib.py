@@ -206,6 +206,18 @@ _SIGS_IQ = {
     "tsdr_iq_expand_d": (C.c_int, [vp, vp, C.c_int, C.c_float, c_sz, vp]),
 }
 
+# include/tempest_hip_cplx.h (the other header tempest_hip.h includes): calculate_autocorrelation of complex input -- ComplexF32,
+# integer IQ as stored, ComplexF64 -- and its search twin
+_AC = [c_sz, C.c_double, C.c_double, C.c_double, C.c_int, vp, c_szp]   # len, Fs, minDelay, maxDelay, log_scale, out, n_out
+_SIGS_CPLX = {
+    "tsdr_autocorr_cplx": (C.c_int, [vp, vp] + _AC),
+    "tsdr_autocorr_cplx_d": (C.c_int, [vp, vp] + _AC),
+    "tsdr_autocorr_cplx_iq": (C.c_int, [vp, vp, C.c_int, C.c_float] + _AC),
+    "tsdr_autocorr_cplx_search_iq_d": (C.c_int, [vp, vp, C.c_int, C.c_float] + _AC + [c_sz, c_sz, c_szp, c_f]),
+    "tsdr_autocorr_cplx_f64": (C.c_int, [vp, vp] + _AC),
+    "tsdr_autocorr_cplx_f64_d": (C.c_int, [vp, vp] + _AC),
+}
+
 
 def exported_names():
     """Every symbol include/tempest_hip.h declares (kept in sync by tests/test_abi.py)."""
@@ -215,6 +227,11 @@ def exported_names():
 def exported_names_iq():
     """Every symbol include/tempest_hip_iq.h declares (kept in sync by tests/test_iq_spectra_host.py)."""
     return sorted(_SIGS_IQ)
+
+
+def exported_names_cplx():
+    """Every symbol include/tempest_hip_cplx.h declares (kept in sync by tests/test_autocorr_complex_host.py)."""
+    return sorted(_SIGS_CPLX)
 
 
 def _share_torch_hip_runtime():
@@ -242,7 +259,7 @@ def load():
             f"{LIB_PATH} not found: build it with `python tempestsdr.jl_amd/build.py` "
             "(there is no CPU fallback)")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_IQ.items()):
+    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_IQ.items()) + list(_SIGS_CPLX.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI is incomplete
         fn.restype = res
         fn.argtypes = args

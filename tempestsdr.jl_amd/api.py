@@ -342,7 +342,13 @@ class Context:
         return Resampler(self, int(bufferSize), int(upCoeff), dtype=np.dtype(T))
 
     # -- Autocorrelations.jl --------------------------------------------------------------
-    def calculate_autocorrelation(self, x, Fs, minDelay, maxDelay, scale="log", *, dtype=None):
+    def calculate_autocorrelation(self, x, Fs, minDelay, maxDelay, scale="log", *, dtype=None, iq_fmt=None, iq_scale=1.0):
+        """Real x: the autocorrelation of x (Float32, or Float64 with dtype=np.float64).  Complex x -- complex64, complex128
+        with dtype=np.float64, or with iq_fmt "sc16" / "sc8" / "uc8" (keyword only) an int16 / int8 / uint8 array of 2*n
+        interleaved components -- takes the complex route: the coherent autocorrelation of the IQ samples themselves
+        (autocorr_cplx.py; the reference function is untyped, Autocorrelations.jl:23-37)."""
+        if iq_fmt is not None or np.iscomplexobj(x):
+            return autocorr_cplx.calculate(self, x, Fs, minDelay, maxDelay, scale, dtype=dtype, iq_fmt=iq_fmt, iq_scale=iq_scale)
         f64 = _is64(dtype)
         xv = _f64(x, "calculate_autocorrelation") if f64 else _f32(x)
         index_min = 1 + int(np.round(minDelay * Fs))
@@ -411,6 +417,13 @@ class Context:
             if d_out is not None:
                 self.dev_free(d_out)
         return G, int(idx.value), float(val.value)
+
+    def autocorr_search_complex(self, sig, Fs, minDelay, maxDelay, rate_min=50, rate_max=90, scale="log", *, iq_fmt=None, iq_scale=1.0,
+                                n_samples=None):
+        """autocorr_search on the complex samples themselves (no abs2 before the correlation): a complex array, integer IQ
+        with iq_fmt, or a device address with iq_fmt and n_samples -> (G, pos, val).  autocorr_cplx.search."""
+        return autocorr_cplx.search(self, sig, Fs, minDelay, maxDelay, rate_min, rate_max, scale, iq_fmt=iq_fmt, iq_scale=iq_scale,
+                                    n_samples=n_samples)
 
     def zoom_autocorr(self, G, Fs, rate_min=20, rate_max=100):
         pmin, pmax = C.c_size_t(0), C.c_size_t(0)
@@ -621,6 +634,8 @@ def _int_iq(sig, iq_fmt, what):
 # Device-pointer forms of the spectra and demodulators on a buffer of `fmt` samples (the entry points of include/tempest_hip_iq.h):
 # iq.py, re-exported here next to frames_iq_d.
 from .iq import DEMOD_IQ, demod_iq_d, expand_iq_d, spectrum_iq_d, waterfall_iq_d, welch_iq_d  # noqa: E402
+# calculate_autocorrelation of complex input (the entry points of include/tempest_hip_cplx.h): autocorr_cplx.py
+from . import autocorr_cplx  # noqa: E402
 
 
 def frames_iq_d(ctx, sync, iq, fmt, scale, nEch, S, y_t, x_t, alpha, do_align, state, frames_out=None, raster_out=None, sync_idx=None,
@@ -976,8 +991,8 @@ def sig_to_image(sig, y_t, x_t, *, dtype=None): return default_context().sig_to_
 def downgradeImage(image, *, dtype=None): return default_context().downgradeImage(image, dtype=dtype)
 def naiveResampler(sigOut, sigId, upCoeff, *, dtype=None): return default_context().naiveResampler(sigOut, sigId, upCoeff, dtype=dtype)
 def init_resampler(T, bufferSize, upCoeff): return default_context().init_resampler(T, bufferSize, upCoeff)
-def calculate_autocorrelation(x, Fs, minDelay, maxDelay, scale="log", *, dtype=None):
-    return default_context().calculate_autocorrelation(x, Fs, minDelay, maxDelay, scale, dtype=dtype)
+def calculate_autocorrelation(x, Fs, minDelay, maxDelay, scale="log", *, dtype=None, iq_fmt=None, iq_scale=1.0):
+    return default_context().calculate_autocorrelation(x, Fs, minDelay, maxDelay, scale, dtype=dtype, iq_fmt=iq_fmt, iq_scale=iq_scale)
 def zoom_autocorr(G, Fs, rate_min=20, rate_max=100): return default_context().zoom_autocorr(G, Fs, rate_min, rate_max)
 def getSpectrum(fs, sig, N=None, *, dtype=None): return default_context().getSpectrum(fs, sig, N, dtype=dtype)
 def getWelch(fe, sig, sizeFFT=1024, *, dtype=None): return default_context().getWelch(fe, sig, sizeFFT, dtype=dtype)

@@ -18,6 +18,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "amax.h"
 #include "fft_dev.h"
 
 namespace tsdr {
@@ -197,16 +198,6 @@ __global__ __launch_bounds__(64) void k_amax_publish(unsigned long long *__restr
 }
 
 static inline double jl_round(double v) { return nearbyint(v); }  // Julia round(): ties to even
-
-// findmax fused into the autocorrelation's last pass: the window and where the result goes (see amax_begin / amax_wait)
-struct AmaxReq {
-  size_t lo = 0, cnt = 0;  // window out[lo .. lo + cnt)
-  unsigned long long *key = nullptr, *clear = nullptr, *slots = nullptr;
-  unsigned *arrived = nullptr;
-  unsigned long long *host = nullptr;
-  unsigned long long seq = 0;
-  bool fused = false;      // out: the last pass delivered the maximum (else the caller runs k_argmax)
-};
 
 // shared core: x (real f32, or IQ whose abs2 is taken on the fly), first n samples
 static int autocorr_core(tsdr_ctx *ctx, const float *x, int is_iq, size_t n, size_t k0, size_t cnt, int log_scale,
@@ -388,8 +379,11 @@ int tsdr_zoom_bounds(size_t N, double Fs, double rate_min, double rate_max, size
   return TSDR_OK;
 }
 
+}  // extern "C"
+namespace tsdr {   // (amax.h: shared with autocorr_cplx.hip)
+
 // one findmax request: the key slot for this search (zero), the slot to clear for the next one, the sequence number
-static int amax_begin(tsdr_ctx *ctx, AmaxReq *r) {
+int amax_begin(tsdr_ctx *ctx, AmaxReq *r) {
   if (!ctx->amax_keys) {
     TSDR_HIP(ctx, hipMalloc((void **)&ctx->amax_keys, 32 + 8 * kAmaxSlots));  // two key slots + the arrival counter + fused-findmax slots
     TSDR_HIP(ctx, hipMemset(ctx->amax_keys, 0, 32 + 8 * kAmaxSlots));
@@ -418,7 +412,7 @@ static int amax_begin(tsdr_ctx *ctx, AmaxReq *r) {
 
 // the value rides in the key's upper half (NaN canonicalised); the kernel delivers key and sequence number to pinned
 // memory and the host polls the sequence word
-static int amax_wait(tsdr_ctx *ctx, unsigned long long seq, size_t *idx, float *val) {
+int amax_wait(tsdr_ctx *ctx, unsigned long long seq, size_t *idx, float *val) {
   bool seen = false;
   std::chrono::steady_clock::time_point t0;
   for (unsigned it = 1; !seen; ++it) {
@@ -448,12 +442,21 @@ static int amax_wait(tsdr_ctx *ctx, unsigned long long seq, size_t *idx, float *
   return TSDR_OK;
 }
 
-static int argmax_launch(tsdr_ctx *ctx, const float *v, size_t n, const AmaxReq &r) {
+int argmax_launch(tsdr_ctx *ctx, const float *v, size_t n, const AmaxReq &r) {
   const int ablocks = (int)std::min<size_t>(ceil_div(n, 2048), 256);
   TSDR_LAUNCH(ctx, "argmax", k_argmax, dim3(ablocks), dim3(256), 0, v, n, r.key, r.clear, r.arrived, r.host, r.seq);
   ctx->amax_slot ^= 1;
   return TSDR_OK;
 }
+
+// behind a last pass that carried the findmax: the one-wavefront launch that folds the slot words and hands the winner over
+int amax_publish(tsdr_ctx *ctx, const AmaxReq &r) {
+  TSDR_LAUNCH(ctx, "amax_publish", k_amax_publish, dim3(1), dim3(64), 0, r.slots, r.host, r.seq);
+  return TSDR_OK;
+}
+
+}  // namespace tsdr
+extern "C" {
 
 int tsdr_argmax_d(tsdr_ctx *ctx, const float *v, size_t n, size_t *idx, float *val) {
   if (!ctx || !v || !idx || n == 0) return TSDR_EINVAL;  // findmax of an empty collection throws
@@ -494,7 +497,8 @@ static int autocorr_search_any_d(tsdr_ctx *ctx, const float *x, int is_iq, float
     rc = argmax_launch(ctx, out + win_lo, win_cnt, r);
     if (rc) return rc;
   } else {
-    TSDR_LAUNCH(ctx, "amax_publish", k_amax_publish, dim3(1), dim3(64), 0, r.slots, r.host, r.seq);
+    rc = amax_publish(ctx, r);
+    if (rc) return rc;
     ctx->amax_dirty = false;
   }
   return amax_wait(ctx, r.seq, idx, val);

@@ -236,6 +236,7 @@ __global__ __launch_bounds__(256) void k_fft_pass(const float2 *__restrict__ in,
     // digits k_2..k_{p-1} of arest -> their natural-order weight (already multiples of R_1)
     const unsigned Kp = digit_swap(arest, d.nprev - 1, d.logRprev + 1) << d.logR1;
     const size_t orel = (size_t)kt * T + Kp;
+    unsigned long long best = 0ull;   // fused findmax of an epilogue that asks for one (fft_dev.h: EPI_CAC)
 #pragma unroll
     for (int q = 0; q < CO; ++q) {
       const int s = tid + 256 * q;
@@ -249,10 +250,14 @@ __global__ __launch_bounds__(256) void k_fft_pass(const float2 *__restrict__ in,
           // outputs past `keep` are never looked at by the caller (e.g. lags beyond the window)
           if (o < d.keep) {
             const float2 y = conj_if(make_float2(x.x * d.scale, x.y * d.scale), smask);
-            if (d.epi.out) epilogue_store(d.epi, o, y); else out[tbase + o] = y;
+            if (d.epi.out) epilogue_store(d.epi, o, y, best); else out[tbase + o] = y;
           }
         }
       }
+    }
+    if (d.epi.amax_keys) {
+      __syncthreads();  // the exchange buffer is dead: its first words carry the wavefronts' keys
+      epi_argmax_finish(d.epi, best, reinterpret_cast<unsigned long long *>(sm), 4);
     }
   } else {
     __syncthreads();  // exchange buffer fully read

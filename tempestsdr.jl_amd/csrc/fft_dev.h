@@ -163,8 +163,10 @@ __device__ inline float2 conj_if(float2 v, unsigned smask) {  // smask = 0x80000
 //   SRC_RE0   (x[g], 0): a real f32 sequence as complex input (getSpectrum of a real signal) -- k_r2c without its pass
 //   SRC_MULH  in[g] * aux[g], aux = ComplexF64 (double2 behind the float2 pointer): the resampler's frequency-domain filter
 //             applied while the inverse transform loads -- evaluated in f64 and rounded to ComplexF32 (Resampler.jl:51-53)
+//   SRC_ABS2  (|in[g]|^2, 0): the power spectrum of a COMPLEX sequence while the inverse transform of its autocorrelation
+//             loads (autocorr_cplx.hip) -- pointwise, re*re + im*im, a zero imaginary part; SRC_POWER's place on that route
 enum { SRC_C2C = 0, SRC_REAL = 1, SRC_IQPOW = 2, SRC_POWER = 3, SRC_STUFF = 4, SRC_MULH = 5, SRC_RE0 = 6, SRC_IQPOW_SC16 = 7, SRC_IQPOW_SC8 = 8, SRC_IQPOW_UC8 = 9,
-       SRC_IQ_SC16 = 10, SRC_IQ_SC8 = 11, SRC_IQ_UC8 = 12 };
+       SRC_IQ_SC16 = 10, SRC_IQ_SC8 = 11, SRC_IQ_UC8 = 12, SRC_ABS2 = 13 };
 inline bool src_is_int_iq(int src_mode) { return src_mode >= SRC_IQPOW_SC16 && src_mode <= SRC_IQ_UC8; }
 inline bool src_is_cplx_int(int src_mode) { return src_mode >= SRC_IQ_SC16 && src_mode <= SRC_IQ_UC8; }
 inline int src_of_iq(const IqFmt &f) { return f.kind == IQK_SC16 ? SRC_IQ_SC16 : f.kind == IQK_SC8 ? SRC_IQ_SC8 : f.kind == IQK_UC8 ? SRC_IQ_UC8 : SRC_C2C; }
@@ -199,6 +201,10 @@ __device__ inline float2 fft_load(const float2 *__restrict__ in, int src_mode, u
     const float P0 = X0.x * X0.x + X0.y * X0.y, P1 = X1.x * X1.x + X1.y * X1.y;
     const float sum = P0 + P1, dif = P0 - P1;
     return make_float2(sum + dif * W.y, dif * W.x);  // (P + P') + i conj(W) (P - P')
+  }
+  if (src_mode == SRC_ABS2) {
+    const float2 a = in[g];
+    return make_float2(a.x * a.x + a.y * a.y, 0.f);
   }
   if (src_mode >= SRC_IQ_SC16) {
     if (src_mode == SRC_IQ_SC16) return cvt_sc16(reinterpret_cast<const short2 *>(in)[g], (float)inv_m8);
@@ -258,14 +264,16 @@ __device__ inline float2 tw_frac(unsigned e, double inv_n8) {
 //              arrival counter: a release fence per workgroup writes its freshly stored lags back through L2 and tripled
 //              the pass (measured 12 -> 38 us at C2).  A one-wavefront launch behind the pass folds the slots and hands
 //              the result to the host (k_amax_publish); the separate pass over the lags is gone.
-enum { EPI_NONE = 0, EPI_AC = 1, EPI_REAL = 2, EPI_SPEC = 3 };
+//   EPI_CAC    autocorrelation of a COMPLEX sequence (autocorr_cplx.hip): x is the one complex lag o; lags k0 <= o < k0+cnt
+//              leave as abs2 (and 10log10) at out[o - k0], order and rounding as EPI_SPEC; the fused findmax as EPI_AC
+enum { EPI_NONE = 0, EPI_AC = 1, EPI_REAL = 2, EPI_SPEC = 3, EPI_CAC = 4 };
 struct FftEpilogue {
   float *out = nullptr;
   unsigned long long k0 = 0, cnt = 0;
   int log_scale = 0;
   int kind = EPI_AC;
   float gain = 1.0f;
-  // fused findmax (EPI_AC only)
+  // fused findmax (EPI_AC and EPI_CAC)
   unsigned long long *amax_keys = nullptr;  // kAmaxSlots device words, zero on entry
   unsigned long long amax_lo = 0, amax_cnt = 0;
 };
@@ -289,6 +297,15 @@ __device__ inline void epilogue_store(const FftEpilogue &e, size_t o, float2 x, 
       if (j >= e.cnt) j -= e.cnt;
       const float p = x.x * x.x + x.y * x.y;
       e.out[j] = e.log_scale ? 10.0f * log10f(p) : p;
+    }
+    return;
+  }
+  if (e.kind == EPI_CAC) {
+    const unsigned long long i = (unsigned long long)o - e.k0;  // (wraps to huge when below k0)
+    if (i < e.cnt) {
+      const float p = x.x * x.x + x.y * x.y, v = e.log_scale ? 10.0f * log10f(p) : p;
+      e.out[i] = v;
+      if (i - e.amax_lo < e.amax_cnt) { const unsigned long long k = argmax_key(v, (unsigned)(i - e.amax_lo)); best = k > best ? k : best; }
     }
     return;
   }

@@ -49,10 +49,12 @@ static int ws64(tsdr_ctx *ctx, size_t n, double2 **X, double2 **T) {
   return (*X && *T) ? (int)TSDR_OK : (int)TSDR_ENOMEM;
 }
 
-static int autocorr64_core(tsdr_ctx *ctx, const double *x, size_t n, size_t k0, size_t cnt, int log_scale, double *out) {
+// is_complex: x is ComplexF64 and the lags are those of the complex sequence itself (autocorr_cplx.hip) -- the loader copies
+// instead of widening; everything behind it is complex already
+int autocorr64_core(tsdr_ctx *ctx, const double *x, size_t n, size_t k0, size_t cnt, int log_scale, double *out, int is_complex = 0) {
   double2 *X, *T;
   if (int rc = ws64(ctx, n, &X, &T)) return rc;
-  TSDR_LAUNCH(ctx, "autocorr_f64_load", k_load64, dim3(stream_grid(ctx, n)), dim3(256), 0, x, 0, n, X);
+  TSDR_LAUNCH(ctx, "autocorr_f64_load", k_load64, dim3(stream_grid(ctx, n)), dim3(256), 0, x, is_complex, n, X);
   if (int rc = fft64_d(ctx, X, T, n, -1)) return rc;
   TSDR_LAUNCH(ctx, "autocorr_f64_power", k_pow64, dim3(stream_grid(ctx, n)), dim3(256), 0, X, n);
   if (int rc = fft64_d(ctx, X, T, n, +1)) return rc;

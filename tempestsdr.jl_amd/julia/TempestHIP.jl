@@ -696,5 +696,7 @@ end
 # Integer IQ through the device-pointer `_iq_d` entry points (include/tempest_hip_iq.h): amDemod / invert_amDemod of
 # Complex{Int16} / Complex{Int8} / Complex{UInt8} vectors, hip_welch_d / hip_waterfall_d of a raw ring slot
 include("TempestHIP_iq.jl")
+# calculate_autocorrelation of ComplexF32 / ComplexF64 / integer IQ vectors (include/tempest_hip_cplx.h)
+include("TempestHIP_cplx.jl")
 
 end # module

@@ -16,11 +16,26 @@ import numpy as np
 from . import video_configurations as vc
 
 
-def extract_configuration(ctx, iq, Fs, delay_rate=0.1, rate_min=50, rate_max=90, *, iq_fmt=None, iq_scale=1.0, n_samples=None):
+def extract_configuration(ctx, iq, Fs, delay_rate=0.1, rate_min=50, rate_max=90, *, iq_fmt=None, iq_scale=1.0, n_samples=None,
+                          domain="power"):
     """-> (rates_refresh, G_refresh, fv, G) with the reference's conventions (incl. the zoom off-by-one).
     iq_fmt "sc16" / "sc8" / "uc8": iq is integer IQ as a raw staging ring holds it -- an integer array of 2*n interleaved
     components, or the device address StagingRing.take_d returned with n_samples = n -- read as it is stored by the search's
-    first pass (Context.autocorr_search); nothing is expanded."""
+    first pass (Context.autocorr_search); nothing is expanded.
+    domain "power" (default): the autocorrelation of abs2.(IQ), GUI.jl:70-73.  "complex": the coherent autocorrelation of the
+    IQ samples themselves (calculate_autocorrelation called on sigRx; Context.autocorr_search_complex) on the same samples."""
+    if domain not in ("power", "complex"):
+        raise AssertionError(f"domain must be 'power' or 'complex' (got {domain!r})")
+    if domain == "complex":
+        dev = isinstance(iq, (int, np.integer)) and not isinstance(iq, bool)
+        n = (int(n_samples) if n_samples is not None else 0) if dev else np.asarray(iq).size // (1 if iq_fmt is None else 2)
+        if n < int(np.round(delay_rate * Fs)):
+            raise IndexError("capture shorter than the autocorrelation window (BoundsError in the reference)")
+        G, _, _ = ctx.autocorr_search_complex(iq, Fs, 0, delay_rate, rate_min=rate_min, rate_max=rate_max, iq_fmt=iq_fmt,
+                                              iq_scale=iq_scale, n_samples=n_samples)
+        rates, Gz = ctx.zoom_autocorr(G, Fs, rate_min=rate_min, rate_max=rate_max)
+        pos = int(np.argmax(Gz))
+        return rates, Gz, 1.0 / (1.0 / rates[pos]), G
     if iq_fmt is not None:
         dev = isinstance(iq, (int, np.integer)) and not isinstance(iq, bool)
         n = int(n_samples) if dev and n_samples is not None else (0 if dev else np.asarray(iq).size // 2)
