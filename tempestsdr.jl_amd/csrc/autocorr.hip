@@ -27,7 +27,7 @@ int get_tw(tsdr_ctx *ctx, int logN, TwTable **out);
 
 __device__ inline float2 cmulf(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
 
-// is_iq: 0 = x is real f32; 1 + TSDR_IQ_* = x is IQ of that format (1: ComplexF32, 2: sc16, 3: sc8, 4: uc8), whose abs2 is the
+// is_iq: fft_dev.h's SigKind -- 0 = x is real f32; 1 + TSDR_IQ_* = x is IQ of that format (1: ComplexF32, 2: sc16, 3: sc8, 4: uc8), whose abs2 is the
 // sample -- integer storage converted as the frame loaders do (common.h: ld_iq, one product by `scale`)
 __device__ inline float ld_power(const float *x, int is_iq, size_t i, float scale) {
   if (is_iq == 1) {
@@ -42,9 +42,6 @@ __device__ inline float ld_power(const float *x, int is_iq, size_t i, float scal
     return abs2_c(z.x, z.y);
   }
   return x[i];
-}
-inline int iq_src_mode(int is_iq) {   // the first pass's loader for that input
-  return is_iq == 0 ? SRC_REAL : is_iq == 1 ? SRC_IQPOW : is_iq == 2 ? SRC_IQPOW_SC16 : is_iq == 3 ? SRC_IQPOW_SC8 : SRC_IQPOW_UC8;
 }
 
 // z[j] = x[2j] + i x[2j+1], zero beyond n; Mc complex outputs
@@ -200,8 +197,11 @@ __global__ __launch_bounds__(64) void k_amax_publish(unsigned long long *__restr
 static inline double jl_round(double v) { return nearbyint(v); }  // Julia round(): ties to even
 
 // shared core: x (real f32, or IQ whose abs2 is taken on the fly), first n samples
-static int autocorr_core(tsdr_ctx *ctx, const float *x, int is_iq, size_t n, size_t k0, size_t cnt, int log_scale,
-                         float *out, AmaxReq *amax = nullptr, float iq_scale = 1.0f) {
+static int autocorr_core(tsdr_ctx *ctx, const SigSrc &sig, size_t n, size_t k0, size_t cnt, int log_scale, float *out,
+                         AmaxReq *amax = nullptr) {
+  const float *x = sig.f32();
+  const int is_iq = sig.kind, src_mode = srcpow_of(sig.kind);   // (the first pass's loader for that input)
+  const float iq_scale = sig.scale;
   // n = 2*Mc with Mc = 2^a 3^b 5^c (the usual case: decimal sample rates, or a power of two): the circular
   // correlation of length n is transformed natively -- no zero padding, no fold, half the bytes (or less) of the
   // padded route below, which remains for every other n.
@@ -209,7 +209,6 @@ static int autocorr_core(tsdr_ctx *ctx, const float *x, int is_iq, size_t n, siz
   const bool mixed_on = ctx->opt_ac_mixed != 0;
   if ((n & 1) == 0 && n > 1024 && (half_pow2 || (mixed_on && fft_mixed_ok(n / 2))) &&
       (!is_iq || (reinterpret_cast<uintptr_t>(x) & 15u) == 0)) {
-    const int src_mode = iq_src_mode(is_iq);
     const size_t Mc = n / 2;
     float2 *z = (float2 *)ctx->scratch(WS_FFT_A, Mc * sizeof(float2));
     float2 *Z = (float2 *)ctx->scratch(WS_FFT_C, Mc * sizeof(float2));
@@ -261,7 +260,7 @@ static int autocorr_core(tsdr_ctx *ctx, const float *x, int is_iq, size_t n, siz
   // the fly when asked -- and never reads the zero padding; no separate pack pass, no 33 MB round trip
   const bool aligned = !is_iq || (reinterpret_cast<uintptr_t>(x) & 15u) == 0;  // the IQ loader reads float4 pairs
   if (logM - 1 > 8 && aligned) {
-    rc = fft_pow2(ctx, reinterpret_cast<const float2 *>(x), Z, logM - 1, 1, -1, 1.0f, iq_src_mode(is_iq), n, 0, nullptr, nullptr, iq_scale);
+    rc = fft_pow2(ctx, reinterpret_cast<const float2 *>(x), Z, logM - 1, 1, -1, 1.0f, src_mode, n, 0, nullptr, nullptr, iq_scale);
   } else {
     TSDR_LAUNCH(ctx, "ac_pack", k_ac_pack, dim3(stream_grid(ctx, Mc)), dim3(256), 0, x, is_iq, n, Mc, z, iq_scale);
     rc = fft_pow2(ctx, z, Z, logM - 1, 1, -1, 1.0f, SRC_C2C, 0, 0);
@@ -312,7 +311,7 @@ static int autocorr_any_d(tsdr_ctx *ctx, const float *x, int is_iq, size_t len, 
   if (rc) return rc;
   if (n_out) *n_out = cnt;
   if (cnt == 0) return TSDR_OK;
-  return autocorr_core(ctx, x, is_iq, n, k0, cnt, log_scale, out);
+  return autocorr_core(ctx, sig_f32(x, is_iq), n, k0, cnt, log_scale, out);
 }
 
 int tsdr_autocorr_d(tsdr_ctx *ctx, const float *x, size_t len, double Fs, double minDelay, double maxDelay, int log_scale,
@@ -334,7 +333,7 @@ int tsdr_autocorr(tsdr_ctx *ctx, const float *x, size_t len, double Fs, double m
   if (n_out) *n_out = cnt;
   if (cnt == 0) return TSDR_OK;
   return host_map(ctx, x, n * 4, out, cnt * 4,
-                  [&](void *i, void *o) { return autocorr_core(ctx, (const float *)i, 0, n, k0, cnt, log_scale, (float *)o); });
+                  [&](void *i, void *o) { return autocorr_core(ctx, sig_f32((const float *)i, 0), n, k0, cnt, log_scale, (float *)o); });
 }
 
 int tsdr_autocorr_partial_d(tsdr_ctx *ctx, const float *x, int is_iq, size_t n, size_t m0, size_t cnt, size_t n_lags,
@@ -470,13 +469,13 @@ int tsdr_argmax_d(tsdr_ctx *ctx, const float *v, size_t n, size_t *idx, float *v
   return amax_wait(ctx, r.seq, idx, val);
 }
 
-// is_iq as ld_power takes it (0, or 1 + TSDR_IQ_*)
-static int autocorr_search_any_d(tsdr_ctx *ctx, const float *x, int is_iq, float iq_scale, size_t len, double Fs, double minDelay,
+static int autocorr_search_any_d(tsdr_ctx *ctx, const SigSrc &sig, size_t len, double Fs, double minDelay,
                                  double maxDelay, int log_scale, float *out, size_t *n_out, size_t win_lo, size_t win_cnt, size_t *idx,
                                  float *val) {
+  const float *x = sig.f32();
   if (!ctx || !x || !out || !idx) return TSDR_EINVAL;
-  // (integer IQ: is_iq >= 2, its 16-byte rule is the caller's, tsdr_autocorr_search_iq_d)
-  TSDR_PTR_ALIGNED(ctx, "autocorr_search", x, is_iq == 1 ? 8 : 4);
+  // (integer IQ: its 16-byte rule is the caller's, tsdr_autocorr_search_iq_d)
+  TSDR_PTR_ALIGNED(ctx, "autocorr_search", x, sig.kind == SIG_CF32 ? 8 : 4);
   TSDR_PTR_ALIGNED(ctx, "autocorr_search", out, 4);
   size_t n, k0, cnt;
   int rc = autocorr_args(ctx, len, Fs, minDelay, maxDelay, &n, &k0, &cnt);
@@ -490,7 +489,7 @@ static int autocorr_search_any_d(tsdr_ctx *ctx, const float *x, int is_iq, float
   r.lo = win_lo;
   r.cnt = win_cnt;
   ctx->amax_dirty = true;   // until the publish launch (or the route without an epilogue) is known to have been enqueued
-  rc = autocorr_core(ctx, x, is_iq, n, k0, cnt, log_scale, out, &r, iq_scale);
+  rc = autocorr_core(ctx, sig, n, k0, cnt, log_scale, out, &r);
   if (rc) return rc;
   if (!r.fused) {  // routes whose last pass has no epilogue: the separate kernel
     ctx->amax_dirty = false;
@@ -506,7 +505,7 @@ static int autocorr_search_any_d(tsdr_ctx *ctx, const float *x, int is_iq, float
 
 int tsdr_autocorr_search_d(tsdr_ctx *ctx, const float *x, int is_iq, size_t len, double Fs, double minDelay, double maxDelay,
                            int log_scale, float *out, size_t *n_out, size_t win_lo, size_t win_cnt, size_t *idx, float *val) {
-  return autocorr_search_any_d(ctx, x, is_iq ? 1 : 0, 1.0f, len, Fs, minDelay, maxDelay, log_scale, out, n_out, win_lo, win_cnt, idx, val);
+  return autocorr_search_any_d(ctx, sig_f32(x, is_iq), len, Fs, minDelay, maxDelay, log_scale, out, n_out, win_lo, win_cnt, idx, val);
 }
 
 int tsdr_autocorr_search_iq_d(tsdr_ctx *ctx, const void *iq, int iq_fmt, float scale, size_t len, double Fs, double minDelay,
@@ -517,8 +516,8 @@ int tsdr_autocorr_search_iq_d(tsdr_ctx *ctx, const void *iq, int iq_fmt, float s
   // the first pass loads two samples at a time; one rule for every format: the base a ring slot or hipMalloc hands out
   if (iq_fmt != TSDR_IQ_CF32 && (reinterpret_cast<uintptr_t>(iq) & 15u)) return set_err(ctx, TSDR_EINVAL, "autocorr_search_iq: integer IQ needs a 16-byte aligned buffer");
   if (iq_fmt == TSDR_IQ_CF32 && (reinterpret_cast<uintptr_t>(iq) & 7u)) return set_err(ctx, TSDR_EINVAL, "autocorr_search_iq: the buffer is not aligned to one sample");
-  return autocorr_search_any_d(ctx, reinterpret_cast<const float *>(iq), 1 + iq_fmt, iq_fmt == TSDR_IQ_CF32 ? 1.0f : scale, len, Fs, minDelay,
-                               maxDelay, log_scale, out, n_out, win_lo, win_cnt, idx, val);
+  return autocorr_search_any_d(ctx, sig_iq(iq, IqFmt{iq_fmt, iq_fmt == TSDR_IQ_CF32 ? 1.0f : scale}), len, Fs, minDelay, maxDelay, log_scale, out,
+                               n_out, win_lo, win_cnt, idx, val);
 }
 
 }  // extern "C"

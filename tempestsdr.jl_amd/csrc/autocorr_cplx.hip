@@ -16,8 +16,6 @@
 
 namespace tsdr {
 
-int fft_any(tsdr_ctx *ctx, const float *x, int is_complex, float2 *out, size_t n, size_t batch, int dir);
-int fft_any_iq(tsdr_ctx *ctx, const void *iq, const IqFmt &f, float2 *out, size_t n, size_t batch);   // fft.hip
 int autocorr_args(tsdr_ctx *ctx, size_t len, double Fs, double minDelay, double maxDelay, size_t *n, size_t *k0, size_t *cnt);
 int autocorr64_core(tsdr_ctx *ctx, const double *x, size_t n, size_t k0, size_t cnt, int log_scale, double *out, int is_complex);
 
@@ -44,18 +42,15 @@ static bool cac_native(tsdr_ctx *ctx, size_t n) {
   return fft_passes(n) >= 2 && (is_pow2(n) || ctx->opt_ac_mixed != 0);
 }
 
-// shared core: the first n samples of z in format f (1 <= n < 2^31, cnt >= 1, k0 + cnt <= n)
-static int autocorr_cplx_core(tsdr_ctx *ctx, const void *z, const IqFmt &f, size_t n, size_t k0, size_t cnt, int log_scale,
-                              float *out, AmaxReq *amax = nullptr) {
-  const bool intq = f.kind != IQK_CF32;
+// shared core: the first n samples of z, ComplexF32 or integer IQ (1 <= n < 2^31, cnt >= 1, k0 + cnt <= n)
+static int autocorr_cplx_core(tsdr_ctx *ctx, const SigSrc &z, size_t n, size_t k0, size_t cnt, int log_scale, float *out,
+                              AmaxReq *amax = nullptr) {
   float2 *X = (float2 *)ctx->scratch(WS_FFT_A, n * sizeof(float2));
   if (!X) return TSDR_ENOMEM;
   if (cac_native(ctx, n)) {
     const bool p2 = is_pow2(n);
-    const float2 *x = reinterpret_cast<const float2 *>(z);
-    const int sm = intq ? src_of_iq(f) : SRC_C2C;
-    int rc = p2 ? fft_pow2(ctx, x, X, ilog2(n), 1, -1, 1.0f, sm, 0, 0, nullptr, nullptr, f.scale)
-                : fft_mixed(ctx, x, X, n, 1, -1, 1.0f, sm, 0, 0, nullptr, nullptr, f.scale);
+    int rc = p2 ? fft_pow2(ctx, z.c32(), X, ilog2(n), 1, -1, 1.0f, src_of(z.kind), 0, 0, nullptr, nullptr, z.scale)
+                : fft_mixed(ctx, z.c32(), X, n, 1, -1, 1.0f, src_of(z.kind), 0, 0, nullptr, nullptr, z.scale);
     if (rc) return rc;
     FftEpilogue epi;
     epi.kind = EPI_CAC;
@@ -72,11 +67,11 @@ static int autocorr_cplx_core(tsdr_ctx *ctx, const void *z, const IqFmt &f, size
     return p2 ? fft_pow2(ctx, X, X, ilog2(n), 1, +1, inv_n, SRC_ABS2, 0, k0 + cnt, &epi)
               : fft_mixed(ctx, X, X, n, 1, +1, inv_n, SRC_ABS2, 0, k0 + cnt, &epi);
   }
-  // (one-launch and Bluestein lengths: integer samples are expanded into the workspace first, fft_any_iq)
-  int rc = intq ? fft_any_iq(ctx, z, f, X, n, 1) : fft_any(ctx, reinterpret_cast<const float *>(z), 1, X, n, 1, -1);
+  // (one-launch and Bluestein lengths: integer samples are expanded into the workspace first, fft_any)
+  int rc = fft_any(ctx, z, X, n, 1, -1);
   if (rc) return rc;
   TSDR_LAUNCH(ctx, "cac_power", k_cac_power, dim3(stream_grid(ctx, n)), dim3(256), 0, X, n);
-  rc = fft_any(ctx, reinterpret_cast<const float *>(X), 1, X, n, 1, +1);
+  rc = fft_any(ctx, SigSrc{X, SIG_CF32, 1.0f}, X, n, 1, +1);
   if (rc) return rc;
   TSDR_LAUNCH(ctx, "cac_finish", k_cac_finish, dim3(stream_grid(ctx, cnt)), dim3(256), 0, (const float2 *)X, k0, cnt, log_scale, out);
   return TSDR_OK;
@@ -108,7 +103,7 @@ int tsdr_autocorr_cplx_search_iq_d(tsdr_ctx *ctx, const void *iq, int iq_fmt, fl
   size_t n, k0, cnt;
   int rc = cac_args(ctx, len, Fs, minDelay, maxDelay, &n, &k0, &cnt, n_out);
   if (rc) return rc;
-  if (win_cnt == 0) return cnt ? autocorr_cplx_core(ctx, iq, f, n, k0, cnt, log_scale, out) : (int)TSDR_OK;
+  if (win_cnt == 0) return cnt ? autocorr_cplx_core(ctx, sig_iq(iq, f), n, k0, cnt, log_scale, out) : (int)TSDR_OK;
   if (win_lo >= cnt || win_cnt > cnt - win_lo) return set_err(ctx, TSDR_EBOUNDS, "autocorr_cplx_search: window outside the lag vector");
   if (win_cnt >= (size_t(1) << 32)) return set_err(ctx, TSDR_EINVAL, "argmax: vector too long");
   AmaxReq r;
@@ -117,7 +112,7 @@ int tsdr_autocorr_cplx_search_iq_d(tsdr_ctx *ctx, const void *iq, int iq_fmt, fl
   r.lo = win_lo;
   r.cnt = win_cnt;
   ctx->amax_dirty = true;   // until the publish launch (or the route without an epilogue) is known to have been enqueued
-  rc = autocorr_cplx_core(ctx, iq, f, n, k0, cnt, log_scale, out, &r);
+  rc = autocorr_cplx_core(ctx, sig_iq(iq, f), n, k0, cnt, log_scale, out, &r);
   if (rc) return rc;
   if (!r.fused) {  // the routes around fft_any: the separate kernel
     ctx->amax_dirty = false;
@@ -139,19 +134,19 @@ int tsdr_autocorr_cplx_d(tsdr_ctx *ctx, const float *z, size_t len, double Fs, d
   size_t n, k0, cnt;
   int rc = cac_args(ctx, len, Fs, minDelay, maxDelay, &n, &k0, &cnt, n_out);
   if (rc || cnt == 0) return rc;
-  return autocorr_cplx_core(ctx, z, IqFmt{}, n, k0, cnt, log_scale, out);
+  return autocorr_cplx_core(ctx, sig_f32(z, 1), n, k0, cnt, log_scale, out);
 }
 
 int tsdr_autocorr_cplx_iq(tsdr_ctx *ctx, const void *iq, int iq_fmt, float scale, size_t len, double Fs, double minDelay,
                           double maxDelay, int log_scale, float *out, size_t *n_out) {
   if (!ctx || !iq || !out) return TSDR_EINVAL;
-  if (iq_fmt < TSDR_IQ_CF32 || iq_fmt > TSDR_IQ_UC8) return set_err(ctx, TSDR_EINVAL, "autocorr_cplx_iq: iq_fmt %d is not a TSDR_IQ_* format", iq_fmt);
-  const IqFmt f{iq_fmt, iq_fmt == TSDR_IQ_CF32 ? 1.0f : scale};
+  TSDR_IQ_FMT_ARG(ctx, "autocorr_cplx_iq", iq_fmt);
+  SigSrc z = sig_iq(iq, IqFmt{iq_fmt, iq_fmt == TSDR_IQ_CF32 ? 1.0f : scale});
   size_t n, k0, cnt;
   int rc = cac_args(ctx, len, Fs, minDelay, maxDelay, &n, &k0, &cnt, n_out);
   if (rc || cnt == 0) return rc;
-  return host_map(ctx, iq, n * iq_bytes(f), out, cnt * 4,   // the raw bytes go up, not expanded ones
-                  [&](void *i, void *o) { return autocorr_cplx_core(ctx, i, f, n, k0, cnt, log_scale, (float *)o); });
+  return host_map(ctx, iq, n * z.bytes(), out, cnt * 4,   // the raw bytes go up, not expanded ones
+                  [&](void *i, void *o) { z.p = i; return autocorr_cplx_core(ctx, z, n, k0, cnt, log_scale, (float *)o); });
 }
 
 int tsdr_autocorr_cplx(tsdr_ctx *ctx, const float *z, size_t len, double Fs, double minDelay, double maxDelay, int log_scale,

@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <map>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/tempest_hip.h"
@@ -253,11 +254,16 @@ void prof_end(tsdr_ctx *ctx);
 static inline size_t ceil_div(size_t a, size_t b) { return (a + b - 1) / b; }
 
 // The `iq, iq_fmt, scale` arguments of the *_iq_d entry points (tempest_hip.h, TSDR_IQ_*): a known format, the pointer aligned
-// to one sample of it (8 / 4 / 2 bytes) -- else TSDR_EINVAL with the argument's name, before anything is enqueued.
-#define TSDR_IQ_ARG(ctx, fn, iq, iq_fmt, scale, f)                                                                          \
+// to one sample of it (8 / 4 / 2 bytes) -- else TSDR_EINVAL with the argument's name, before anything is enqueued.  (The host-pointer
+// forms check the format alone: TSDR_IQ_FMT_ARG.)
+#define TSDR_IQ_FMT_ARG(ctx, fn, iq_fmt)                                                                                    \
   do {                                                                                                                       \
     if ((iq_fmt) < TSDR_IQ_CF32 || (iq_fmt) > TSDR_IQ_UC8)                                                                    \
       return tsdr::set_err((ctx), TSDR_EINVAL, "%s: iq_fmt %d is not a TSDR_IQ_* format", fn, (int)(iq_fmt));                \
+  } while (0)
+#define TSDR_IQ_ARG(ctx, fn, iq, iq_fmt, scale, f)                                                                          \
+  do {                                                                                                                       \
+    TSDR_IQ_FMT_ARG(ctx, fn, iq_fmt);                                                                                        \
     (f) = tsdr::IqFmt{(iq_fmt), (iq_fmt) == TSDR_IQ_CF32 ? 1.0f : (scale)};                                                  \
     if (reinterpret_cast<uintptr_t>(iq) % tsdr::iq_bytes(f))                                                                 \
       return tsdr::set_err((ctx), TSDR_EINVAL, "%s: iq is not aligned to one sample of its format (%d bytes)", fn, (int)tsdr::iq_bytes(f)); \
@@ -362,6 +368,24 @@ __device__ inline float2 ld_iq(const float *__restrict__ src, unsigned k, const 
 // register allocation and instruction stream must not pay for the other formats) or read from the launch's parameters
 // (IQF_RT: every other reader)
 enum { IQF_CF32 = 0, IQF_SC16 = 1, IQF_RT = 2, IQF_SC8 = 3, IQF_UC8 = 4 };
+// the compile-time twin of a run-time format (IqFmt::kind), and the one place a launch site of the per-function paths goes from
+// the one to the other: fn(std::integral_constant<int, IQF_*>{}) is called for the integer format `iqf` holds (IQF_SC16 / _SC8 /
+// _UC8: the kernels with a format argument there exist for those only)
+constexpr int iqf_of(int iqk) { return iqk == IQK_SC16 ? IQF_SC16 : iqk == IQK_SC8 ? IQF_SC8 : iqk == IQK_UC8 ? IQF_UC8 : IQF_CF32; }
+template <typename F>
+inline int with_int_iqf(int iqf, F &&fn) {
+  if (iqf == IQF_SC16) return fn(std::integral_constant<int, IQF_SC16>{});
+  if (iqf == IQF_SC8) return fn(std::integral_constant<int, IQF_SC8>{});
+  return fn(std::integral_constant<int, IQF_UC8>{});
+}
+enum { IQN_SC16 = 0, IQN_SC8 = 1, IQN_UC8 = 2 };   // index of an integer format's launch name in a {"..._sc16", "..._sc8", "..._uc8"} table
+constexpr int iqf_name(int iqf) { return iqf == IQF_SC16 ? IQN_SC16 : iqf == IQF_SC8 ? IQN_SC8 : IQN_UC8; }
+// one integer sample's bits (I in the low half: 32 bits of sc16, 16 of the 8-bit formats) -> ComplexF32
+template <int IQF>
+__device__ inline float2 cvt_iq(unsigned w, float scale) {
+  if (IQF == IQF_SC16) return cvt_sc16(make_short2((short)(w & 0xFFFFu), (short)(w >> 16)), scale);
+  return IQF == IQF_SC8 ? cvt_sc8(w, scale) : cvt_uc8(w, scale);
+}
 template <int IQF>
 __device__ inline float2 ld_iq_as(const float *__restrict__ src, unsigned k, const IqFmt &f) {
   if (IQF == IQF_CF32) return reinterpret_cast<const float2 *>(src)[k];

@@ -100,12 +100,6 @@ __global__ __launch_bounds__(256) void k_fm(const float2 *__restrict__ iq, size_
 // A sample is converted by common.h's cvt_* (one product by `scale`), then goes through demod1 / the FM product exactly as a
 // ComplexF32 sample does, so the outputs are those of the expanded buffer bit for bit.  One 16-byte load is 4 sc16 samples (one
 // float4 out) or 8 eight-bit samples (two float4 out).
-template <int IQF>
-__device__ inline float2 iq_word(unsigned w, float scale) {   // w: one sample's bits, I in the low half
-  if (IQF == IQF_SC16) return cvt_sc16(make_short2((short)(w & 0xFFFFu), (short)(w >> 16)), scale);
-  return IQF == IQF_SC8 ? cvt_sc8(w & 0xFFFFu, scale) : cvt_uc8(w & 0xFFFFu, scale);
-}
-
 template <int MODE, bool TRACK_MAX, int IQF>
 __global__ __launch_bounds__(256) void k_demod_iq(const uint4 *__restrict__ iq, size_t n, float scale, float4 *__restrict__ out,
                                                   unsigned *__restrict__ maxbits) {
@@ -120,10 +114,10 @@ __global__ __launch_bounds__(256) void k_demod_iq(const uint4 *__restrict__ iq, 
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       if (SPV == 4) {
-        const float2 a = iq_word<IQF>(w[k], scale);
+        const float2 a = cvt_iq<IQF>(w[k], scale);
         r[k] = demod1<MODE>(a.x, a.y);
       } else {
-        const float2 a = iq_word<IQF>(w[k] & 0xFFFFu, scale), b = iq_word<IQF>(w[k] >> 16, scale);
+        const float2 a = cvt_iq<IQF>(w[k] & 0xFFFFu, scale), b = cvt_iq<IQF>(w[k] >> 16, scale);
         r[2 * k] = demod1<MODE>(a.x, a.y);
         r[2 * k + 1] = demod1<MODE>(b.x, b.y);
       }
@@ -182,15 +176,6 @@ __global__ __launch_bounds__(256) void k_fm_iq(const void *__restrict__ iq, size
   }
 }
 
-#define TSDR_COMMA ,
-// launch KER<..., IQF> for the integer format of f (a macro: the kernel name carries other template arguments)
-#define TSDR_LAUNCH_IQF(ctx, kname, f, KER, grid, ...)                                                                  \
-  do {                                                                                                                  \
-    if ((f).kind == IQK_SC16) TSDR_LAUNCH(ctx, kname "_sc16", (KER IQF_SC16>), grid, dim3(256), 0, __VA_ARGS__);         \
-    else if ((f).kind == IQK_SC8) TSDR_LAUNCH(ctx, kname "_sc8", (KER IQF_SC8>), grid, dim3(256), 0, __VA_ARGS__);       \
-    else TSDR_LAUNCH(ctx, kname "_uc8", (KER IQF_UC8>), grid, dim3(256), 0, __VA_ARGS__);                                \
-  } while (0)
-
 // k_demod moves 16-byte vectors on both sides; any other element-aligned pair of pointers takes k_demod1
 static inline bool vec16(const float *iq, const float *out) {
   return ((reinterpret_cast<uintptr_t>(iq) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0;
@@ -215,15 +200,16 @@ static int demod_d(tsdr_ctx *ctx, const char *kname, const float *iq, size_t n, 
 // am_demod / abs2 / invert_am's first launch on integer IQ: 16-byte vectors where both pointers allow, one sample per lane else
 template <int MODE, bool TRACK_MAX>
 static int demod_iq_launch(tsdr_ctx *ctx, const void *iq, const IqFmt &f, size_t n, float *out, unsigned *mx) {
-  if (vec16(reinterpret_cast<const float *>(iq), out)) {
-    const dim3 grid(stream_grid(ctx, ceil_div(n, f.kind == IQK_SC16 ? 4 : 8)));
-    TSDR_LAUNCH_IQF(ctx, "demod_iq", f, k_demod_iq<MODE TSDR_COMMA TRACK_MAX TSDR_COMMA, grid, reinterpret_cast<const uint4 *>(iq), n, f.scale,
-                    reinterpret_cast<float4 *>(out), mx);
-  } else {
-    const dim3 grid(stream_grid(ctx, n));
-    TSDR_LAUNCH_IQF(ctx, "demod1_iq", f, k_demod1_iq<MODE TSDR_COMMA TRACK_MAX TSDR_COMMA, grid, iq, n, f.scale, out, mx);
-  }
-  return TSDR_OK;
+  static const char *const kVec[3] = {"demod_iq_sc16", "demod_iq_sc8", "demod_iq_uc8"}, *const kOne[3] = {"demod1_iq_sc16", "demod1_iq_sc8", "demod1_iq_uc8"};
+  return with_int_iqf(iqf_of(f.kind), [&](auto iqf) -> int {
+    if (vec16(reinterpret_cast<const float *>(iq), out)) {
+      TSDR_LAUNCH(ctx, kVec[iqf_name(iqf)], (k_demod_iq<MODE, TRACK_MAX, iqf>), dim3(stream_grid(ctx, ceil_div(n, iqf == IQF_SC16 ? 4 : 8))), dim3(256), 0,
+                  reinterpret_cast<const uint4 *>(iq), n, f.scale, reinterpret_cast<float4 *>(out), mx);
+    } else {
+      TSDR_LAUNCH(ctx, kOne[iqf_name(iqf)], (k_demod1_iq<MODE, TRACK_MAX, iqf>), dim3(stream_grid(ctx, n)), dim3(256), 0, iq, n, f.scale, out, mx);
+    }
+    return TSDR_OK;
+  });
 }
 
 template <int MODE>
@@ -301,8 +287,11 @@ int tsdr_fm_demod_iq_d(tsdr_ctx *ctx, const void *iq, int iq_fmt, float scale, s
   TSDR_PTR_ALIGNED(ctx, "fm_demod_iq", out, 4);
   if (iq_fmt == TSDR_IQ_CF32) return tsdr_fm_demod_d(ctx, reinterpret_cast<const float *>(iq), n, out);
   if (n == 0) return TSDR_OK;
-  TSDR_LAUNCH_IQF(ctx, "fm_demod_iq", f, k_fm_iq<, dim3(stream_grid(ctx, n)), iq, n, f.scale, out);
-  return TSDR_OK;
+  static const char *const kName[3] = {"fm_demod_iq_sc16", "fm_demod_iq_sc8", "fm_demod_iq_uc8"};
+  return with_int_iqf(iqf_of(f.kind), [&](auto iqf) -> int {
+    TSDR_LAUNCH(ctx, kName[iqf_name(iqf)], (k_fm_iq<iqf>), dim3(stream_grid(ctx, n)), dim3(256), 0, iq, n, f.scale, out);
+    return TSDR_OK;
+  });
 }
 
 int tsdr_am_demod(tsdr_ctx *ctx, const float *iq, size_t n, float *out) {

@@ -513,34 +513,48 @@ static int get_bluestein(tsdr_ctx *ctx, size_t n, BluesteinPlan **out) {
   return TSDR_OK;
 }
 
-// General-length FFT of `batch` contiguous transforms.  x: real (is_complex=0) or interleaved
-// complex; out: complex.  Uses WS_FFT_B (pow2 engine), WS_FFT_C, WS_FFT_D.
-int fft_any(tsdr_ctx *ctx, const float *x, int is_complex, float2 *out, size_t n, size_t batch, int dir) {
+// Integer samples enter a transform through a loader: the whole-row kernels' (fft_rows_store, tried first) or the first pass's
+// of a multi-pass transform.  This is the second: does (n, batch) run two or more passes on the engine that takes it?  Where
+// neither exists -- one-launch lengths, Bluestein, and 1024-point rows (k_seg1024's row form reads ComplexF32) -- the samples
+// are expanded into WS_IQX first.
+static bool first_pass_loads(tsdr_ctx *ctx, size_t n, size_t batch) {
+  if (is_pow2(n)) return ilog2(n) > 8;
+  return fft_mixed_ok(n) && fft_mixed_passes(ctx, n, batch) >= 2;
+}
+
+// General-length FFT of `batch` contiguous transforms.  x: real f32, interleaved complex, or integer IQ as stored (forward only),
+// on the route its length takes whatever the kind; out: complex.  Uses WS_FFT_B (pow2 engine), WS_FFT_C, WS_FFT_D, WS_IQX.
+int fft_any(tsdr_ctx *ctx, SigSrc x, float2 *out, size_t n, size_t batch, int dir) {
   if (n == 0 || batch == 0) return TSDR_OK;
   const int d = dir < 0 ? -1 : 1;
-  if (is_complex && batch > 1) {  // rows of 257 .. 4096 points: one launch, on chip
-    if (n == 1024) return fft_rows1024(ctx, reinterpret_cast<const float2 *>(x), out, batch, d, d > 0 ? (float)(1.0 / 1024.0) : 1.0f);
+  if (x.is_int() && d > 0) return set_err(ctx, TSDR_EINVAL, "fft: integer samples take the forward transform only");
+  const float scale = d > 0 ? (float)(1.0 / (double)n) : 1.0f;
+  auto expand = [&]() -> int {
+    float2 *e = (float2 *)ctx->scratch(WS_IQX, n * batch * sizeof(float2));
+    if (!e) return TSDR_ENOMEM;
+    int rc = iq_expand(ctx, x.p, x.iq(), n * batch, e);
+    x = SigSrc{e, SIG_CF32, 1.0f};
+    return rc;
+  };
+  if (x.kind != SIG_REAL && batch > 1) {  // rows of 257 .. 4096 points: one launch, on chip
+    if (n == 1024) {
+      if (x.is_int()) { if (int rc = expand()) return rc; }
+      return fft_rows1024(ctx, x.c32(), out, batch, d, scale);
+    }
     bool did = false;
-    int rcr = fft_rows_store(ctx, reinterpret_cast<const float2 *>(x), out, n, batch, d, d > 0 ? (float)(1.0 / (double)n) : 1.0f, &did);
+    int rcr = fft_rows_store(ctx, x, out, n, batch, d, scale, &did);
     if (rcr || did) return rcr;
   }
-  if (is_pow2(n)) {
-    const float scale = d > 0 ? (float)(1.0 / (double)n) : 1.0f;
-    const float2 *src = reinterpret_cast<const float2 *>(x);
-    if (!is_complex) {
-      TSDR_LAUNCH(ctx, "r2c", k_r2c, dim3(stream_grid(ctx, n * batch)), dim3(256), 0, x, n * batch, out);
+  if (x.is_int() && !first_pass_loads(ctx, n, batch)) { if (int rc = expand()) return rc; }
+  if (is_pow2(n) || fft_mixed_ok(n)) {  // 2^a 3^b 5^c: native mixed-radix passes (fft_mixed.hip)
+    const float2 *src = x.c32();
+    if (x.kind == SIG_REAL) {
+      TSDR_LAUNCH(ctx, "r2c", k_r2c, dim3(stream_grid(ctx, n * batch)), dim3(256), 0, x.f32(), n * batch, out);
       src = out;
     }
-    return fft_pow2(ctx, src, out, ilog2(n), batch, d, scale, SRC_C2C, 0, 0);
-  }
-  if (fft_mixed_ok(n)) {  // 2^a 3^b 5^c: native mixed-radix passes (fft_mixed.hip)
-    const float scale = d > 0 ? (float)(1.0 / (double)n) : 1.0f;
-    const float2 *src = reinterpret_cast<const float2 *>(x);
-    if (!is_complex) {
-      TSDR_LAUNCH(ctx, "r2c", k_r2c, dim3(stream_grid(ctx, n * batch)), dim3(256), 0, x, n * batch, out);
-      src = out;
-    }
-    return fft_mixed(ctx, src, out, n, batch, d, scale, SRC_C2C, 0, 0);
+    const int sm = x.is_int() ? src_of(x.kind) : SRC_C2C;
+    return is_pow2(n) ? fft_pow2(ctx, src, out, ilog2(n), batch, d, scale, sm, 0, 0, nullptr, nullptr, x.scale)
+                      : fft_mixed(ctx, src, out, n, batch, d, scale, sm, 0, 0, nullptr, nullptr, x.scale);
   }
   BluesteinPlan *pl = nullptr;
   int rc = get_bluestein(ctx, n, &pl);
@@ -550,7 +564,7 @@ int fft_any(tsdr_ctx *ctx, const float *x, int is_complex, float2 *out, size_t n
   float2 *a2 = (float2 *)ctx->scratch(WS_FFT_D, L * batch * sizeof(float2));
   if (!a || !a2) return TSDR_ENOMEM;
   const int inv = d > 0;
-  TSDR_LAUNCH(ctx, "blu_pre", k_blu_pre, dim3(stream_grid(ctx, L * batch)), dim3(256), 0, x, is_complex, inv, n, L, batch,
+  TSDR_LAUNCH(ctx, "blu_pre", k_blu_pre, dim3(stream_grid(ctx, L * batch)), dim3(256), 0, x.f32(), (int)(x.kind != SIG_REAL), inv, n, L, batch,
               (const float2 *)pl->chirp, a);
   rc = fft_pow2(ctx, a, a2, ilog2(L), batch, -1, 1.0f, SRC_C2C, 0, 0);
   if (rc) return rc;
@@ -558,32 +572,9 @@ int fft_any(tsdr_ctx *ctx, const float *x, int is_complex, float2 *out, size_t n
               batch);
   rc = fft_pow2(ctx, a2, a, ilog2(L), batch, +1, (float)(1.0 / (double)L), SRC_C2C, 0, 0);
   if (rc) return rc;
-  const float scale = inv ? (float)(1.0 / (double)n) : 1.0f;
   TSDR_LAUNCH(ctx, "blu_post", k_blu_post, dim3(stream_grid(ctx, n * batch)), dim3(256), 0, (const float2 *)a, n, L, batch,
               (const float2 *)pl->chirp, inv, scale, out);
   return TSDR_OK;
-}
-
-// Forward transforms of `batch` rows of n integer IQ samples (format f, not IQK_CF32) on the route ComplexF32 input takes in
-// fft_any: the whole-row kernel's or the first pass's loader converts; the lengths without a loader hook (one-launch lengths,
-// Bluestein; 1024-point rows, which getWelch / getWaterfall never bring here) expand into WS_IQX and run fft_any itself.
-int fft_any_iq(tsdr_ctx *ctx, const void *iq, const IqFmt &f, float2 *out, size_t n, size_t batch) {
-  if (n == 0 || batch == 0) return TSDR_OK;
-  const float2 *x = reinterpret_cast<const float2 *>(iq);
-  bool expand = batch > 1 && n == 1024;
-  if (!expand && batch > 1) {
-    bool did = false;
-    int rcr = fft_rows_store(ctx, x, out, n, batch, -1, 1.0f, &did, &f);
-    if (rcr || did) return rcr;
-  }
-  if (!expand && is_pow2(n) && ilog2(n) > 8) return fft_pow2(ctx, x, out, ilog2(n), batch, -1, 1.0f, src_of_iq(f), 0, 0, nullptr, nullptr, f.scale);
-  if (!expand && !is_pow2(n) && fft_mixed_ok(n) && fft_mixed_passes(ctx, n, batch) >= 2)
-    return fft_mixed(ctx, x, out, n, batch, -1, 1.0f, src_of_iq(f), 0, 0, nullptr, nullptr, f.scale);
-  float2 *e = (float2 *)ctx->scratch(WS_IQX, n * batch * sizeof(float2));
-  if (!e) return TSDR_ENOMEM;
-  int rc = iq_expand(ctx, iq, f, n * batch, e);
-  if (rc) return rc;
-  return fft_any(ctx, reinterpret_cast<const float *>(e), 1, out, n, batch, -1);
 }
 
 }  // namespace tsdr
@@ -596,7 +587,7 @@ int tsdr_fft_c2c_d(tsdr_ctx *ctx, const float *in, float *out, size_t n, size_t 
   if (!ctx || ((n * batch) && (!in || !out))) return TSDR_EINVAL;
   TSDR_PTR_ALIGNED(ctx, "fft_c2c", in, 8);
   TSDR_PTR_ALIGNED(ctx, "fft_c2c", out, 8);
-  return fft_any(ctx, in, 1, reinterpret_cast<float2 *>(out), n, batch, dir);
+  return fft_any(ctx, sig_f32(in, 1), reinterpret_cast<float2 *>(out), n, batch, dir);
 }
 
 int tsdr_fft_c2c(tsdr_ctx *ctx, const float *in, float *out, size_t n, size_t batch, int dir) {

@@ -169,7 +169,35 @@ enum { SRC_C2C = 0, SRC_REAL = 1, SRC_IQPOW = 2, SRC_POWER = 3, SRC_STUFF = 4, S
        SRC_IQ_SC16 = 10, SRC_IQ_SC8 = 11, SRC_IQ_UC8 = 12, SRC_ABS2 = 13 };
 inline bool src_is_int_iq(int src_mode) { return src_mode >= SRC_IQPOW_SC16 && src_mode <= SRC_IQ_UC8; }
 inline bool src_is_cplx_int(int src_mode) { return src_mode >= SRC_IQ_SC16 && src_mode <= SRC_IQ_UC8; }
-inline int src_of_iq(const IqFmt &f) { return f.kind == IQK_SC16 ? SRC_IQ_SC16 : f.kind == IQK_SC8 ? SRC_IQ_SC8 : f.kind == IQK_UC8 ? SRC_IQ_UC8 : SRC_C2C; }
+
+// What the per-function host paths (spectra, tsdr_fft_c2c, autocorrelations) are handed: a pointer, what kind of samples it points
+// to and, for integer IQ, their factor.  The IQ kinds are 1 + TSDR_IQ_*; k_ac_pack / k_pc_pack (autocorr.hip) take the kind as a
+// kernel argument.  Every other encoding of "which samples" -- loader modes, row-kernel modes, template arguments -- is a function
+// of the kind, below and in common.h (iqf_of), each pinned value by value.
+enum SigKind { SIG_REAL = 0, SIG_CF32 = 1, SIG_SC16 = 2, SIG_SC8 = 3, SIG_UC8 = 4 };
+struct SigSrc {
+  const void *p; int kind; float scale;
+  bool is_int() const { return kind >= SIG_SC16; }
+  size_t bytes() const { return kind == SIG_CF32 ? 8 : kind == SIG_SC8 || kind == SIG_UC8 ? 2 : 4; }   // per element
+  IqFmt iq() const { return IqFmt{is_int() ? kind - SIG_CF32 : IQK_CF32, scale}; }
+  const float *f32() const { return reinterpret_cast<const float *>(p); }
+  const float2 *c32() const { return reinterpret_cast<const float2 *>(p); }
+};
+inline SigSrc sig_f32(const float *x, int is_complex) { return SigSrc{x, is_complex ? SIG_CF32 : SIG_REAL, 1.0f}; }
+inline SigSrc sig_iq(const void *iq, const IqFmt &f) { return SigSrc{iq, SIG_CF32 + f.kind, f.scale}; }
+static_assert(SIG_CF32 == 1 + IQK_CF32 && SIG_SC16 == 1 + IQK_SC16 && SIG_SC8 == 1 + IQK_SC8 && SIG_UC8 == 1 + IQK_UC8, "IQ kinds are 1 + TSDR_IQ_*");
+
+// element-wise loader of a first pass: in[g] of that kind as a complex value
+constexpr int src_of(int kind) { return kind == SIG_REAL ? SRC_RE0 : kind == SIG_CF32 ? SRC_C2C : SRC_IQ_SC16 + (kind - SIG_SC16); }
+static_assert(src_of(SIG_REAL) == 6 && src_of(SIG_CF32) == 0 && src_of(SIG_SC16) == 10 && src_of(SIG_SC8) == 11 && src_of(SIG_UC8) == 12, "SRC_RE0 / SRC_C2C / SRC_IQ_*");
+// packing loader of the real autocorrelation: two samples (or two abs2 of IQ samples) per complex value
+constexpr int srcpow_of(int kind) { return kind == SIG_REAL ? SRC_REAL : kind == SIG_CF32 ? SRC_IQPOW : SRC_IQPOW_SC16 + (kind - SIG_SC16); }
+static_assert(srcpow_of(SIG_REAL) == 1 && srcpow_of(SIG_CF32) == 2 && srcpow_of(SIG_SC16) == 7 && srcpow_of(SIG_SC8) == 8 && srcpow_of(SIG_UC8) == 9, "SRC_REAL / SRC_IQPOW*");
+// MixDesc::rows_real of the whole-row kernels (fft_mixed.hip): the integer kinds keep their SigKind value
+enum { ROWS_CF32 = 0, ROWS_REAL = 1, ROWS_SC16 = 2, ROWS_SC8 = 3, ROWS_UC8 = 4 };
+constexpr int rows_of(int kind) { return kind == SIG_REAL ? ROWS_REAL : kind == SIG_CF32 ? ROWS_CF32 : kind; }
+static_assert(rows_of(SIG_REAL) == 1 && rows_of(SIG_CF32) == 0 && rows_of(SIG_SC16) == 2 && rows_of(SIG_SC8) == 3 && rows_of(SIG_UC8) == 4, "ROWS_*");
+static_assert(iqf_of(IQK_CF32) == 0 && iqf_of(IQK_SC16) == 1 && iqf_of(IQK_SC8) == 3 && iqf_of(IQK_UC8) == 4 && IQF_RT == 2, "IQF_*");
 
 // inv_m8 is the loader's one f64 parameter: 8/M for SRC_POWER with M not a power of two, the f32 scale for integer IQ, else 0
 // tw_frac below (needed by the SRC_POWER loader when M = 2*Mc is not a power of two)
@@ -234,13 +262,13 @@ __device__ inline float2 fft_load(const float2 *__restrict__ in, int src_mode, u
   return make_float2(abs2_c(a.x, a.y), i0 + 1 < src_n ? abs2_c(b.x, b.y) : 0.f);
 }
 
-// one element of a whole-row kernel's input (MixDesc::rows_real): 0 ComplexF32, 1 real f32, 2 + IQK_* integer IQ (the scale in
-// MixDesc::src_w8).  `e` is the element's index from the buffer's start.
-enum { ROWS_CF32 = 0, ROWS_REAL = 1, ROWS_IQ = 1 };   // integer IQ of kind k: ROWS_IQ + k (k = IQK_SC16 ..)
+// one element of a whole-row kernel's integer IQ input (MixDesc::rows_real = ROWS_SC16 / _SC8 / _UC8, the scale in MixDesc::src_w8).
+// `e` is the element's index from the buffer's start.  (The twin of fft_load's SRC_IQ_* branch: folded into one run-time loader
+// the compiler emits other code for the pass kernels, so the two stay.)
 __device__ inline float2 rows_load_int(const float2 *__restrict__ in, int rows_real, size_t e, float scale) {
-  if (rows_real == ROWS_IQ + IQK_SC16) return cvt_sc16(reinterpret_cast<const short2 *>(in)[e], scale);
+  if (rows_real == ROWS_SC16) return cvt_sc16(reinterpret_cast<const short2 *>(in)[e], scale);
   const unsigned v = reinterpret_cast<const unsigned short *>(in)[e];
-  return rows_real == ROWS_IQ + IQK_SC8 ? cvt_sc8(v, scale) : cvt_uc8(v, scale);
+  return rows_real == ROWS_SC8 ? cvt_sc8(v, scale) : cvt_uc8(v, scale);
 }
 
 // exp(-2*pi*i*e/N) for any N: inv_n8 = 8/N in f64, 0 <= e < N.  The phase e/N is formed in f64 (relative error
@@ -351,14 +379,15 @@ int fft_mixed(tsdr_ctx *ctx, const float2 *in, float2 *out, size_t N, size_t bat
 int fft_mixed_autocorr(tsdr_ctx *ctx, const float2 *x, int src_mode, size_t src_n, size_t Mc, float2 *Zbuf, float2 *zbuf,
                        float scale, size_t keep, const FftEpilogue *epi, bool *done, float src_scale = 1.0f);
 unsigned fft_rows_welch_parts(tsdr_ctx *ctx);
-// (iq != nullptr: the rows are integer IQ of that format, read by the row loader itself; is_complex is then 1)
-int fft_rows_welch(tsdr_ctx *ctx, const float *sig, int is_complex, size_t N, size_t nbSeg, float *part, unsigned *nparts, bool *did,
-                   const IqFmt *iq = nullptr);
+// whole-row kernels (fft_mixed.hip): the rows are read as stored, whatever their kind (fft_rows_store: not real ones)
+int fft_rows_welch(tsdr_ctx *ctx, const SigSrc &sig, size_t N, size_t nbSeg, float *part, unsigned *nparts, bool *did);
+int fft_rows_store(tsdr_ctx *ctx, const SigSrc &in, float2 *out, size_t N, size_t batch, int dir, float scale, bool *did);
+int fft_rows_waterfall(tsdr_ctx *ctx, const SigSrc &sig, size_t N, size_t nbSeg, double *wf, bool *did);
 int fft_rows1024(tsdr_ctx *ctx, const float2 *in, float2 *out, size_t batch, int dir, float scale);   // spectrum.hip
-int fft_rows_store(tsdr_ctx *ctx, const float2 *in, float2 *out, size_t N, size_t batch, int dir, float scale, bool *did,
-                   const IqFmt *iq = nullptr);
-int fft_rows_waterfall(tsdr_ctx *ctx, const float *sig, int is_complex, size_t N, size_t nbSeg, double *wf, bool *did,
-                       const IqFmt *iq = nullptr);
+// fft.hip: `batch` contiguous transforms of any length n from any kind of samples (integer IQ: forward only)
+int fft_any(tsdr_ctx *ctx, SigSrc x, float2 *out, size_t n, size_t batch, int dir);
+int fft64_d(tsdr_ctx *ctx, double2 *data, double2 *scratch, size_t N, int dir);   // fft64.hip
+int resampler_init_kind(tsdr_ctx *ctx, size_t bufferSize, int upCoeff, bool f64, tsdr_resampler **out);   // spectrum.hip
 int fft_mixed_passes(tsdr_ctx *ctx, size_t N, size_t batch);   // passes fft_mixed takes for `batch` transforms of N points (0: not its length)
 bool fft_mixed_ok(size_t N);
 int fft_passes(size_t N);

@@ -53,7 +53,7 @@ struct MixDesc {
   // rows mode as getWelch's accumulator (GetSpectrum.jl:36-52): nothing is stored per transform; every workgroup walks
   // tiles blockIdx.x, blockIdx.x + gridDim.x, ... of `rows` segments, adds abs2 of every spectrum it forms in registers and
   // leaves ONE partial power spectrum, acc[blockIdx.x * R + k] (natural frequency order).  rows_real: the rows are real f32
-  // (1) or integer IQ (fft_dev.h:ROWS_IQ + kind, converted by the row loader with the scale in src_w8).
+  // (1) or integer IQ (fft_dev.h:ROWS_*, converted by the row loader with the scale in src_w8).
   float *acc;
   int rows_real;
   // ... or getWaterfall's writer (GetSpectrum.jl:54-66; three-step kernels only): Float64(abs2) of every spectrum straight from
@@ -878,7 +878,7 @@ struct Mix3Geom {
 // tile, walked by persistent workgroups (separate instantiations: as run-time branches of one kernel the row store's conjugations
 // and the writers' extra live values cost the accumulator 15-60 %)
 enum { M3_ACC = 10, M3_WF = 11, M3_ROWS = 12,     // getWelch's accumulator | getWaterfall's writer | batched row transforms
-       M3_ACC_IQ = 13, M3_WF_IQ = 14, M3_ROWS_IQ = 15 };   // the same three on integer IQ rows (MixDesc::rows_real = ROWS_IQ + kind): instantiations
+       M3_ACC_IQ = 13, M3_WF_IQ = 14, M3_ROWS_IQ = 15 };   // the same three on integer IQ rows (MixDesc::rows_real = ROWS_SC16 ..): instantiations
                                                            // of their own, so that the ComplexF32 / real ones keep their registers and occupancy
 template <int RA, int RB, int RC, int LOGT, int MODE>
 __global__ __launch_bounds__((Mix3Geom<RA, RB, RC, LOGT>::NT)) void k_fft_mix3(const float2 *__restrict__ in, float2 *__restrict__ out, MixDesc d) {
@@ -1630,8 +1630,7 @@ static int fft_mixed_ex(tsdr_ctx *ctx, const float2 *in, float2 *out, size_t N, 
 // getWelch's accumulation for any 2^a 3^b 5^c segment length up to 4096 without writing a segment spectrum: *nparts partial
 // power spectra of N floats each (natural order) land in `part` (room for fft_rows_welch_parts() of them)
 unsigned fft_rows_welch_parts(tsdr_ctx *ctx) { return (unsigned)(ctx->cu_count > 0 ? ctx->cu_count : 256) * 3u; }
-int fft_rows_welch(tsdr_ctx *ctx, const float *sig, int is_complex, size_t N, size_t nbSeg, float *part, unsigned *nparts, bool *did,
-                   const IqFmt *iq) {
+int fft_rows_welch(tsdr_ctx *ctx, const SigSrc &sig, size_t N, size_t nbSeg, float *part, unsigned *nparts, bool *did) {
   *did = false;
   if (N < 2 || N > 4096 || nbSeg == 0 || nbSeg >= (size_t(1) << 31)) return TSDR_OK;
   // the whole segment as ONE factor of the generic LDS-stage kernel (the pass planner caps factors at 256 / 2000: its costs
@@ -1658,8 +1657,8 @@ int fft_rows_welch(tsdr_ctx *ctx, const float *sig, int is_complex, size_t N, si
   d.logT = floor_log2(4096u / d.R);
   d.rows = (unsigned)nbSeg;
   d.acc = part;
-  d.rows_real = is_complex ? 0 : 1;
-  if (iq && iq->kind != IQK_CF32) { d.rows_real = ROWS_IQ + iq->kind; d.src_w8 = (double)iq->scale; }
+  d.rows_real = rows_of(sig.kind);
+  if (sig.is_int()) d.src_w8 = (double)sig.scale;
   if (const Mix3Entry *m3 = ctx->opt_fft_no_mix2 ? nullptr : welch3_lookup(d.R, true)) {
     // 500 / 1000 / 2000 (and 256 / 512 / 2048 / 4096 / 4000): the three-register-step kernel, 8 (4, 2, 1) segments per workgroup
     int rc3 = mix3_prepare(ctx, m3);
@@ -1672,7 +1671,7 @@ int fft_rows_welch(tsdr_ctx *ctx, const float *sig, int is_complex, size_t N, si
     // workgroups on a CU)
     const unsigned per_cu3 = (unsigned)std::max<size_t>(1, std::min<size_t>(3, (size_t)(160 * 1024) / m3->lds));
     const unsigned grid3 = std::min({ntiles3, (unsigned)(ctx->cu_count > 0 ? ctx->cu_count : 256) * per_cu3, fft_rows_welch_parts(ctx)});
-    TSDR_LAUNCH(ctx, "welch_rows_acc3", d.rows_real > ROWS_REAL ? m3->acc_iq : m3->acc, dim3(grid3), dim3(m3->nt), m3->lds, reinterpret_cast<const float2 *>(sig), (float2 *)nullptr, d);
+    TSDR_LAUNCH(ctx, "welch_rows_acc3", d.rows_real > ROWS_REAL ? m3->acc_iq : m3->acc, dim3(grid3), dim3(m3->nt), m3->lds, sig.c32(), (float2 *)nullptr, d);
     *nparts = grid3;
     *did = true;
     return TSDR_OK;
@@ -1685,7 +1684,7 @@ int fft_rows_welch(tsdr_ctx *ctx, const float *sig, int is_complex, size_t N, si
   const unsigned ntiles = (unsigned)ceil_div(nbSeg, (size_t)1 << d.logT);
   const unsigned per_cu = (unsigned)std::max<size_t>(1, std::min<size_t>(3, (size_t)(150 * 1024) / lds));
   const unsigned grid = std::min(ntiles, (unsigned)(ctx->cu_count > 0 ? ctx->cu_count : 256) * per_cu);
-  TSDR_LAUNCH(ctx, "welch_rows_acc", k_fft_mix, dim3(grid), dim3(256), lds, reinterpret_cast<const float2 *>(sig), (float2 *)nullptr, d);
+  TSDR_LAUNCH(ctx, "welch_rows_acc", k_fft_mix, dim3(grid), dim3(256), lds, sig.c32(), (float2 *)nullptr, d);
   *nparts = grid;
   *did = true;
   return TSDR_OK;
@@ -1694,7 +1693,7 @@ int fft_rows_welch(tsdr_ctx *ctx, const float *sig, int is_complex, size_t N, si
 // Batched row transforms (tsdr_fft_c2c with batch > 1) of the lengths the three-step kernels serve, in ONE launch: a row never
 // leaves the chip between its steps.  (The pass engines split a 512 .. 4096-point row into two passes whose strided one has only
 // 16-64 columns to work on: 67-197 us for 1e7 points against 35-50 us here; rows up to 256 points are one pass there already.)
-int fft_rows_store(tsdr_ctx *ctx, const float2 *in, float2 *out, size_t N, size_t batch, int dir, float scale, bool *did, const IqFmt *iq) {
+int fft_rows_store(tsdr_ctx *ctx, const SigSrc &in, float2 *out, size_t N, size_t batch, int dir, float scale, bool *did) {
   *did = false;
   if (N <= 256 || N > 4096 || batch < 2 || batch >= (size_t(1) << 31) || ctx->opt_fft_no_mix2) return TSDR_OK;
   const Mix3Entry *m3 = welch3_lookup((unsigned)N, false);
@@ -1708,13 +1707,14 @@ int fft_rows_store(tsdr_ctx *ctx, const float2 *in, float2 *out, size_t N, size_
   d.logT = m3->logT;
   d.rows = (unsigned)batch;
   d.rows_out = out;
-  if (iq && iq->kind != IQK_CF32) { d.rows_real = ROWS_IQ + iq->kind; d.src_w8 = (double)iq->scale; }   // (forward only: no conjugation on the way in)
+  d.rows_real = rows_of(in.kind);
+  if (in.is_int()) d.src_w8 = (double)in.scale;   // (forward only: no conjugation on the way in)
   int rc = mix3_prepare(ctx, m3);
   if (rc) return rc;
   const unsigned ntiles = (unsigned)ceil_div(batch, (size_t)1 << d.logT);
   const unsigned per_cu = (unsigned)std::max<size_t>(1, std::min<size_t>(3, (size_t)(160 * 1024) / m3->lds));
   const unsigned grid = std::min(ntiles, (unsigned)(ctx->cu_count > 0 ? ctx->cu_count : 256) * per_cu);
-  TSDR_LAUNCH(ctx, "fft_rows3", d.rows_real > ROWS_REAL ? m3->rows_iq : m3->rows, dim3(grid), dim3(m3->nt), m3->lds, in, (float2 *)nullptr, d);
+  TSDR_LAUNCH(ctx, "fft_rows3", d.rows_real > ROWS_REAL ? m3->rows_iq : m3->rows, dim3(grid), dim3(m3->nt), m3->lds, in.c32(), (float2 *)nullptr, d);
   *did = true;
   return TSDR_OK;
 }
@@ -1722,7 +1722,7 @@ int fft_rows_store(tsdr_ctx *ctx, const float2 *in, float2 *out, size_t N, size_
 // getWaterfall for the segment lengths the three-step kernels serve (1024 has k_seg1024): segments -> Float64 power spectra,
 // fftshifted, in ONE launch -- the segment spectra never reach HBM (the route through a batched FFT + k_waterfall writes and
 // re-reads them: 109-250 us per C2 buffer at 512 .. 4096 against 40-60 us here)
-int fft_rows_waterfall(tsdr_ctx *ctx, const float *sig, int is_complex, size_t N, size_t nbSeg, double *wf, bool *did, const IqFmt *iq) {
+int fft_rows_waterfall(tsdr_ctx *ctx, const SigSrc &sig, size_t N, size_t nbSeg, double *wf, bool *did) {
   *did = false;
   if (N < 2 || N > 4096 || nbSeg == 0 || nbSeg >= (size_t(1) << 31) || ctx->opt_fft_no_mix2) return TSDR_OK;
   const Mix3Entry *m3 = welch3_lookup((unsigned)N, false);
@@ -1736,14 +1736,14 @@ int fft_rows_waterfall(tsdr_ctx *ctx, const float *sig, int is_complex, size_t N
   d.logT = m3->logT;
   d.rows = (unsigned)nbSeg;
   d.wf = wf;
-  d.rows_real = is_complex ? 0 : 1;
-  if (iq && iq->kind != IQK_CF32) { d.rows_real = ROWS_IQ + iq->kind; d.src_w8 = (double)iq->scale; }
+  d.rows_real = rows_of(sig.kind);
+  if (sig.is_int()) d.src_w8 = (double)sig.scale;
   int rc = mix3_prepare(ctx, m3);
   if (rc) return rc;
   const unsigned ntiles = (unsigned)ceil_div(nbSeg, (size_t)1 << d.logT);
   const unsigned per_cu = (unsigned)std::max<size_t>(1, (size_t)(160 * 1024) / m3->lds);
   const unsigned grid = std::min(ntiles, (unsigned)(ctx->cu_count > 0 ? ctx->cu_count : 256) * per_cu);
-  TSDR_LAUNCH(ctx, "waterfall_rows3", d.rows_real > ROWS_REAL ? m3->wf_iq : m3->wf, dim3(grid), dim3(m3->nt), m3->lds, reinterpret_cast<const float2 *>(sig), (float2 *)nullptr, d);
+  TSDR_LAUNCH(ctx, "waterfall_rows3", d.rows_real > ROWS_REAL ? m3->wf_iq : m3->wf, dim3(grid), dim3(m3->nt), m3->lds, sig.c32(), (float2 *)nullptr, d);
   *did = true;
   return TSDR_OK;
 }

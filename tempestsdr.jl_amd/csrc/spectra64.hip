@@ -19,13 +19,11 @@
 #include <cmath>
 #include <vector>
 
-#include "common.h"
+#include "fft_dev.h"
 #include "resampler_state.h"
 
 namespace tsdr {
 
-int fft64_d(tsdr_ctx *ctx, double2 *data, double2 *scratch, size_t N, int dir);
-int resampler_init_kind(tsdr_ctx *ctx, size_t bufferSize, int upCoeff, bool f64, tsdr_resampler **out);
 
 constexpr int kT64 = 256;          // threads of every workgroup here
 constexpr int kTile64 = 4096;      // complex f64 values one workgroup holds in LDS at most (64 KiB)

@@ -11,11 +11,6 @@
 
 namespace tsdr {
 
-int fft64_d(tsdr_ctx *ctx, double2 *data, double2 *scratch, size_t N, int dir);
-
-int fft_any(tsdr_ctx *ctx, const float *x, int is_complex, float2 *out, size_t n, size_t batch, int dir);
-int fft_any_iq(tsdr_ctx *ctx, const void *iq, const IqFmt &f, float2 *out, size_t n, size_t batch);   // fft.hip
-
 // fftshift: output j takes input (j + ceil(N/2)) mod N
 __device__ inline size_t shift_src(size_t j, size_t N) {
   size_t s = j + (N - N / 2);
@@ -122,11 +117,6 @@ constexpr bool kSegPrefetch = true;
 // prefetched segment (16 VGPRs instead of 32) and converts them when the segment's turn comes: the same f32 values the
 // expansion kernels write, then the ComplexF32 instantiation's arithmetic.  A wave-instruction still reads one contiguous run
 // (256 B of sc16, 128 B of 8-bit samples).  The ComplexF32 / real instantiations are untouched by the parameter.
-template <int IQF>
-__device__ inline float2 seg_cvt(unsigned w, float scale) {
-  if (IQF == IQF_SC16) return cvt_sc16(make_short2((short)(w & 0xFFFFu), (short)(w >> 16)), scale);
-  return IQF == IQF_SC8 ? cvt_sc8(w, scale) : cvt_uc8(w, scale);
-}
 enum { SEG_WELCH = 0, SEG_WATERFALL = 1, SEG_ROWS = 2 };
 template <int KIND, bool CPLX, int IQF = IQF_CF32>
 __global__ __launch_bounds__(64 * kSegWaves, kSegOcc) void k_seg1024(const float *__restrict__ sig, size_t nbSeg,
@@ -182,7 +172,7 @@ __global__ __launch_bounds__(64 * kSegWaves, kSegOcc) void k_seg1024(const float
     float2 v[16];
     if (!kSegPrefetch) fetch(seg);
 #pragma unroll
-    for (int m = 0; m < 16; ++m) v[m] = INTQ ? seg_cvt<IQF>(nraw[INTQ ? m : 0], scale) : KIND == SEG_ROWS ? conj_if(nx[INTQ ? 0 : m], smask) : nx[INTQ ? 0 : m];
+    for (int m = 0; m < 16; ++m) v[m] = INTQ ? cvt_iq<IQF>(nraw[INTQ ? m : 0], scale) : KIND == SEG_ROWS ? conj_if(nx[INTQ ? 0 : m], smask) : nx[INTQ ? 0 : m];
     if (kSegPrefetch && seg + 1 < seg1) fetch(seg + 1);
     reg_dft<16>(v);
 #pragma unroll
@@ -459,10 +449,11 @@ __global__ __launch_bounds__(256) void k_resample4096(const float *__restrict__ 
   for (int m = 0; m < 16; ++m) out[tid + 256 * m] = gain * (v[m].x * inv);  // real(conj(.)) = real(.): ifft scale, then 2*up
 }
 
-// f: the samples' format when they are integer IQ (is_complex = 1), else IQK_CF32
-static int spectrum_d(tsdr_ctx *ctx, const float *sig, int is_complex, size_t N, int lin, float *y, const IqFmt &f = IqFmt{}) {
+// ---- host code ----------------------------------------------------------------------------------------------------------------
+// Every branch below is taken on the lengths alone: a kind of samples (SigSrc: real f32, ComplexF32, integer IQ as stored) takes the
+// route ComplexF32 takes, and is converted by that route's loader.
+static int spectrum_d(tsdr_ctx *ctx, const SigSrc &sig, size_t N, int lin, float *y) {
   if (N == 0) return TSDR_OK;
-  const bool intq = f.kind != IQK_CF32;
   // (Round 5, built and dropped: ONE launch for short signals -- N = R1 * R2, workgroup k1 forms sum_n1 x[R2 n1 + n2] W_R1^(n1 k1)
   // by direct summation and runs one R2-point LDS transform: no second pass, no grid barrier.  Correct on every size tried, and
   // 41-56 us at N = 80 000 against the two passes' 14.9: the work per THREAD is N / 1024 terms whatever R1 is (grid = R1), and
@@ -470,7 +461,7 @@ static int spectrum_d(tsdr_ctx *ctx, const float *sig, int is_complex, size_t N,
   float2 *X = (float2 *)ctx->scratch(WS_FFT_A, N * sizeof(float2));
   if (!X) return TSDR_ENOMEM;
   if (fft_passes(N) >= 2) {
-    // the passes alone: a real signal enters through the first pass's loader, abs2 / 10log10 and the fftshift leave
+    // the passes alone: the samples enter through the first pass's loader, abs2 / 10log10 and the fftshift leave
     // through the last pass's epilogue
     FftEpilogue epi;
     epi.kind = EPI_SPEC;
@@ -478,60 +469,23 @@ static int spectrum_d(tsdr_ctx *ctx, const float *sig, int is_complex, size_t N,
     epi.cnt = N;
     epi.k0 = N / 2;
     epi.log_scale = !lin;
-    const float2 *x = reinterpret_cast<const float2 *>(sig);
-    const int sm = intq ? src_of_iq(f) : is_complex ? SRC_C2C : SRC_RE0;
-    return is_pow2(N) ? fft_pow2(ctx, x, X, ilog2(N), 1, -1, 1.0f, sm, 0, 0, &epi, nullptr, f.scale)
-                      : fft_mixed(ctx, x, X, N, 1, -1, 1.0f, sm, 0, 0, &epi, nullptr, f.scale);
+    return is_pow2(N) ? fft_pow2(ctx, sig.c32(), X, ilog2(N), 1, -1, 1.0f, src_of(sig.kind), 0, 0, &epi, nullptr, sig.scale)
+                      : fft_mixed(ctx, sig.c32(), X, N, 1, -1, 1.0f, src_of(sig.kind), 0, 0, &epi, nullptr, sig.scale);
   }
-  // (one-launch and Bluestein lengths: integer samples are expanded into the workspace first, fft_any_iq)
-  int rc = intq ? fft_any_iq(ctx, sig, f, X, N, 1) : fft_any(ctx, sig, is_complex, X, N, 1, -1);
+  // (one-launch and Bluestein lengths: integer samples are expanded into the workspace first, fft_any)
+  int rc = fft_any(ctx, sig, X, N, 1, -1);
   if (rc) return rc;
   TSDR_LAUNCH(ctx, "spectrum_out", k_spec_out, dim3(stream_grid(ctx, N)), dim3(256), 0, (const float2 *)X, N, lin, y);
   return TSDR_OK;
 }
 
-static int segments_fft(tsdr_ctx *ctx, const float *sig, int is_complex, size_t len, size_t sizeFFT, float2 **X,
-                        size_t *nbSeg, const IqFmt &f = IqFmt{}) {
+static int segments_fft(tsdr_ctx *ctx, const SigSrc &sig, size_t len, size_t sizeFFT, float2 **X, size_t *nbSeg) {
   if (sizeFFT == 0) return set_err(ctx, TSDR_EINVAL, "sizeFFT must be positive");
   *nbSeg = len / sizeFFT;
   *X = (float2 *)ctx->scratch(WS_FFT_A, (*nbSeg ? *nbSeg : 1) * sizeFFT * sizeof(float2));
   if (!*X) return TSDR_ENOMEM;
   if (*nbSeg == 0) return TSDR_OK;
-  if (f.kind != IQK_CF32) return fft_any_iq(ctx, sig, f, *X, sizeFFT, *nbSeg);
-  return fft_any(ctx, sig, is_complex, *X, sizeFFT, *nbSeg, -1);
-}
-
-}  // namespace tsdr
-
-using namespace tsdr;
-
-extern "C" {
-
-int tsdr_spectrum_d(tsdr_ctx *ctx, const float *sig, int is_complex, size_t N, int lin, float *y) {
-  if (!ctx || (N && (!sig || !y))) return TSDR_EINVAL;
-  TSDR_PTR_ALIGNED(ctx, "spectrum", sig, is_complex ? 8 : 4);
-  TSDR_PTR_ALIGNED(ctx, "spectrum", y, 4);
-  return spectrum_d(ctx, sig, is_complex, N, lin, y);
-}
-
-int tsdr_spectrum_iq_d(tsdr_ctx *ctx, const void *iq, int iq_fmt, float scale, size_t N, int lin, float *y) {
-  if (!ctx || (N && (!iq || !y))) return TSDR_EINVAL;
-  IqFmt f;
-  TSDR_IQ_ARG(ctx, "spectrum_iq", iq, iq_fmt, scale, f);
-  TSDR_PTR_ALIGNED(ctx, "spectrum_iq", y, 4);
-  return spectrum_d(ctx, reinterpret_cast<const float *>(iq), 1, N, lin, y, f);
-}
-
-int tsdr_spectrum_iq(tsdr_ctx *ctx, const void *iq, int iq_fmt, float scale, size_t N, int lin, float *y) {
-  if (!ctx) return TSDR_EINVAL;
-  if (iq_fmt < TSDR_IQ_CF32 || iq_fmt > TSDR_IQ_UC8) return set_err(ctx, TSDR_EINVAL, "spectrum_iq: iq_fmt %d is not a TSDR_IQ_* format", iq_fmt);
-  return host_map(ctx, iq, N * iq_bytes(IqFmt{iq_fmt, scale}), y, N * 4,
-                  [&](void *i, void *o) { return tsdr_spectrum_iq_d(ctx, i, iq_fmt, scale, N, lin, (float *)o); });
-}
-
-int tsdr_spectrum(tsdr_ctx *ctx, const float *sig, int is_complex, size_t N, int lin, float *y) {
-  return host_map(ctx, sig, N * (is_complex ? 8 : 4), y, N * 4,
-                  [&](void *i, void *o) { return spectrum_d(ctx, (const float *)i, is_complex, N, lin, (float *)o); });
+  return fft_any(ctx, sig, *X, sizeFFT, *nbSeg, -1);
 }
 
 // wavefronts of the 1024-point fast path: one per segment while they all fit the device at once (three 4-wavefront
@@ -544,8 +498,6 @@ static unsigned seg_waves(tsdr_ctx *ctx, size_t nbSeg, unsigned *blocks) {
   return nwaves;
 }
 
-}  // extern "C"
-namespace tsdr {
 // batched 1024-point row transforms on the wavefront-per-segment kernel (fft.hip:fft_any): 1e7 points in 30 us
 int fft_rows1024(tsdr_ctx *ctx, const float2 *in, float2 *out, size_t batch, int dir, float scale) {
   if (batch == 0) return TSDR_OK;
@@ -556,32 +508,38 @@ int fft_rows1024(tsdr_ctx *ctx, const float2 *in, float2 *out, size_t batch, int
               nwaves, (float *)nullptr, (double *)nullptr, out, dir > 0 ? 0x80000000u : 0u, scale);
   return TSDR_OK;
 }
-}  // namespace tsdr
-extern "C" {
 
-}  // extern "C"
-// getWelch on checked arguments.  f: the samples' format when they are integer IQ (is_complex = 1), else IQK_CF32; every branch
-// below is taken on (len, sizeFFT) alone, so a format takes the route ComplexF32 takes.
-static int welch_d(tsdr_ctx *ctx, const float *sig, int is_complex, const IqFmt &f, size_t len, size_t sizeFFT, int lin, float *y) {
-  const bool intq = f.kind != IQK_CF32;
+// getWelch's (part) / getWaterfall's (wf) k_seg1024 launch for the kind of samples `sig` holds
+template <int KIND>
+static int seg1024_launch(tsdr_ctx *ctx, const SigSrc &sig, size_t nbSeg, unsigned nwaves, unsigned blocks, float *part, double *wf) {
+  static const char *const kName = KIND == SEG_WELCH ? "welch_seg1024" : "waterfall_seg1024";
+  static const char *const kIntName[3] = {KIND == SEG_WELCH ? "welch_seg1024_sc16" : "waterfall_seg1024_sc16",
+                                          KIND == SEG_WELCH ? "welch_seg1024_sc8" : "waterfall_seg1024_sc8",
+                                          KIND == SEG_WELCH ? "welch_seg1024_uc8" : "waterfall_seg1024_uc8"};
+  const dim3 g(blocks), b(64 * kSegWaves);
+  if (sig.kind == SIG_REAL) {
+    TSDR_LAUNCH(ctx, kName, (k_seg1024<KIND, false>), g, b, 0, sig.f32(), nbSeg, nwaves, part, wf);
+  } else if (sig.kind == SIG_CF32) {
+    TSDR_LAUNCH(ctx, kName, (k_seg1024<KIND, true>), g, b, 0, sig.f32(), nbSeg, nwaves, part, wf);
+  } else {
+    return with_int_iqf(iqf_of(sig.iq().kind), [&](auto iqf) -> int {
+      TSDR_LAUNCH(ctx, kIntName[iqf_name(iqf)], (k_seg1024<KIND, true, iqf>), g, b, 0, sig.f32(), nbSeg, nwaves, part, wf, (float2 *)nullptr, 0u,
+                  sig.scale);
+      return TSDR_OK;
+    });
+  }
+  return TSDR_OK;
+}
+
+// getWelch on checked arguments
+static int welch_d(tsdr_ctx *ctx, const SigSrc &sig, size_t len, size_t sizeFFT, int lin, float *y) {
   if (sizeFFT == (size_t)kSegN && len / sizeFFT > 0 && len / sizeFFT < (size_t(1) << 31)) {
     const size_t nbSeg = len / sizeFFT;
     unsigned blocks = 0;
     const unsigned nwaves = seg_waves(ctx, nbSeg, &blocks);
     float *part = (float *)ctx->scratch(WS_FFT_A, (size_t)blocks * kSegN * 4);
     if (!part) return TSDR_ENOMEM;
-    if (intq) {
-      const dim3 g(blocks), b(64 * kSegWaves);
-      if (f.kind == IQK_SC16) TSDR_LAUNCH(ctx, "welch_seg1024_sc16", (k_seg1024<SEG_WELCH, true, IQF_SC16>), g, b, 0, sig, nbSeg, nwaves, part, (double *)nullptr, (float2 *)nullptr, 0u, f.scale);
-      else if (f.kind == IQK_SC8) TSDR_LAUNCH(ctx, "welch_seg1024_sc8", (k_seg1024<SEG_WELCH, true, IQF_SC8>), g, b, 0, sig, nbSeg, nwaves, part, (double *)nullptr, (float2 *)nullptr, 0u, f.scale);
-      else TSDR_LAUNCH(ctx, "welch_seg1024_uc8", (k_seg1024<SEG_WELCH, true, IQF_UC8>), g, b, 0, sig, nbSeg, nwaves, part, (double *)nullptr, (float2 *)nullptr, 0u, f.scale);
-    } else if (is_complex) {
-      TSDR_LAUNCH(ctx, "welch_seg1024", (k_seg1024<SEG_WELCH, true>), dim3(blocks), dim3(64 * kSegWaves), 0, sig, nbSeg, nwaves, part,
-                  (double *)nullptr);
-    } else {
-      TSDR_LAUNCH(ctx, "welch_seg1024", (k_seg1024<SEG_WELCH, false>), dim3(blocks), dim3(64 * kSegWaves), 0, sig, nbSeg, nwaves, part,
-                  (double *)nullptr);
-    }
+    if (int rc = seg1024_launch<SEG_WELCH>(ctx, sig, nbSeg, nwaves, blocks, part, nullptr)) return rc;
     TSDR_LAUNCH(ctx, "welch_finish", k_welch_finish, dim3(kSegN / 16), dim3(256), 0, (const float *)part, blocks, lin, y);
     return TSDR_OK;
   }
@@ -593,7 +551,7 @@ static int welch_d(tsdr_ctx *ctx, const float *sig, int is_complex, const IqFmt 
     if (!part) return TSDR_ENOMEM;
     unsigned nparts = 0;
     bool did = false;
-    int rc = fft_rows_welch(ctx, sig, is_complex, sizeFFT, len / sizeFFT, part, &nparts, &did, intq ? &f : nullptr);
+    int rc = fft_rows_welch(ctx, sig, sizeFFT, len / sizeFFT, part, &nparts, &did);
     if (rc) return rc;
     if (did) {
       TSDR_LAUNCH(ctx, "welch_sum", k_welch_sum, dim3((unsigned)ceil_div(sizeFFT, 16)), dim3(256), 0, (const float *)part, sizeFFT, nparts, lin, y);
@@ -602,7 +560,7 @@ static int welch_d(tsdr_ctx *ctx, const float *sig, int is_complex, const IqFmt 
   }
   float2 *X;
   size_t nbSeg;
-  int rc = segments_fft(ctx, sig, is_complex, len, sizeFFT, &X, &nbSeg, f);
+  int rc = segments_fft(ctx, sig, len, sizeFFT, &X, &nbSeg);
   if (rc) return rc;
   if (nbSeg == 0) {  // sum over no segments: zeros (-Inf dB), as the reference's zero-initialised accumulator gives
     TSDR_LAUNCH(ctx, "welch_sum", k_welch_sum, dim3((unsigned)ceil_div(sizeFFT, 16)), dim3(256), 0, (const float *)nullptr, sizeFFT, 0u, lin,
@@ -620,106 +578,26 @@ static int welch_d(tsdr_ctx *ctx, const float *sig, int is_complex, const IqFmt 
   return TSDR_OK;
 }
 
-extern "C" {
-
-int tsdr_welch_d(tsdr_ctx *ctx, const float *sig, int is_complex, size_t len, size_t sizeFFT, int lin, float *y) {
-  if (!ctx || !y || (len && !sig)) return TSDR_EINVAL;
-  TSDR_PTR_ALIGNED(ctx, "welch", sig, is_complex ? 8 : 4);
-  TSDR_PTR_ALIGNED(ctx, "welch", y, 4);
-  return welch_d(ctx, sig, is_complex, IqFmt{}, len, sizeFFT, lin, y);
-}
-
-int tsdr_welch_iq_d(tsdr_ctx *ctx, const void *iq, int iq_fmt, float scale, size_t len, size_t sizeFFT, int lin, float *y) {
-  if (!ctx || !y || (len && !iq)) return TSDR_EINVAL;
-  IqFmt f;
-  TSDR_IQ_ARG(ctx, "welch_iq", iq, iq_fmt, scale, f);
-  TSDR_PTR_ALIGNED(ctx, "welch_iq", y, 4);
-  return welch_d(ctx, reinterpret_cast<const float *>(iq), 1, f, len, sizeFFT, lin, y);
-}
-
-int tsdr_welch_iq(tsdr_ctx *ctx, const void *iq, int iq_fmt, float scale, size_t len, size_t sizeFFT, int lin, float *y) {
-  if (!ctx) return TSDR_EINVAL;
-  if (iq_fmt < TSDR_IQ_CF32 || iq_fmt > TSDR_IQ_UC8) return set_err(ctx, TSDR_EINVAL, "welch_iq: iq_fmt %d is not a TSDR_IQ_* format", iq_fmt);
-  return host_map(ctx, iq, len * iq_bytes(IqFmt{iq_fmt, scale}), y, sizeFFT * 4, [&](void *i, void *o) {   // the raw bytes go up, not expanded ones
-    return tsdr_welch_iq_d(ctx, i, iq_fmt, scale, len, sizeFFT, lin, (float *)o);
-  });
-}
-
-int tsdr_welch(tsdr_ctx *ctx, const float *sig, int is_complex, size_t len, size_t sizeFFT, int lin, float *y) {
-  return host_map(ctx, sig, len * (is_complex ? 8 : 4), y, sizeFFT * 4, [&](void *i, void *o) {
-    return tsdr_welch_d(ctx, (const float *)i, is_complex, len, sizeFFT, lin, (float *)o);
-  });
-}
-
-}  // extern "C"
-static int waterfall_d(tsdr_ctx *ctx, const float *sig, int is_complex, const IqFmt &f, size_t len, size_t sizeFFT, double *sMatrix) {
-  const bool intq = f.kind != IQK_CF32;
+static int waterfall_d(tsdr_ctx *ctx, const SigSrc &sig, size_t len, size_t sizeFFT, double *sMatrix) {
   if (sizeFFT == (size_t)kSegN && len / sizeFFT > 0 && len / sizeFFT < (size_t(1) << 31) && sMatrix) {
-    const size_t nbSeg = len / sizeFFT;
     unsigned blocks = 0;
-    const unsigned nwaves = seg_waves(ctx, nbSeg, &blocks);
-    if (intq) {
-      const dim3 g(blocks), b(64 * kSegWaves);
-      if (f.kind == IQK_SC16) TSDR_LAUNCH(ctx, "waterfall_seg1024_sc16", (k_seg1024<SEG_WATERFALL, true, IQF_SC16>), g, b, 0, sig, nbSeg, nwaves, (float *)nullptr, sMatrix, (float2 *)nullptr, 0u, f.scale);
-      else if (f.kind == IQK_SC8) TSDR_LAUNCH(ctx, "waterfall_seg1024_sc8", (k_seg1024<SEG_WATERFALL, true, IQF_SC8>), g, b, 0, sig, nbSeg, nwaves, (float *)nullptr, sMatrix, (float2 *)nullptr, 0u, f.scale);
-      else TSDR_LAUNCH(ctx, "waterfall_seg1024_uc8", (k_seg1024<SEG_WATERFALL, true, IQF_UC8>), g, b, 0, sig, nbSeg, nwaves, (float *)nullptr, sMatrix, (float2 *)nullptr, 0u, f.scale);
-    } else if (is_complex) {
-      TSDR_LAUNCH(ctx, "waterfall_seg1024", (k_seg1024<SEG_WATERFALL, true>), dim3(blocks), dim3(64 * kSegWaves), 0, sig, nbSeg, nwaves,
-                  (float *)nullptr, sMatrix);
-    } else {
-      TSDR_LAUNCH(ctx, "waterfall_seg1024", (k_seg1024<SEG_WATERFALL, false>), dim3(blocks), dim3(64 * kSegWaves), 0, sig, nbSeg, nwaves,
-                  (float *)nullptr, sMatrix);
-    }
-    return TSDR_OK;
+    const unsigned nwaves = seg_waves(ctx, len / sizeFFT, &blocks);
+    return seg1024_launch<SEG_WATERFALL>(ctx, sig, len / sizeFFT, nwaves, blocks, nullptr, sMatrix);
   }
   if (sizeFFT && sMatrix && len / sizeFFT > 0) {
     bool did = false;
-    int rcw = fft_rows_waterfall(ctx, sig, is_complex, sizeFFT, len / sizeFFT, sMatrix, &did, intq ? &f : nullptr);
+    int rcw = fft_rows_waterfall(ctx, sig, sizeFFT, len / sizeFFT, sMatrix, &did);
     if (rcw || did) return rcw;
   }
   float2 *X;
   size_t nbSeg;
-  int rc = segments_fft(ctx, sig, is_complex, len, sizeFFT, &X, &nbSeg, f);
+  int rc = segments_fft(ctx, sig, len, sizeFFT, &X, &nbSeg);
   if (rc) return rc;
   if (nbSeg == 0) return TSDR_OK;
   if (!sMatrix) return TSDR_EINVAL;
   TSDR_LAUNCH(ctx, "waterfall_out", k_waterfall, dim3(stream_grid(ctx, sizeFFT * nbSeg)), dim3(256), 0, (const float2 *)X,
               sizeFFT, nbSeg, sMatrix);
   return TSDR_OK;
-}
-
-extern "C" {
-
-int tsdr_waterfall_d(tsdr_ctx *ctx, const float *sig, int is_complex, size_t len, size_t sizeFFT, double *sMatrix) {
-  if (!ctx || (len && !sig)) return TSDR_EINVAL;
-  TSDR_PTR_ALIGNED(ctx, "waterfall", sig, is_complex ? 8 : 4);
-  TSDR_PTR_ALIGNED(ctx, "waterfall", sMatrix, 8);
-  return waterfall_d(ctx, sig, is_complex, IqFmt{}, len, sizeFFT, sMatrix);
-}
-
-int tsdr_waterfall_iq_d(tsdr_ctx *ctx, const void *iq, int iq_fmt, float scale, size_t len, size_t sizeFFT, double *sMatrix) {
-  if (!ctx || (len && !iq)) return TSDR_EINVAL;
-  IqFmt f;
-  TSDR_IQ_ARG(ctx, "waterfall_iq", iq, iq_fmt, scale, f);
-  TSDR_PTR_ALIGNED(ctx, "waterfall_iq", sMatrix, 8);
-  return waterfall_d(ctx, reinterpret_cast<const float *>(iq), 1, f, len, sizeFFT, sMatrix);
-}
-
-int tsdr_waterfall_iq(tsdr_ctx *ctx, const void *iq, int iq_fmt, float scale, size_t len, size_t sizeFFT, double *sMatrix) {
-  if (!ctx || sizeFFT == 0) return TSDR_EINVAL;
-  if (iq_fmt < TSDR_IQ_CF32 || iq_fmt > TSDR_IQ_UC8) return set_err(ctx, TSDR_EINVAL, "waterfall_iq: iq_fmt %d is not a TSDR_IQ_* format", iq_fmt);
-  const size_t nb = len / sizeFFT;
-  return host_map(ctx, iq, len * iq_bytes(IqFmt{iq_fmt, scale}), sMatrix, nb * sizeFFT * 8, [&](void *i, void *o) {
-    return tsdr_waterfall_iq_d(ctx, i, iq_fmt, scale, len, sizeFFT, (double *)o);
-  });
-}
-
-int tsdr_waterfall(tsdr_ctx *ctx, const float *sig, int is_complex, size_t len, size_t sizeFFT, double *sMatrix) {
-  if (sizeFFT == 0) return TSDR_EINVAL;
-  const size_t nb = len / sizeFFT;
-  return host_map(ctx, sig, len * (is_complex ? 8 : 4), sMatrix, nb * sizeFFT * 8, [&](void *i, void *o) {
-    return tsdr_waterfall_d(ctx, (const float *)i, is_complex, len, sizeFFT, (double *)o);
-  });
 }
 
 // ---- init_resampler / initLPF (Resampler.jl:26-99) ------------------------------------------------
@@ -753,8 +631,6 @@ static inline double lpf_phase(size_t k, const LpfPhase &st) {
   return a + b;
 }
 
-}  // extern "C"
-namespace tsdr {
 // init_resampler(T, bufferSize, upCoeff) for T = Float32 (f64 false) or Float64: the same H either way (initLPF builds it in f64
 // for both); the containerFFT buffers of the kind asked for
 int resampler_init_kind(tsdr_ctx *ctx, size_t bufferSize, int upCoeff, bool f64, tsdr_resampler **out) {
@@ -822,8 +698,100 @@ int resampler_init_kind(tsdr_ctx *ctx, size_t bufferSize, int upCoeff, bool f64,
   *out = r;
   return TSDR_OK;
 }
+
 }  // namespace tsdr
+
+using namespace tsdr;
+
 extern "C" {
+
+int tsdr_spectrum_d(tsdr_ctx *ctx, const float *sig, int is_complex, size_t N, int lin, float *y) {
+  if (!ctx || (N && (!sig || !y))) return TSDR_EINVAL;
+  TSDR_PTR_ALIGNED(ctx, "spectrum", sig, is_complex ? 8 : 4);
+  TSDR_PTR_ALIGNED(ctx, "spectrum", y, 4);
+  return spectrum_d(ctx, sig_f32(sig, is_complex), N, lin, y);
+}
+
+int tsdr_spectrum_iq_d(tsdr_ctx *ctx, const void *iq, int iq_fmt, float scale, size_t N, int lin, float *y) {
+  if (!ctx || (N && (!iq || !y))) return TSDR_EINVAL;
+  IqFmt f;
+  TSDR_IQ_ARG(ctx, "spectrum_iq", iq, iq_fmt, scale, f);
+  TSDR_PTR_ALIGNED(ctx, "spectrum_iq", y, 4);
+  return spectrum_d(ctx, sig_iq(iq, f), N, lin, y);
+}
+
+int tsdr_spectrum_iq(tsdr_ctx *ctx, const void *iq, int iq_fmt, float scale, size_t N, int lin, float *y) {
+  if (!ctx) return TSDR_EINVAL;
+  TSDR_IQ_FMT_ARG(ctx, "spectrum_iq", iq_fmt);
+  return host_map(ctx, iq, N * iq_bytes(IqFmt{iq_fmt, scale}), y, N * 4,
+                  [&](void *i, void *o) { return tsdr_spectrum_iq_d(ctx, i, iq_fmt, scale, N, lin, (float *)o); });
+}
+
+int tsdr_spectrum(tsdr_ctx *ctx, const float *sig, int is_complex, size_t N, int lin, float *y) {
+  return host_map(ctx, sig, N * (is_complex ? 8 : 4), y, N * 4,
+                  [&](void *i, void *o) { return spectrum_d(ctx, sig_f32((const float *)i, is_complex), N, lin, (float *)o); });
+}
+
+int tsdr_welch_d(tsdr_ctx *ctx, const float *sig, int is_complex, size_t len, size_t sizeFFT, int lin, float *y) {
+  if (!ctx || !y || (len && !sig)) return TSDR_EINVAL;
+  TSDR_PTR_ALIGNED(ctx, "welch", sig, is_complex ? 8 : 4);
+  TSDR_PTR_ALIGNED(ctx, "welch", y, 4);
+  return welch_d(ctx, sig_f32(sig, is_complex), len, sizeFFT, lin, y);
+}
+
+int tsdr_welch_iq_d(tsdr_ctx *ctx, const void *iq, int iq_fmt, float scale, size_t len, size_t sizeFFT, int lin, float *y) {
+  if (!ctx || !y || (len && !iq)) return TSDR_EINVAL;
+  IqFmt f;
+  TSDR_IQ_ARG(ctx, "welch_iq", iq, iq_fmt, scale, f);
+  TSDR_PTR_ALIGNED(ctx, "welch_iq", y, 4);
+  return welch_d(ctx, sig_iq(iq, f), len, sizeFFT, lin, y);
+}
+
+int tsdr_welch_iq(tsdr_ctx *ctx, const void *iq, int iq_fmt, float scale, size_t len, size_t sizeFFT, int lin, float *y) {
+  if (!ctx) return TSDR_EINVAL;
+  TSDR_IQ_FMT_ARG(ctx, "welch_iq", iq_fmt);
+  return host_map(ctx, iq, len * iq_bytes(IqFmt{iq_fmt, scale}), y, sizeFFT * 4, [&](void *i, void *o) {   // the raw bytes go up, not expanded ones
+    return tsdr_welch_iq_d(ctx, i, iq_fmt, scale, len, sizeFFT, lin, (float *)o);
+  });
+}
+
+int tsdr_welch(tsdr_ctx *ctx, const float *sig, int is_complex, size_t len, size_t sizeFFT, int lin, float *y) {
+  return host_map(ctx, sig, len * (is_complex ? 8 : 4), y, sizeFFT * 4, [&](void *i, void *o) {
+    return tsdr_welch_d(ctx, (const float *)i, is_complex, len, sizeFFT, lin, (float *)o);
+  });
+}
+
+int tsdr_waterfall_d(tsdr_ctx *ctx, const float *sig, int is_complex, size_t len, size_t sizeFFT, double *sMatrix) {
+  if (!ctx || (len && !sig)) return TSDR_EINVAL;
+  TSDR_PTR_ALIGNED(ctx, "waterfall", sig, is_complex ? 8 : 4);
+  TSDR_PTR_ALIGNED(ctx, "waterfall", sMatrix, 8);
+  return waterfall_d(ctx, sig_f32(sig, is_complex), len, sizeFFT, sMatrix);
+}
+
+int tsdr_waterfall_iq_d(tsdr_ctx *ctx, const void *iq, int iq_fmt, float scale, size_t len, size_t sizeFFT, double *sMatrix) {
+  if (!ctx || (len && !iq)) return TSDR_EINVAL;
+  IqFmt f;
+  TSDR_IQ_ARG(ctx, "waterfall_iq", iq, iq_fmt, scale, f);
+  TSDR_PTR_ALIGNED(ctx, "waterfall_iq", sMatrix, 8);
+  return waterfall_d(ctx, sig_iq(iq, f), len, sizeFFT, sMatrix);
+}
+
+int tsdr_waterfall_iq(tsdr_ctx *ctx, const void *iq, int iq_fmt, float scale, size_t len, size_t sizeFFT, double *sMatrix) {
+  if (!ctx || sizeFFT == 0) return TSDR_EINVAL;
+  TSDR_IQ_FMT_ARG(ctx, "waterfall_iq", iq_fmt);
+  const size_t nb = len / sizeFFT;
+  return host_map(ctx, iq, len * iq_bytes(IqFmt{iq_fmt, scale}), sMatrix, nb * sizeFFT * 8, [&](void *i, void *o) {
+    return tsdr_waterfall_iq_d(ctx, i, iq_fmt, scale, len, sizeFFT, (double *)o);
+  });
+}
+
+int tsdr_waterfall(tsdr_ctx *ctx, const float *sig, int is_complex, size_t len, size_t sizeFFT, double *sMatrix) {
+  if (sizeFFT == 0) return TSDR_EINVAL;
+  const size_t nb = len / sizeFFT;
+  return host_map(ctx, sig, len * (is_complex ? 8 : 4), sMatrix, nb * sizeFFT * 8, [&](void *i, void *o) {
+    return tsdr_waterfall_d(ctx, (const float *)i, is_complex, len, sizeFFT, (double *)o);
+  });
+}
 
 int tsdr_resampler_init(tsdr_ctx *ctx, size_t bufferSize, int upCoeff, tsdr_resampler **out) {
   return resampler_init_kind(ctx, bufferSize, upCoeff, false, out);
@@ -850,11 +818,11 @@ int tsdr_resampler_run_d(tsdr_resampler *r, const float *in, size_t n_in, float 
     const size_t Nh = r->bufferSize / 2, M = N / 2;
     float2 *P = (float2 *)ctx->scratch(WS_FFT_A, Nh * sizeof(float2));
     if (!P) return TSDR_ENOMEM;
-    int rc = fft_any(ctx, in, 1, P, Nh, 1, -1);
+    int rc = fft_any(ctx, sig_f32(in, 1), P, Nh, 1, -1);
     if (rc) return rc;
     TSDR_LAUNCH(ctx, "resampler_mid", k_resamp_mid, dim3(stream_grid(ctx, M / 2 + 1)), dim3(256), 0, (const float2 *)P,
                 (const double2 *)r->Hs, r->bufferSize, N, (double)(2 * r->up), (const double2 *)r->tw, (unsigned)r->up, r->work);
-    return fft_any(ctx, reinterpret_cast<const float *>(r->work), 1, reinterpret_cast<float2 *>(out), M, 1, +1);
+    return fft_any(ctx, SigSrc{r->work, SIG_CF32, 1.0f}, reinterpret_cast<float2 *>(out), M, 1, +1);
   }
   float2 *tmp = (float2 *)ctx->scratch(WS_FFT_A, N * sizeof(float2));
   if (!tmp) return TSDR_ENOMEM;
@@ -877,10 +845,10 @@ int tsdr_resampler_run_d(tsdr_resampler *r, const float *in, size_t n_in, float 
               : fft_mixed(ctx, tmp, r->work, N, 1, +1, inv, SRC_MULH, 0, 0, &epi, reinterpret_cast<const float2 *>(r->H));
   }
   TSDR_LAUNCH(ctx, "resampler_stuff", k_stuff, dim3(stream_grid(ctx, N)), dim3(256), 0, in, N, (unsigned)r->up, r->work);
-  int rc = fft_any(ctx, reinterpret_cast<const float *>(r->work), 1, tmp, N, 1, -1);
+  int rc = fft_any(ctx, SigSrc{r->work, SIG_CF32, 1.0f}, tmp, N, 1, -1);
   if (rc) return rc;
   TSDR_LAUNCH(ctx, "resampler_filter", k_cmul, dim3(stream_grid(ctx, N)), dim3(256), 0, tmp, (const double2 *)r->H, N);
-  rc = fft_any(ctx, reinterpret_cast<const float *>(tmp), 1, r->work, N, 1, +1);
+  rc = fft_any(ctx, SigSrc{tmp, SIG_CF32, 1.0f}, r->work, N, 1, +1);
   if (rc) return rc;
   TSDR_LAUNCH(ctx, "resampler_out", k_real_scale, dim3(stream_grid(ctx, N)), dim3(256), 0, (const float2 *)r->work, N,
               (float)(2 * r->up), out);
