@@ -23,21 +23,19 @@
 
 namespace tsdr {
 
-int get_tw(tsdr_ctx *ctx, int logN, TwTable **out);
-
 __device__ inline float2 cmulf(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
 
 // is_iq: fft_dev.h's SigKind -- 0 = x is real f32; 1 + TSDR_IQ_* = x is IQ of that format (1: ComplexF32, 2: sc16, 3: sc8, 4: uc8), whose abs2 is the
 // sample -- integer storage converted as the frame loaders do (common.h: ld_iq, one product by `scale`)
 __device__ inline float ld_power(const float *x, int is_iq, size_t i, float scale) {
-  if (is_iq == 1) {
+  if (is_iq == SIG_CF32) {
     float2 z = reinterpret_cast<const float2 *>(x)[i];
     return abs2_c(z.x, z.y);
   }
   if (is_iq) {
     float2 z;
-    if (is_iq == 2) z = cvt_sc16(reinterpret_cast<const short2 *>(x)[i], scale);
-    else if (is_iq == 3) z = cvt_sc8(reinterpret_cast<const unsigned short *>(x)[i], scale);
+    if (is_iq == SIG_SC16) z = cvt_sc16(reinterpret_cast<const short2 *>(x)[i], scale);
+    else if (is_iq == SIG_SC8) z = cvt_sc8(reinterpret_cast<const unsigned short *>(x)[i], scale);
     else z = cvt_uc8(reinterpret_cast<const unsigned short *>(x)[i], scale);
     return abs2_c(z.x, z.y);
   }
@@ -200,7 +198,7 @@ static inline double jl_round(double v) { return nearbyint(v); }  // Julia round
 static int autocorr_core(tsdr_ctx *ctx, const SigSrc &sig, size_t n, size_t k0, size_t cnt, int log_scale, float *out,
                          AmaxReq *amax = nullptr) {
   const float *x = sig.f32();
-  const int is_iq = sig.kind, src_mode = srcpow_of(sig.kind);   // (the first pass's loader for that input)
+  const int is_iq = sig.kind;
   const float iq_scale = sig.scale;
   // n = 2*Mc with Mc = 2^a 3^b 5^c (the usual case: decimal sample rates, or a power of two): the circular
   // correlation of length n is transformed natively -- no zero padding, no fold, half the bytes (or less) of the
@@ -213,6 +211,9 @@ static int autocorr_core(tsdr_ctx *ctx, const SigSrc &sig, size_t n, size_t k0, 
     float2 *z = (float2 *)ctx->scratch(WS_FFT_A, Mc * sizeof(float2));
     float2 *Z = (float2 *)ctx->scratch(WS_FFT_C, Mc * sizeof(float2));
     if (!z || !Z) return TSDR_ENOMEM;
+    FftReq fwd;   // the forward transform straight from the samples: the first pass forms abs2 (IQ) and packs two per complex value
+    fwd.out = Z; fwd.n = Mc; fwd.src_n = n;
+    fwd.load(sig, srcpow_of(sig.kind));
     if (!half_pow2) {
       // mixed-radix route, three fusions: the first forward pass forms abs2 and packs; the first inverse pass forms the
       // packed power spectrum from Z while loading (no k_ac_power round trip); the last inverse pass writes
@@ -226,22 +227,28 @@ static int autocorr_core(tsdr_ctx *ctx, const SigSrc &sig, size_t n, size_t k0, 
         epi.amax_keys = amax->slots; epi.amax_lo = amax->lo; epi.amax_cnt = amax->cnt;
         amax->fused = true;
       }
+      FftReq b;   // the inverse transform: its scale, the lags kept and the epilogue are the fused sequence's too
+      b.in = Z; b.out = z; b.n = Mc; b.dir = +1; b.scale = (float)(0.5 / (double)Mc); b.src_mode = SRC_POWER; b.src_n = Mc;
+      b.keep = (k0 + cnt + 1) / 2; b.epi = &epi;
       // one launch carries the last forward pass, the power spectrum and the first inverse pass when the split allows
       if (ctx->opt_ac_fuse_mid) {
+        FftReq a = fwd;   // the forward's samples and loader; the inverse's output, scale, kept lags and epilogue
+        a.out = z; a.scale = b.scale; a.keep = b.keep; a.epi = b.epi;
         bool done = false;
-        int rc = fft_mixed_autocorr(ctx, reinterpret_cast<const float2 *>(x), src_mode, n, Mc, Z, z,
-                                    (float)(0.5 / (double)Mc), (k0 + cnt + 1) / 2, &epi, &done, iq_scale);
+        int rc = fft_run_autocorr(ctx, a, Z, &done);
         if (rc || done) return rc;
       }
-      int rc = fft_mixed(ctx, reinterpret_cast<const float2 *>(x), Z, Mc, 1, -1, 1.0f, src_mode, n, 0, nullptr, nullptr, iq_scale);
+      int rc = fft_run(ctx, fwd);
       if (rc) return rc;
-      return fft_mixed(ctx, Z, z, Mc, 1, +1, (float)(0.5 / (double)Mc), SRC_POWER, Mc, (k0 + cnt + 1) / 2, &epi);
+      return fft_run(ctx, b);
     }
-    int rc = fft_pow2(ctx, reinterpret_cast<const float2 *>(x), Z, ilog2(Mc), 1, -1, 1.0f, src_mode, n, 0, nullptr, nullptr, iq_scale);
+    int rc = fft_run(ctx, fwd);
     if (rc) return rc;
     TSDR_LAUNCH(ctx, "ac_power", k_ac_power, dim3(stream_grid(ctx, Mc / 2 + 1)), dim3(256), 0, Z, Mc, (const float2 *)nullptr,
                 (const float2 *)nullptr, 0, 4.0 / (double)Mc);
-    rc = fft_pow2(ctx, Z, z, ilog2(Mc), 1, +1, (float)(0.5 / (double)Mc), SRC_C2C, n, (k0 + cnt + 1) / 2);
+    FftReq b;
+    b.in = Z; b.out = z; b.n = Mc; b.dir = +1; b.scale = (float)(0.5 / (double)Mc); b.src_n = n; b.keep = (k0 + cnt + 1) / 2;
+    rc = fft_run(ctx, b);
     if (rc) return rc;
     TSDR_LAUNCH(ctx, "ac_finish", k_ac_finish, dim3(stream_grid(ctx, cnt)), dim3(256), 0, reinterpret_cast<const float *>(z),
                 k0, cnt, log_scale, out);
@@ -259,23 +266,29 @@ static int autocorr_core(tsdr_ctx *ctx, const SigSrc &sig, size_t n, size_t k0, 
   // forward transform straight from the samples: the first pass packs (x[2j], x[2j+1]) -- forming abs2.(iq) on
   // the fly when asked -- and never reads the zero padding; no separate pack pass, no 33 MB round trip
   const bool aligned = !is_iq || (reinterpret_cast<uintptr_t>(x) & 15u) == 0;  // the IQ loader reads float4 pairs
+  FftReq f;
+  f.out = Z; f.n = Mc;
   if (logM - 1 > 8 && aligned) {
-    rc = fft_pow2(ctx, reinterpret_cast<const float2 *>(x), Z, logM - 1, 1, -1, 1.0f, src_mode, n, 0, nullptr, nullptr, iq_scale);
+    f.src_n = n;
+    f.load(sig, srcpow_of(sig.kind));
   } else {
     TSDR_LAUNCH(ctx, "ac_pack", k_ac_pack, dim3(stream_grid(ctx, Mc)), dim3(256), 0, x, is_iq, n, Mc, z, iq_scale);
-    rc = fft_pow2(ctx, z, Z, logM - 1, 1, -1, 1.0f, SRC_C2C, 0, 0);
+    f.in = z;
   }
+  rc = fft_run(ctx, f);
   if (rc) return rc;
   // only lags < n are ever folded: the last inverse pass stores a[0 .. n] = n/2 + 1 complex values.  With more
   // than one pass the power spectrum is formed by the first pass's loader (SRC_POWER); the in-place kernel remains
   // for single-pass lengths.
+  FftReq b;
+  b.in = Z; b.out = z; b.n = Mc; b.dir = +1; b.scale = (float)(0.5 / (double)Mc); b.keep = n / 2 + 1;
   if (logM - 1 > 8) {
-    rc = fft_pow2(ctx, Z, z, logM - 1, 1, +1, (float)(0.5 / (double)Mc), SRC_POWER, Mc, n / 2 + 1);
+    b.src_mode = SRC_POWER; b.src_n = Mc;
   } else {
     TSDR_LAUNCH(ctx, "ac_power", k_ac_power, dim3(stream_grid(ctx, Mc / 2 + 1)), dim3(256), 0, Z, Mc, (const float2 *)tw->lo,
                 (const float2 *)tw->hi, tw->h, 0.0);
-    rc = fft_pow2(ctx, Z, z, logM - 1, 1, +1, (float)(0.5 / (double)Mc), SRC_C2C, 0, n / 2 + 1);
   }
+  rc = fft_run(ctx, b);
   if (rc) return rc;
   TSDR_LAUNCH(ctx, "ac_fold", k_ac_fold, dim3(stream_grid(ctx, cnt)), dim3(256), 0, reinterpret_cast<const float *>(z), n, k0,
               cnt, log_scale, out);
@@ -350,10 +363,13 @@ int tsdr_autocorr_partial_d(tsdr_ctx *ctx, const float *x, int is_iq, size_t n, 
   float2 *Z = (float2 *)ctx->scratch(WS_FFT_C, M * sizeof(float2));
   if (!z || !Z) return TSDR_ENOMEM;
   TSDR_LAUNCH(ctx, "pc_pack", k_pc_pack, dim3(stream_grid(ctx, M)), dim3(256), 0, x, is_iq ? 1 : 0, n, m0, cnt, vlen, M, z, 1.0f);
-  int rc = fft_pow2(ctx, z, Z, logM, 1, -1, 1.0f, SRC_C2C, 0, 0);
+  FftReq f;
+  f.in = z; f.out = Z; f.n = M;
+  int rc = fft_run(ctx, f);
   if (rc) return rc;
   TSDR_LAUNCH(ctx, "pc_cross", k_pc_cross, dim3(stream_grid(ctx, M / 2 + 1)), dim3(256), 0, Z, M);
-  rc = fft_pow2(ctx, Z, z, logM, 1, +1, (float)(1.0 / (double)M), SRC_C2C, 0, n_lags);
+  f.in = Z; f.out = z; f.dir = +1; f.scale = (float)(1.0 / (double)M); f.keep = n_lags;
+  rc = fft_run(ctx, f);
   if (rc) return rc;
   TSDR_LAUNCH(ctx, "pc_real", k_real_part, dim3(stream_grid(ctx, n_lags)), dim3(256), 0, (const float2 *)z, n_lags, part);
   return TSDR_OK;

@@ -48,9 +48,9 @@ static int autocorr_cplx_core(tsdr_ctx *ctx, const SigSrc &z, size_t n, size_t k
   float2 *X = (float2 *)ctx->scratch(WS_FFT_A, n * sizeof(float2));
   if (!X) return TSDR_ENOMEM;
   if (cac_native(ctx, n)) {
-    const bool p2 = is_pow2(n);
-    int rc = p2 ? fft_pow2(ctx, z.c32(), X, ilog2(n), 1, -1, 1.0f, src_of(z.kind), 0, 0, nullptr, nullptr, z.scale)
-                : fft_mixed(ctx, z.c32(), X, n, 1, -1, 1.0f, src_of(z.kind), 0, 0, nullptr, nullptr, z.scale);
+    FftReq f;
+    f.out = X; f.n = n;
+    int rc = fft_run(ctx, f.load(z, src_of(z.kind)));
     if (rc) return rc;
     FftEpilogue epi;
     epi.kind = EPI_CAC;
@@ -63,9 +63,9 @@ static int autocorr_cplx_core(tsdr_ctx *ctx, const SigSrc &z, size_t n, size_t k
       amax->fused = true;
     }
     // (nothing is stored through the `out` argument of a pass with an epilogue; lags past the window are not formed into outputs)
-    const float inv_n = (float)(1.0 / (double)n);
-    return p2 ? fft_pow2(ctx, X, X, ilog2(n), 1, +1, inv_n, SRC_ABS2, 0, k0 + cnt, &epi)
-              : fft_mixed(ctx, X, X, n, 1, +1, inv_n, SRC_ABS2, 0, k0 + cnt, &epi);
+    FftReq b;
+    b.in = X; b.out = X; b.n = n; b.dir = +1; b.scale = (float)(1.0 / (double)n); b.src_mode = SRC_ABS2; b.keep = k0 + cnt; b.epi = &epi;
+    return fft_run(ctx, b);
   }
   // (one-launch and Bluestein lengths: integer samples are expanded into the workspace first, fft_any)
   int rc = fft_any(ctx, z, X, n, 1, -1);

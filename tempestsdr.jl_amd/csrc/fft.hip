@@ -20,28 +20,11 @@
 // exactly (k^2 mod 2n in 64-bit integers) and evaluated in f64.
 #include <cmath>
 
-#include "fft_dev.h"
+#include "fft_plan.h"
 
 namespace tsdr {
 
-struct PassDesc {
-  int mode, logR, logT, dir;
-  float scale;
-  unsigned long long N;  // elements per transform
-  unsigned A, B, tiles;  // strided: outer count, inner size (= stride of the DFT index), B/T
-  int logNtw, logBnext, logPprev;
-  int nprev;
-  int logRprev[4];       // radices of the passes before this one (pass order)
-  int logR1;
-  unsigned Aprime, k1tiles;  // last pass: A / R_1, R_1 / T
-  unsigned rows;             // rows mode: number of transforms
-  int src_mode;              // first pass loader (SRC_*); only with batch == 1
-  unsigned long long src_n;  // real samples behind SRC_REAL / SRC_IQPOW
-  unsigned long long keep;   // last pass: complex outputs >= keep (per transform) are not stored
-  const float2 *src_aux;     // SRC_MULH: the factor array
-  double src_w8;             // fft_load's f64 parameter: the scale of an integer IQ source (else 0)
-  FftEpilogue epi;           // last pass: epilogue when epi.out != nullptr (fft_dev.h)
-};
+// (PassDesc, the pass split and what each pass launches: fft_plan.h)
 
 // K(a): a = k_1*(R_2..R_m) + ... + k_m  ->  k_1 + R_1*k_2 + R_1R_2*k_3 + ...
 __device__ inline unsigned digit_swap(unsigned a, int m, const int *logR) {
@@ -287,8 +270,6 @@ __global__ __launch_bounds__(256) void k_fft_pass(const float2 *__restrict__ in,
   }
 }
 
-typedef void (*fft_pass_fn)(const float2 *, float2 *, PassDesc, const float2 *);
-
 template <int MODE>
 static fft_pass_fn pass_fn(int logR) {
   switch (logR) {
@@ -302,7 +283,10 @@ static fft_pass_fn pass_fn(int logR) {
     default: return k_fft_pass<8, MODE>;
   }
 }
-static const size_t kPassLds = (4096 + 256 + 16 + 256 + 256) * sizeof(float2);
+// k_fft_pass<logR, mode> for the launcher (fft_mixed.hip:launch_step)
+fft_pass_fn fft_pass_kernel(int mode, int logR) {
+  return mode == FFT_ROWS ? pass_fn<FFT_ROWS>(logR) : mode == FFT_STRIDED ? pass_fn<FFT_STRIDED>(logR) : pass_fn<FFT_LAST>(logR);
+}
 
 // ---- twiddle tables ------------------------------------------------------------------------
 int ensure_tw_small(tsdr_ctx *ctx) {  // W_4096^e, e < 4096 (ctx->tw_small)
@@ -342,96 +326,6 @@ int get_tw(tsdr_ctx *ctx, int logN, TwTable **out) {
   *out = &ins.first->second;
   return TSDR_OK;
 }
-
-// ---- power-of-two driver ---------------------------------------------------------------------
-// in/out may alias.  Uses WS_FFT_B when more than one pass is needed: callers must not hand
-// WS_FFT_B buffers to this function.
-int fft_pow2(tsdr_ctx *ctx, const float2 *in, float2 *out, int logN, size_t batch, int dir, float scale, int src_mode,
-             size_t src_n, size_t keep, const FftEpilogue *epi, const float2 *src_aux, float src_scale) {
-  if (logN < 0 || logN > 31) return set_err(ctx, TSDR_EINVAL, "fft: unsupported power-of-two length 2^%d", logN);
-  if (batch == 0) return TSDR_OK;
-  int rc = ensure_tw_small(ctx);
-  if (rc) return rc;
-  const size_t N = size_t(1) << logN;
-  if (N * batch >= (size_t(1) << 40)) return set_err(ctx, TSDR_EINVAL, "fft: batch too large");
-  if (logN == 0) {
-    if (in != out) TSDR_HIP(ctx, hipMemcpyAsync(out, in, batch * sizeof(float2), hipMemcpyDeviceToDevice, ctx->stream));
-    return TSDR_OK;
-  }
-  int p = logN <= 8 ? 1 : (logN + 7) / 8;
-  int bits[4];
-  for (int i = 0; i < p; ++i) bits[i] = logN / p + (i < logN % p ? 1 : 0);
-  PassDesc d{};
-  d.dir = dir < 0 ? -1 : 1;
-  d.N = N;
-  d.src_mode = SRC_C2C;
-  d.src_n = 0;
-  d.keep = keep ? keep : N;
-  // (the integer IQ loaders are element-wise like SRC_C2C: any batch, as long as there is a strided pass to load through)
-  if ((src_mode != SRC_C2C || epi) && ((batch != 1 && (epi || !src_is_cplx_int(src_mode))) || logN <= 8)) return set_err(ctx, TSDR_EINVAL, "fft: fused loader / epilogue needs one multi-pass transform");
-  d.src_aux = src_aux;
-  d.src_w8 = src_is_int_iq(src_mode) ? (double)src_scale : 0.0;
-  if (p == 1) {
-    d.mode = FFT_ROWS;
-    d.logR = logN;
-    d.logT = 12 - logN;  // R*T = 4096
-    d.scale = scale;
-    d.rows = (unsigned)batch;
-    if (batch >= (size_t(1) << 32)) return set_err(ctx, TSDR_EINVAL, "fft: too many rows");
-    const int T = 1 << d.logT;
-    const unsigned grid = (unsigned)ceil_div(batch, (size_t)T);
-    TSDR_LAUNCH(ctx, "fft_rows", pass_fn<FFT_ROWS>(d.logR), dim3(grid), dim3(256), kPassLds, in, out, d, (const float2 *)ctx->tw_small);
-    return TSDR_OK;
-  }
-  float2 *work = (float2 *)ctx->scratch(WS_FFT_B, N * batch * sizeof(float2));
-  if (!work) return TSDR_ENOMEM;
-  int logP = 0;  // log2(R_1..R_{i-1})
-  const float2 *src = in;
-  for (int i = 0; i < p - 1; ++i) {
-    const int logB = logN - logP - bits[i];
-    d.mode = FFT_STRIDED;
-    d.src_mode = i == 0 ? src_mode : SRC_C2C;
-    d.src_n = src_n;
-    d.logR = bits[i];
-    d.logT = std::min(12 - bits[i], logB);
-    d.scale = 1.0f;
-    d.A = 1u << logP;
-    d.B = 1u << logB;
-    d.tiles = d.B >> d.logT;
-    d.logNtw = logP + bits[i] + bits[i + 1];
-    d.logBnext = logB - bits[i + 1];
-    d.logPprev = logP;
-    d.nprev = i;
-    for (int j = 0; j < i; ++j) d.logRprev[j] = bits[j];
-    const size_t grid = batch * d.A * d.tiles;
-    if (grid >= (size_t(1) << 31)) return set_err(ctx, TSDR_EINVAL, "fft: grid too large");
-    static const char *const kStridedName[3] = {"fft_strided1", "fft_strided2", "fft_strided3"};
-    TSDR_LAUNCH(ctx, kStridedName[i], pass_fn<FFT_STRIDED>(d.logR), dim3((unsigned)grid), dim3(256), kPassLds, src, work, d,
-                (const float2 *)ctx->tw_small);
-    src = work;
-    logP += bits[i];
-  }
-  d.mode = FFT_LAST;
-  d.src_mode = SRC_C2C;
-  if (epi) d.epi = *epi;
-  d.logR = bits[p - 1];
-  d.logR1 = bits[0];
-  d.logT = std::min(12 - bits[p - 1], bits[0]);
-  d.scale = scale;
-  d.logPprev = logP;
-  d.nprev = p - 1;
-  for (int j = 0; j < p - 1; ++j) d.logRprev[j] = bits[j];
-  d.Aprime = 1u << (logP - bits[0]);
-  d.k1tiles = 1u << (bits[0] - d.logT);
-  {
-    const size_t grid = batch * d.Aprime * d.k1tiles;
-    if (grid >= (size_t(1) << 31)) return set_err(ctx, TSDR_EINVAL, "fft: grid too large");
-    TSDR_LAUNCH(ctx, "fft_last", pass_fn<FFT_LAST>(d.logR), dim3((unsigned)grid), dim3(256), kPassLds, (const float2 *)work, out, d,
-                (const float2 *)ctx->tw_small);
-  }
-  return TSDR_OK;
-}
-
 
 // ---- Bluestein ----------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_chirp(float2 *__restrict__ chirp, unsigned long long n) {
@@ -506,7 +400,9 @@ static int get_bluestein(tsdr_ctx *ctx, size_t n, BluesteinPlan **out) {
   float2 *tmp = (float2 *)ctx->scratch(WS_FFT_D, pl.L * sizeof(float2));
   if (!tmp) return TSDR_ENOMEM;
   TSDR_LAUNCH(ctx, "blu_b", k_blu_b, dim3(stream_grid(ctx, pl.L)), dim3(256), 0, (const float2 *)pl.chirp, n, pl.L, tmp);
-  int rc = fft_pow2(ctx, tmp, pl.bfft, ilog2(pl.L), 1, -1, 1.0f, SRC_C2C, 0, 0);
+  FftReq q;
+  q.in = tmp; q.out = pl.bfft; q.n = pl.L;
+  int rc = fft_run(ctx, q);
   if (rc) return rc;
   auto ins = ctx->blu.emplace(n, pl);
   *out = &ins.first->second;
@@ -518,8 +414,7 @@ static int get_bluestein(tsdr_ctx *ctx, size_t n, BluesteinPlan **out) {
 // neither exists -- one-launch lengths, Bluestein, and 1024-point rows (k_seg1024's row form reads ComplexF32) -- the samples
 // are expanded into WS_IQX first.
 static bool first_pass_loads(tsdr_ctx *ctx, size_t n, size_t batch) {
-  if (is_pow2(n)) return ilog2(n) > 8;
-  return fft_mixed_ok(n) && fft_mixed_passes(ctx, n, batch) >= 2;
+  return fft_split(n, fft_big_ok(fft_opts(ctx), n * batch)) >= 2;
 }
 
 // General-length FFT of `batch` contiguous transforms.  x: real f32, interleaved complex, or integer IQ as stored (forward only),
@@ -552,9 +447,10 @@ int fft_any(tsdr_ctx *ctx, SigSrc x, float2 *out, size_t n, size_t batch, int di
       TSDR_LAUNCH(ctx, "r2c", k_r2c, dim3(stream_grid(ctx, n * batch)), dim3(256), 0, x.f32(), n * batch, out);
       src = out;
     }
-    const int sm = x.is_int() ? src_of(x.kind) : SRC_C2C;
-    return is_pow2(n) ? fft_pow2(ctx, src, out, ilog2(n), batch, d, scale, sm, 0, 0, nullptr, nullptr, x.scale)
-                      : fft_mixed(ctx, src, out, n, batch, d, scale, sm, 0, 0, nullptr, nullptr, x.scale);
+    FftReq q;
+    q.in = src; q.out = out; q.n = n; q.batch = batch; q.dir = d; q.scale = scale;
+    if (x.is_int()) q.load(x, src_of(x.kind));
+    return fft_run(ctx, q);
   }
   BluesteinPlan *pl = nullptr;
   int rc = get_bluestein(ctx, n, &pl);
@@ -566,11 +462,14 @@ int fft_any(tsdr_ctx *ctx, SigSrc x, float2 *out, size_t n, size_t batch, int di
   const int inv = d > 0;
   TSDR_LAUNCH(ctx, "blu_pre", k_blu_pre, dim3(stream_grid(ctx, L * batch)), dim3(256), 0, x.f32(), (int)(x.kind != SIG_REAL), inv, n, L, batch,
               (const float2 *)pl->chirp, a);
-  rc = fft_pow2(ctx, a, a2, ilog2(L), batch, -1, 1.0f, SRC_C2C, 0, 0);
+  FftReq q;
+  q.in = a; q.out = a2; q.n = L; q.batch = batch;
+  rc = fft_run(ctx, q);
   if (rc) return rc;
   TSDR_LAUNCH(ctx, "blu_mul", k_cmul_bcast, dim3(stream_grid(ctx, L * batch)), dim3(256), 0, a2, (const float2 *)pl->bfft, L,
               batch);
-  rc = fft_pow2(ctx, a2, a, ilog2(L), batch, +1, (float)(1.0 / (double)L), SRC_C2C, 0, 0);
+  q.in = a2; q.out = a; q.dir = +1; q.scale = (float)(1.0 / (double)L);
+  rc = fft_run(ctx, q);
   if (rc) return rc;
   TSDR_LAUNCH(ctx, "blu_post", k_blu_post, dim3(stream_grid(ctx, n * batch)), dim3(256), 0, (const float2 *)a, n, L, batch,
               (const float2 *)pl->chirp, inv, scale, out);

@@ -369,15 +369,35 @@ __device__ inline void epi_argmax_finish(const FftEpilogue &e, unsigned long lon
   }
 }
 
-// host entry points of the two engines (fft.hip, fft_mixed.hip).  src_mode / src_n / src_aux: fused loader of the first
-// pass; keep: complex outputs per transform the caller will look at (0 = all); epi: epilogue of the last pass.  Loaders
-// and epilogues need one transform (batch == 1) of more than one pass.
-int fft_pow2(tsdr_ctx *ctx, const float2 *in, float2 *out, int logN, size_t batch, int dir, float scale, int src_mode,
-             size_t src_n, size_t keep, const FftEpilogue *epi = nullptr, const float2 *src_aux = nullptr, float src_scale = 1.0f);
-int fft_mixed(tsdr_ctx *ctx, const float2 *in, float2 *out, size_t N, size_t batch, int dir, float scale, int src_mode,
-              size_t src_n, size_t keep, const FftEpilogue *epi = nullptr, const float2 *src_aux = nullptr, float src_scale = 1.0f);
-int fft_mixed_autocorr(tsdr_ctx *ctx, const float2 *x, int src_mode, size_t src_n, size_t Mc, float2 *Zbuf, float2 *zbuf,
-                       float scale, size_t keep, const FftEpilogue *epi, bool *done, float src_scale = 1.0f);
+// One transform request: `batch` contiguous transforms of n = 2^a 3^b 5^c points, in -> out (they may alias; neither may be a
+// WS_FFT_B buffer).  The first pass can load through a fused loader (src_mode / src_n / src_aux / src_scale, see fft_load), the last
+// pass can store only the first `keep` complex outputs per transform (0 = all) or leave through an epilogue.  Loaders and epilogues
+// need one transform (batch == 1; the element-wise integer IQ loaders: any batch) of more than one pass.
+struct FftReq {
+  const float2 *in = nullptr;
+  float2 *out = nullptr;
+  size_t n = 0, batch = 1;
+  int dir = -1;                        // -1 forward, +1 inverse
+  float scale = 1.0f;
+  int src_mode = SRC_C2C;
+  size_t src_n = 0;
+  const float2 *src_aux = nullptr;
+  float src_scale = 1.0f;              // integer IQ loaders: the samples' factor
+  size_t keep = 0;
+  const FftEpilogue *epi = nullptr;
+  // the first pass reads `s` through loader `mode` (src_of / srcpow_of of its kind)
+  FftReq &load(const SigSrc &s, int mode) { in = s.c32(); src_mode = mode; src_scale = s.scale; return *this; }
+};
+
+// the options a plan depends on, by value: "fft_no_mix2", "fft_big", the device's CU count
+struct FftOpts { int no_mix2 = 0, big = 1, cu_count = 0; };
+inline FftOpts fft_opts(const tsdr_ctx *ctx) { FftOpts o; o.no_mix2 = ctx->opt_fft_no_mix2; o.big = ctx->opt_fft_big; o.cu_count = ctx->cu_count; return o; }
+
+// host entry points of the engines (fft.hip, fft_mixed.hip; what each call launches is decided by fft_plan.h)
+int fft_run(tsdr_ctx *ctx, const FftReq &q);   // one 2^a 3^b 5^c request, on the engine its length takes
+// the circular autocorrelation of 2 * q.n real samples with the fused middle (fft_plan.h:plan_autocorr; Zbuf: q.n complex values);
+// *done = false (nothing launched) when this length has none
+int fft_run_autocorr(tsdr_ctx *ctx, const FftReq &q, float2 *Zbuf, bool *done);
 unsigned fft_rows_welch_parts(tsdr_ctx *ctx);
 // whole-row kernels (fft_mixed.hip): the rows are read as stored, whatever their kind (fft_rows_store: not real ones)
 int fft_rows_welch(tsdr_ctx *ctx, const SigSrc &sig, size_t N, size_t nbSeg, float *part, unsigned *nparts, bool *did);
@@ -388,9 +408,10 @@ int fft_rows1024(tsdr_ctx *ctx, const float2 *in, float2 *out, size_t batch, int
 int fft_any(tsdr_ctx *ctx, SigSrc x, float2 *out, size_t n, size_t batch, int dir);
 int fft64_d(tsdr_ctx *ctx, double2 *data, double2 *scratch, size_t N, int dir);   // fft64.hip
 int resampler_init_kind(tsdr_ctx *ctx, size_t bufferSize, int upCoeff, bool f64, tsdr_resampler **out);   // spectrum.hip
-int fft_mixed_passes(tsdr_ctx *ctx, size_t N, size_t batch);   // passes fft_mixed takes for `batch` transforms of N points (0: not its length)
+int fft_mixed_passes(tsdr_ctx *ctx, size_t N, size_t batch);   // passes the mixed-radix engine takes for `batch` transforms of N points (0: not its length)
 bool fft_mixed_ok(size_t N);
-int fft_passes(size_t N);
-int ensure_tw_small(tsdr_ctx *ctx);  // builds ctx->tw_small: W_4096^e for e < 4096  // launches a length-N transform takes (0: not a 2^a 3^b 5^c length)
+int fft_passes(size_t N);            // launches a length-N transform takes (0: not a 2^a 3^b 5^c length)
+int ensure_tw_small(tsdr_ctx *ctx);  // builds ctx->tw_small: W_4096^e for e < 4096
+int get_tw(tsdr_ctx *ctx, int logN, TwTable **out);   // fft.hip: the two-level table of W_N^e, N = 2^logN, built at first use
 
 }  // namespace tsdr

@@ -16,53 +16,14 @@
 //     position -> frequency map while storing.
 // The factors are ordered so that the last one carries the factors of two: every stride B_i is then a multiple
 // of 16 elements and the T-wide runs of a tile stay 128-byte aligned.
-#include <algorithm>
+#include <cassert>
 #include <cmath>
 #include <cstdlib>
-#include <mutex>
-#include <unordered_map>
 #include <vector>
 
-#include "fft_dev.h"
+#include "fft_plan.h"
 
 namespace tsdr {
-
-enum { MIX_MAX_PASS = 6, MIX_MAX_STAGE = 8 };
-
-struct MixDesc {
-  int mode, dir, logT, nst;
-  float scale;
-  unsigned R;
-  unsigned char rad[MIX_MAX_STAGE];  // stage radices, product R
-  unsigned long long N;              // elements per transform
-  unsigned A, B, tiles;              // strided: outer count, inner size (= stride of the DFT index), ceil(B/T)
-  unsigned Bnext, Pprev;             // B / R_{i+1};  R_1..R_{i-1}
-  unsigned ntw_hi, ntw_lo;           // floor(2^64 / (Pprev * R * R_{i+1})): twiddle phase e/Ntw as a 32-bit fraction
-  unsigned r_hi, r_lo;               // floor(2^64 / R)
-  int nprev;
-  unsigned Rprev[MIX_MAX_PASS], Wprev[MIX_MAX_PASS];  // radices of the earlier passes and their weights in k
-  unsigned R1, Aprime, k1tiles;      // last pass: first radix, A / R_1, ceil(R_1 / T)
-  unsigned rows;                     // rows mode: number of transforms
-  int src_mode;
-  unsigned long long src_n, keep;
-  int tw_sets;                       // strided, two-step kernels: inter-pass twiddle sets held in LDS (0: none)
-  const float2 *twg;                 // strided, Bnext == 1: W_{R*Rnext}^(col*k) at [k * B + col] (else nullptr)
-  const float2 *src_aux;             // SRC_MULH: the factor array
-  double src_w8;                     // SRC_POWER with M = 2*src_n not a power of two: 8/M (else 0)
-  FftEpilogue epi;                   // last pass: autocorrelation epilogue when epi.out != nullptr
-  // rows mode as getWelch's accumulator (GetSpectrum.jl:36-52): nothing is stored per transform; every workgroup walks
-  // tiles blockIdx.x, blockIdx.x + gridDim.x, ... of `rows` segments, adds abs2 of every spectrum it forms in registers and
-  // leaves ONE partial power spectrum, acc[blockIdx.x * R + k] (natural frequency order).  rows_real: the rows are real f32
-  // (1) or integer IQ (fft_dev.h:ROWS_*, converted by the row loader with the scale in src_w8).
-  float *acc;
-  int rows_real;
-  // ... or getWaterfall's writer (GetSpectrum.jl:54-66; three-step kernels only): Float64(abs2) of every spectrum straight from
-  // the registers to wf[segment * R + fftshift position], acc unused (non-null only to select the branch)
-  double *wf;
-  // ... or plain batched row transforms (tsdr_fft_c2c with batch > 1, three-step kernels only): rows_out[row * R + k] = scale * X[k],
-  // either direction; may alias the input (a tile's rows are all loaded before any of them is stored)
-  float2 *rows_out;
-};
 
 // a = k_1*(R_2..R_m) + ... + k_m  ->  k_1*W_1 + ... + k_m*W_m  (uniform per workgroup: scalar code)
 __device__ inline unsigned digit_swap_g(unsigned a, int m, const unsigned *R, const unsigned *W) {
@@ -437,19 +398,7 @@ __global__ __launch_bounds__(256, 4) void k_fft_mix(const float2 *__restrict__ i
 // step 2: RB-point DFTs over j0 in registers (slot = (column t, frequency ka)), stores straight from registers.
 // The generic kernel above walks the tile through LDS once per stage and twice more for loading and storing.
 // STRIDED loads go global -> registers; LAST stages its rows (contiguous over the DFT index) through LDS first.
-template <int RA, int RB>
-struct Mix2Geom {
-  static constexpr int R = RA * RB;
-  static constexpr int tmax() { int t = 1; while (2 * t * R <= 4096 && 2 * t <= 256) t *= 2; return t; }
-  static constexpr int TM = tmax();                       // widest tile (columns, a power of two)
-  // threads per workgroup: one DFT slot per thread in the larger step when that fits 384 threads (10 x 10 with 32
-  // columns: 320 threads, every lane busy in both steps), else 256 threads with several slots each
-  static constexpr int BIG = (RA > RB ? RA : RB) * TM;
-  static constexpr int NT = BIG <= 384 ? (BIG + 63) / 64 * 64 : 256;
-  static constexpr int CA = (RB * TM + NT - 1) / NT;      // step-1 slots per thread
-  static constexpr int CB = (RA * TM + NT - 1) / NT;      // step-2 slots per thread
-};
-
+// (Mix2Geom: fft_plan.h)
 template <int RA, int RB, int MODE>
 __global__ __launch_bounds__((Mix2Geom<RA, RB>::NT)) void k_fft_mix2(const float2 *__restrict__ in, float2 *__restrict__ out, MixDesc d) {
   using G = Mix2Geom<RA, RB>;
@@ -650,15 +599,7 @@ __global__ __launch_bounds__((Mix2Geom<RA, RB>::NT)) void k_fft_mix2(const float
 // as FFT_LAST), parks Z in LDS, forms Y from the pairs, transforms inverse (two register steps, as FFT_STRIDED) and
 // stores with the inverse's inter-pass twiddles.  Z is never written to memory and never read twice: one launch, one
 // 16-byte-per-point round trip and one doubled read less per search.
-struct MidDesc {
-  unsigned R, Bc, ndir;           // radix, columns N/R, direct columns Bc/2 + 1
-  int logT, nprev;                // tile width (direct + mirrored halves), earlier forward factors
-  unsigned Rprev[MIX_MAX_PASS];   // forward factors R_1 .. R_{p-1} (column digits, least significant first)
-  unsigned r_hi, r_lo;            // floor(2^64 / R)
-  unsigned Bnext, ntw_hi, ntw_lo; // inverse pass 2: Bc / R'_2 and floor(2^64 / (R * R'_2))
-  int tw_sets;                    // inverse inter-pass twiddle sets per half held in LDS (0: evaluated per output)
-  double w8;                      // 8 / (2N): phase unit of W_{2N}^g
-};
+// (MidDesc: fft_plan.h)
 
 template <int RA, int RB>
 __global__ __launch_bounds__((Mix2Geom<RA, RB>::NT)) void k_fft_mid(const float2 *__restrict__ in, float2 *__restrict__ out, MidDesc d) {
@@ -829,17 +770,10 @@ __global__ __launch_bounds__((Mix2Geom<RA, RB>::NT)) void k_fft_mid(const float2
 }
 
 typedef void (*mid_fn)(const float2 *, float2 *, MidDesc);
-struct MidEntry { unsigned R, RA; int tm, nt; mid_fn fn; size_t lds3; };   // lds3: three-step kernels' dynamic LDS (0: two-step)
-#define MID(RA_, RB_) { RA_ * RB_, RA_, Mix2Geom<RA_, RB_>::TM, Mix2Geom<RA_, RB_>::NT, k_fft_mid<RA_, RB_>, 0 }
-// last forward factors that have the fused kernel (the planner puts the factor with the most twos last)
-static const MidEntry kMid[] = {MID(10, 20), MID(10, 10), MID(16, 16), MID(16, 10), MID(16, 9), MID(16, 8), MID(16, 5), MID(8, 8), MID(8, 5)};
-#undef MID
-static const MidEntry *mid3_lookup(unsigned R);
-static const MidEntry *mid_lookup(unsigned R) {
-  for (const MidEntry &e : kMid)
-    if (e.R == R) return &e;
-  return mid3_lookup(R);
-}
+#define TSDR_X(RA_, RB_) k_fft_mid<RA_, RB_>,
+static const mid_fn kMidFn[] = {TSDR_MID_LIST(TSDR_X)};   // entry i of fft_plan.h:kMid
+#undef TSDR_X
+static_assert(sizeof(kMidFn) / sizeof(kMidFn[0]) == kNMid2, "one kernel per entry of TSDR_MID_LIST");
 
 
 // ---- three register steps per pass: factors of 500 .. 2000 ---------------------------------------------------------------
@@ -854,32 +788,7 @@ static const MidEntry *mid_lookup(unsigned R) {
 // workgroup resident at once), so their number is what counts.  STRIDED loads go global -> registers in T-element runs;
 // LAST reads its rows contiguously (slot order with the column slowest).  Inter-pass twiddles W^(n (Ka + k P)) are linear
 // in k3: one evaluation for the slot's first output, one for the step, then a product per output.
-template <int RA, int RB, int RC, int LOGT>
-struct Mix3Geom {
-  static constexpr int R = RA * RB * RC, T = 1 << LOGT;
-  static constexpr int S1 = RB * RC * T, S2 = RA * RC * T, S3 = RA * RB * T;
-  static constexpr int SMAX = S1 > S2 ? (S1 > S3 ? S1 : S3) : (S2 > S3 ? S2 : S3);
-  static constexpr int NT = (SMAX + 63) / 64 * 64;
-  static_assert(NT <= 1024, "three-step kernel: a step has more slots than a workgroup has threads");
-  static constexpr int PLANE = RB * RC * T + T;
-  static constexpr int VMAX = RA > RB ? (RA > RC ? RA : RC) : (RB > RC ? RB : RC);
-  static constexpr size_t LDS = ((size_t)RA * PLANE + R) * sizeof(float2);
-  // Exchange-tile position of (second digit, third digit n3, column t) within a k1 plane: (n2 RC + n3) T + (t ^ swz(n3)).
-  // The passes that read their rows contiguously (FFT_LAST, the fused middle's forward half, getWelch's accumulator) write
-  // step 1 with the lanes of a wavefront running along n3: unswizzled that is a stride of T float2 -- 16 (8) lanes of a
-  // 16-lane group on the same bank pair, 7.7 (3.8) LDS passes per ds_write_b64 for T = 8 (4), SQ_LDS_BANK_CONFLICT = 3400
-  // cycles per workgroup.  The column is XORed with n3 / 2: 2.0 (1.9) passes there, and the other three access patterns
-  // (step-1 writes with the column fastest, steps 2 and 3: lanes along t, then n3 or k1) stay conflict-free -- n3 is
-  // constant per thread in step 2 and a compile-time constant in step 3, so the swizzle costs a handful of XORs per pass.
-  static __device__ __forceinline__ int swz(int n3) { return (n3 >> 1) & (T - 1); }
-};
-
-// MODE: FFT_STRIDED / FFT_LAST = passes of a multi-pass transform; the three whole-row modes below = rows of R points, T per
-// tile, walked by persistent workgroups (separate instantiations: as run-time branches of one kernel the row store's conjugations
-// and the writers' extra live values cost the accumulator 15-60 %)
-enum { M3_ACC = 10, M3_WF = 11, M3_ROWS = 12,     // getWelch's accumulator | getWaterfall's writer | batched row transforms
-       M3_ACC_IQ = 13, M3_WF_IQ = 14, M3_ROWS_IQ = 15 };   // the same three on integer IQ rows (MixDesc::rows_real = ROWS_SC16 ..): instantiations
-                                                           // of their own, so that the ComplexF32 / real ones keep their registers and occupancy
+// (Mix3Geom and the whole-row modes M3_*: fft_plan.h)
 template <int RA, int RB, int RC, int LOGT, int MODE>
 __global__ __launch_bounds__((Mix3Geom<RA, RB, RC, LOGT>::NT)) void k_fft_mix3(const float2 *__restrict__ in, float2 *__restrict__ out, MixDesc d) {
   using G = Mix3Geom<RA, RB, RC, LOGT>;
@@ -1089,57 +998,19 @@ __global__ __launch_bounds__((Mix3Geom<RA, RB, RC, LOGT>::NT)) void k_fft_mix3(c
   }
 }
 
-typedef void (*mix3_fn)(const float2 *, float2 *, MixDesc);
-struct Mix3Entry { unsigned R; int logT, nt; size_t lds; mix3_fn strided, last, acc, wf, rows, acc_iq, wf_iq, rows_iq; };
-#define MIX3(RA_, RB_, RC_, LT_)                                                                                            \
-  { RA_ * RB_ * RC_, LT_, Mix3Geom<RA_, RB_, RC_, LT_>::NT, Mix3Geom<RA_, RB_, RC_, LT_>::LDS,                               \
-    k_fft_mix3<RA_, RB_, RC_, LT_, FFT_STRIDED>, k_fft_mix3<RA_, RB_, RC_, LT_, FFT_LAST>, k_fft_mix3<RA_, RB_, RC_, LT_, M3_ACC>, \
-    k_fft_mix3<RA_, RB_, RC_, LT_, M3_WF>, k_fft_mix3<RA_, RB_, RC_, LT_, M3_ROWS>, k_fft_mix3<RA_, RB_, RC_, LT_, M3_ACC_IQ>,         \
-    k_fft_mix3<RA_, RB_, RC_, LT_, M3_WF_IQ>, k_fft_mix3<RA_, RB_, RC_, LT_, M3_ROWS_IQ> }
-// 8000-point tiles (64 KiB of LDS + the twiddle table): 1000 x 8 columns, 2000 x 4; 500 x 8 (4000 points)
-// (tiles half as wide -- 32-byte runs -- measured 25.8 / 22.9 us per pass against 18.5 / 19.9 at 2e6 points)
-static const Mix3Entry kMix3[] = {MIX3(10, 10, 10, 3), MIX3(20, 10, 10, 2), MIX3(5, 10, 10, 3)};
-#undef MIX3
-static const Mix3Entry *mix3_lookup(unsigned R) {
-  for (const Mix3Entry &e : kMix3)
-    if (e.R == R) return &e;
-  return nullptr;
-}
-// getWelch's accumulator only (fft_rows_welch: the FFT_LAST kernel with MixDesc::acc; the pass planner does not see these):
-// the power-of-two segment lengths next to the 1024 that k_seg1024 serves -- 2048 = 16 x 16 x 8 (two segments per tile),
-// 4096 = 16 x 16 x 16 (one), 512 = 8 x 8 x 8 (eight), 256 = 8 x 8 x 4 (eight), 128 -- and the round lengths that split into
-// three of the register DFT sizes (4000, 3200, 2500, 1600, 1280, 1200, 768; 960 = 20 x 16 x 3 measured slower than the
-// generic kernel: 108 against 88 us); everything else: the generic LDS-stage kernel
-#define WELCH3(RA_, RB_, RC_, LT_)                                                                                          \
-  { RA_ * RB_ * RC_, LT_, Mix3Geom<RA_, RB_, RC_, LT_>::NT, Mix3Geom<RA_, RB_, RC_, LT_>::LDS, nullptr, nullptr,             \
-    k_fft_mix3<RA_, RB_, RC_, LT_, M3_ACC>, k_fft_mix3<RA_, RB_, RC_, LT_, M3_WF>, k_fft_mix3<RA_, RB_, RC_, LT_, M3_ROWS>,         \
-    k_fft_mix3<RA_, RB_, RC_, LT_, M3_ACC_IQ>, k_fft_mix3<RA_, RB_, RC_, LT_, M3_WF_IQ>, k_fft_mix3<RA_, RB_, RC_, LT_, M3_ROWS_IQ> }
-static const Mix3Entry kWelch3[] = {
-    WELCH3(16, 16, 8, 1), WELCH3(16, 16, 16, 0), WELCH3(8, 8, 8, 3), WELCH3(8, 8, 4, 3), WELCH3(8, 4, 4, 4),   // 2048 4096 512 256 128
-    WELCH3(10, 10, 10, 2), WELCH3(5, 10, 10, 2),                                                               // 1000 500 on half the pass kernels' tiles: row / waterfall modes
-    // (1000: rows 50.5 -> 40.8 us, waterfall 57 -> 47 us, but the accumulator 44 -> 50 us; 2000 on 4000-point tiles lost everywhere)
-    WELCH3(20, 20, 10, 0), WELCH3(25, 10, 10, 0), WELCH3(20, 16, 10, 0), WELCH3(20, 10, 8, 1),                  // 4000 2500 3200 1600
-    WELCH3(16, 16, 5, 1), WELCH3(20, 20, 3, 1), WELCH3(16, 16, 3, 2),                                           // 1280 1200 768
-};
-#undef WELCH3
-static const Mix3Entry *welch3_lookup(unsigned R, bool accumulator) {
-  if (accumulator)
-    if (const Mix3Entry *e = mix3_lookup(R)) return e;   // getWelch: the pass kernels' 8000-point tiles measured better
-  for (const Mix3Entry &e : kWelch3)
-    if (e.R == R) return &e;
-  return mix3_lookup(R);
-}
-// kernels above 64 KiB of dynamic LDS have to be opted in once
-static int mix3_prepare(tsdr_ctx *ctx, const Mix3Entry *e) {
-  for (mix3_fn f : {e->strided, e->last, e->acc, e->wf, e->rows, e->acc_iq, e->wf_iq, e->rows_iq}) {
-    if (!f) continue;
-    int rc = lds_opt_in(ctx, (const void *)f, e->lds);
-    if (rc) return rc;
-  }
-  return TSDR_OK;
-}
-
-
+typedef void (*mix_fn)(const float2 *, float2 *, MixDesc);
+// entry i of fft_plan.h:kMix3, by mode: FFT_STRIDED, FFT_LAST, M3_ACC, M3_WF, M3_ROWS, M3_ACC_IQ, M3_WF_IQ, M3_ROWS_IQ (the row-only entries: no pass kernels)
+struct Mix3Fns { mix_fn fn[8]; };
+#define TSDR_ROWS(RA_, RB_, RC_, LT_)                                                                                      \
+  k_fft_mix3<RA_, RB_, RC_, LT_, M3_ACC>, k_fft_mix3<RA_, RB_, RC_, LT_, M3_WF>, k_fft_mix3<RA_, RB_, RC_, LT_, M3_ROWS>,   \
+  k_fft_mix3<RA_, RB_, RC_, LT_, M3_ACC_IQ>, k_fft_mix3<RA_, RB_, RC_, LT_, M3_WF_IQ>, k_fft_mix3<RA_, RB_, RC_, LT_, M3_ROWS_IQ>
+#define TSDR_X(RA_, RB_, RC_, LT_) {{k_fft_mix3<RA_, RB_, RC_, LT_, FFT_STRIDED>, k_fft_mix3<RA_, RB_, RC_, LT_, FFT_LAST>, TSDR_ROWS(RA_, RB_, RC_, LT_)}},
+#define TSDR_XW(RA_, RB_, RC_, LT_) {{nullptr, nullptr, TSDR_ROWS(RA_, RB_, RC_, LT_)}},
+static const Mix3Fns kMix3Fn[] = {TSDR_MIX3_LIST(TSDR_X) TSDR_WELCH3_LIST(TSDR_XW)};
+#undef TSDR_X
+#undef TSDR_XW
+#undef TSDR_ROWS
+static_assert(sizeof(kMix3Fn) / sizeof(kMix3Fn[0]) == kNMix3, "one set of kernels per entry of TSDR_MIX3_LIST + TSDR_WELCH3_LIST");
 
 // ---- the fused middle (k_fft_mid) with three register steps: last forward factor = first inverse factor = 1000 or 2000 ----
 // Same pairing of direct and mirrored columns, same power-spectrum arithmetic; the two length-R DFTs are k_fft_mix3's
@@ -1261,203 +1132,18 @@ __global__ __launch_bounds__((Mix3Geom<RA, RB, RC, LOGT>::NT)) void k_fft_mid3(c
     }
   }
 }
-#define MID3(RA_, RB_, RC_, LT_) { RA_ * RB_ * RC_, 0, 1 << LT_, Mix3Geom<RA_, RB_, RC_, LT_>::NT, k_fft_mid3<RA_, RB_, RC_, LT_>, \
-                                   Mix3Geom<RA_, RB_, RC_, LT_>::LDS + 2 * (size_t)(1 << LT_) * 4 }
-static const MidEntry kMid3[] = {MID3(20, 10, 10, 2), MID3(10, 10, 10, 3)};
-#undef MID3
-static const MidEntry *mid3_lookup(unsigned R) {
-  for (const MidEntry &e : kMid3)
-    if (e.R == R) return &e;
-  return nullptr;
-}
-typedef void (*mix2_fn)(const float2 *, float2 *, MixDesc);
-struct Mix2Entry { unsigned R, RA; int tm, nt; mix2_fn strided, last; };
-#define MIX2(RA_, RB_)                                                                                     \
-  { RA_ * RB_, RA_, Mix2Geom<RA_, RB_>::TM, Mix2Geom<RA_, RB_>::NT, k_fft_mix2<RA_, RB_, FFT_STRIDED>, k_fft_mix2<RA_, RB_, FFT_LAST> }
-// the factor sizes that have a two-step kernel (RB > 1 everywhere); for a size listed twice the first entry wins.
-// The balanced splits come first: with RA ~ RB one thread owns one DFT of each step and nobody idles, and 10- or
-// 16-point register DFTs keep the kernel near 64 VGPRs; 25 x 5 leaves 3 of 8 lanes without a step-1 DFT at 160 VGPRs.
-static const Mix2Entry kMix2[] = {
-    MIX2(10, 10), MIX2(10, 20), MIX2(10, 5),
-    MIX2(16, 16), MIX2(16, 10), MIX2(16, 9), MIX2(16, 8), MIX2(16, 5), MIX2(25, 10), MIX2(25, 9), MIX2(25, 8),
-    MIX2(25, 5),  MIX2(25, 4),  MIX2(25, 3), MIX2(25, 2), MIX2(10, 9), MIX2(9, 9),   MIX2(9, 8),  MIX2(9, 5),
-    MIX2(8, 8),   MIX2(8, 5),   MIX2(5, 5),
-};
-#undef MIX2
-static const Mix2Entry *mix2_lookup(unsigned R) {
-  for (const Mix2Entry &e : kMix2)
-    if (e.R == R) return &e;
-  return nullptr;
-}
-static size_t mix2_lds(unsigned R, unsigned RA, int logT, int tw_sets = 1) {
-  const size_t T = (size_t)1 << logT, RB = R / RA;
-  const size_t SA = (RB << logT) + (T < 32 ? T : 0);
-  return (std::max((size_t)R * (T + 1), (size_t)RA * SA) + (size_t)(1 + std::max(tw_sets, 1)) * R) * sizeof(float2);
-}
+#define TSDR_X(RA_, RB_, RC_, LT_) k_fft_mid3<RA_, RB_, RC_, LT_>,
+static const mid_fn kMid3Fn[] = {TSDR_MID3_LIST(TSDR_X)};   // entry kNMid2 + i of fft_plan.h:kMid
+#undef TSDR_X
+static_assert(sizeof(kMid3Fn) / sizeof(kMid3Fn[0]) == kNMid - kNMid2, "one kernel per entry of TSDR_MID3_LIST");
+#define TSDR_X(RA_, RB_) {k_fft_mix2<RA_, RB_, FFT_STRIDED>, k_fft_mix2<RA_, RB_, FFT_LAST>},
+static const mix_fn kMix2Fn[][2] = {TSDR_MIX2_LIST(TSDR_X)};   // entry i of fft_plan.h:kMix2, by mode
+#undef TSDR_X
+static_assert(sizeof(kMix2Fn) / sizeof(kMix2Fn[0]) == kNMix2, "one pair of kernels per entry of TSDR_MIX2_LIST");
 
-// ---- planning --------------------------------------------------------------------------------
-struct MixPlan {
-  int p = 0;
-  unsigned R[MIX_MAX_PASS];
-  std::vector<unsigned char> rad[MIX_MAX_PASS];
-};
-
-static void stage_radices(unsigned e2, unsigned e3, unsigned e5, std::vector<unsigned char> &out) {
-  out.clear();
-  while (e5 >= 2) { out.push_back(25); e5 -= 2; }
-  if (e5) {
-    if (e2) { out.push_back(10); --e2; } else out.push_back(5);
-  }
-  while (e3 >= 2) { out.push_back(9); e3 -= 2; }
-  if (e3) out.push_back(3);
-  while (e2 >= 4) { out.push_back(16); e2 -= 4; }
-  if (e2 == 3) out.push_back(8);
-  if (e2 == 2) out.push_back(4);
-  if (e2 == 1) out.push_back(2);
-}
-
-// What one pass through a factor costs relative to the best kernels (every pass moves the same 16 bytes per point;
-// measured on MI355X at 2e6..2e7 points): balanced two-step kernels 1, the 25 x n ones ~1.6, the generic LDS-stage
-// kernel ~2.2.
-static double factor_cost(unsigned R) {
-  if (mix3_lookup(R)) return 1.35;  // one pass through a three-step kernel (measured against the balanced two-step ones)
-  const Mix2Entry *e = mix2_lookup(R);
-  if (!e) return 2.2;
-  return e->RA == 25 ? 1.6 : 1.0;
-}
-
-struct PlanSearch {
-  unsigned ex[3];
-  bool allow_big = true;  // factors of 500 .. 2000 (three-step kernels)
-  int best_p = 0;
-  double best = 1e30;
-  unsigned cur[MIX_MAX_PASS][3], out[MIX_MAX_PASS][3];
-  static unsigned val(const unsigned *e) {
-    unsigned v = 1;
-    for (unsigned i = 0; i < e[0]; ++i) v *= 2;
-    for (unsigned i = 0; i < e[1]; ++i) v *= 3;
-    for (unsigned i = 0; i < e[2]; ++i) v *= 5;
-    return v;
-  }
-  // factors in non-increasing order (the order is fixed afterwards), depth-first with a cost bound
-  void go(int depth, unsigned cap, double cost) {
-    if (!(ex[0] | ex[1] | ex[2])) {
-      if (depth == 1 && val(cur[0]) > 256) return;  // the three-step kernels are passes of a multi-pass transform only
-      // ties: prefer a factor carrying 2^4 (it goes last: every stride a multiple of 16 elements)
-      unsigned m2 = 0;
-      for (int i = 0; i < depth; ++i) m2 = std::max(m2, std::min(cur[i][0], 4u));
-      const double c = cost - 0.01 * m2;
-      if (c < best - 1e-9) {
-        best = c;
-        best_p = depth;
-        for (int i = 0; i < depth; ++i) for (int j = 0; j < 3; ++j) out[i][j] = cur[i][j];
-      }
-      return;
-    }
-    if (depth == MIX_MAX_PASS) return;
-    {
-      double rem = 1.0;
-      for (unsigned i = 0; i < ex[0]; ++i) rem *= 2;
-      for (unsigned i = 0; i < ex[1]; ++i) rem *= 3;
-      for (unsigned i = 0; i < ex[2]; ++i) rem *= 5;
-      const double need = std::max(1.0, std::ceil(std::log(rem) / std::log((double)cap) - 1e-9));  // passes still to come
-      if (depth + (int)need > MIX_MAX_PASS || cost + need >= best + 0.05) return;
-    }
-    for (unsigned a = 0; a <= ex[0]; ++a)
-      for (unsigned b = 0; b <= ex[1]; ++b)
-        for (unsigned c = 0; c <= ex[2]; ++c) {
-          const unsigned e[3] = {a, b, c};
-          if (a > 8 || b > 5 || c > 3) continue;
-          const unsigned R = val(e);
-          if (R < 2 || R > cap) continue;
-          if (R > 256 && !(allow_big && mix3_lookup(R))) continue;
-          std::vector<unsigned char> rad;
-          stage_radices(a, b, c, rad);
-          if (rad.size() > MIX_MAX_STAGE) continue;
-          for (int j = 0; j < 3; ++j) { cur[depth][j] = e[j]; ex[j] -= e[j]; }
-          go(depth + 1, R, cost + factor_cost(R));
-          for (int j = 0; j < 3; ++j) ex[j] += e[j];
-        }
-  }
-};
-
-// true when N = 2^a 3^b 5^c (N >= 2) and a pass split with every factor <= 256 exists.  The split minimises the
-// summed pass costs above; the factor with the most twos goes last, the others largest first.
-static bool fft_mixed_plan_search(size_t N, MixPlan *plan, bool allow_big);
-bool fft_mixed_plan(size_t N, MixPlan *plan, bool allow_big = true) {  // the search runs once per length
-  static std::mutex mu;
-  static std::unordered_map<size_t, std::pair<bool, MixPlan>> cache[2];
-  std::lock_guard<std::mutex> g(mu);
-  auto &c = cache[allow_big ? 1 : 0];
-  auto it = c.find(N);
-  if (it == c.end()) {
-    if (c.size() > 4096) c.clear();
-    MixPlan pl;
-    const bool ok = fft_mixed_plan_search(N, &pl, allow_big);
-    it = c.emplace(N, std::make_pair(ok, pl)).first;
-  }
-  if (it->second.first) *plan = it->second.second;
-  return it->second.first;
-}
-static bool fft_mixed_plan_search(size_t N, MixPlan *plan, bool allow_big) {
-  if (N < 2 || N >= (size_t(1) << 31)) return false;
-  PlanSearch ps;
-  ps.allow_big = allow_big;
-  ps.ex[0] = ps.ex[1] = ps.ex[2] = 0;
-  const unsigned pr[3] = {2, 3, 5};
-  size_t m = N;
-  for (int i = 0; i < 3; ++i)
-    while (m % pr[i] == 0) { m /= pr[i]; ++ps.ex[i]; }
-  if (m != 1) return false;
-  ps.go(0, allow_big ? 2000 : 256, 0.0);
-  if (!ps.best_p) return false;
-  const int p = ps.best_p;
-  int last = 0;
-  for (int i = 1; i < p; ++i) {
-    const unsigned ti = std::min(ps.out[i][0], 4u), tl = std::min(ps.out[last][0], 4u);
-    if (ti > tl || (ti == tl && PlanSearch::val(ps.out[i]) > PlanSearch::val(ps.out[last]))) last = i;
-  }
-  plan->p = p;
-  int o = 0;
-  for (int i = 0; i < p; ++i) {
-    if (i == last) continue;
-    plan->R[o] = PlanSearch::val(ps.out[i]);
-    stage_radices(ps.out[i][0], ps.out[i][1], ps.out[i][2], plan->rad[o]);
-    ++o;
-  }
-  plan->R[o] = PlanSearch::val(ps.out[last]);
-  stage_radices(ps.out[last][0], ps.out[last][1], ps.out[last][2], plan->rad[o]);
-  return true;
-}
-
-int fft_passes(size_t N) {
-  if (is_pow2(N)) { int l = 0; while (((size_t)1 << l) < N) ++l; return l <= 8 ? 1 : (l + 7) / 8; }
-  MixPlan pl;
-  return fft_mixed_plan(N, &pl) ? pl.p : 0;
-}
-
-int fft_mixed_passes(tsdr_ctx *ctx, size_t N, size_t batch);
-bool fft_mixed_ok(size_t N) {
-  MixPlan pl;
-  return fft_mixed_plan(N, &pl);
-}
-
-static int floor_log2(unsigned v) { int l = 0; while ((2u << l) <= v) ++l; return l; }
-static int ceil_log2(unsigned v) { int l = 0; while ((1u << l) < v) ++l; return l; }
-
-// Tile width: as wide as 4096 elements allow, narrowed (not below 16 columns = 128-byte runs) until the launch has
-// enough workgroups to keep several resident per CU -- a workgroup is a chain of dependent LDS stages, and with one
-// or two of them per CU nothing hides that latency.
-static int pick_logT(int maxlog, int minlog, size_t other, size_t span) {
-  int logT = std::max(maxlog, 0);
-  while (logT > minlog && other * ceil_div(span, (size_t)1 << logT) < 2048) --logT;
-  return logT;
-}
-
-static size_t mix_lds(unsigned R, int logT) {
-  return ((size_t)R * ((1u << logT) + 1) + R) * sizeof(float2) + ((size_t)R * 2 + 15) / 16 * 16;
-}
-
+// ---- the launcher: the only place that launches a pass kernel ----------------------------------------------------------------------
+// (what is launched, on which buffers, with which tables: fft_plan.h.  A plan's invariants -- indices inside the tables they were
+// made from, a buffer behind every role a step names -- are asserts: no caller can break them.)
 // W_{R*Rn}^(col*k) at [k * Rn + col], k < R, col < Rn (built once per pair in extended precision, then resident)
 static int get_twg(tsdr_ctx *ctx, unsigned R, unsigned Rn, const float2 **out) {
   const unsigned key = (R << 16) | Rn;
@@ -1478,368 +1164,132 @@ static int get_twg(tsdr_ctx *ctx, unsigned R, unsigned Rn, const float2 **out) {
   return TSDR_OK;
 }
 
-// The three-step kernels (factors of 500 .. 2000) trade pass count for narrow tiles -- 8000 points are 1000 x 8 columns,
-// i.e. 64-byte runs.  That wins while a pass is latency-bound and its data cache-resident (2e6 points, 16 MB: two passes of
-// 16 us instead of three of 12), and loses once passes stream from HBM (2e7 points: 128-174 us per pass against 75-85 us
-// for the two-step kernels' 256-byte runs).  So: only for transforms of at most 2^22 points in all.
-static bool fft_big_ok(tsdr_ctx *ctx, size_t total_points) {
-  return ctx->opt_fft_big && !ctx->opt_fft_no_mix2 && total_points <= (size_t(1) << 22);
-}
-
-int fft_mixed_passes(tsdr_ctx *ctx, size_t N, size_t batch) {   // the plan fft_mixed_ex makes for this call
-  MixPlan pl;
-  return fft_mixed_plan(N, &pl, fft_big_ok(ctx, N * batch)) ? pl.p : 0;
-}
-
-// in/out may alias.  Uses WS_FFT_B when more than one pass is needed (callers must not hand WS_FFT_B buffers in).
-// src_mode/src_n: fused first-pass loader (fft_dev.h), batch == 1 and p > 1 only; keep: complex outputs per
-// transform the caller will look at (0 = all).
-//   force: run this pass split instead of the planner's.  first_pass > 0: `in` already holds the output of pass
-//   first_pass - 1 of that split (the fused autocorrelation middle wrote it); the remaining strided passes then run in
-//   place in `in`.  work_out != nullptr: stop before the last pass and hand back the buffer the strided passes left
-//   their result in.
-static int fft_mixed_ex(tsdr_ctx *ctx, const float2 *in, float2 *out, size_t N, size_t batch, int dir, float scale, int src_mode,
-                        size_t src_n, size_t keep, const FftEpilogue *epi, const float2 *src_aux, const MixPlan *force,
-                        int first_pass, float2 **work_out, float src_scale = 1.0f) {
-  MixPlan pl;
-  if (force) pl = *force;
-  else if (!fft_mixed_plan(N, &pl, fft_big_ok(ctx, N * batch)))
-    return set_err(ctx, TSDR_EINVAL, "fft_mixed: length %zu is not 2^a*3^b*5^c", N);
-  if (batch == 0) return TSDR_OK;
-  if (N * batch >= (size_t(1) << 40)) return set_err(ctx, TSDR_EINVAL, "fft: batch too large");
-  const int p = pl.p;
-  // (the integer IQ loaders are element-wise like SRC_C2C: any batch)
-  if (src_mode != SRC_C2C && ((batch != 1 && !src_is_cplx_int(src_mode)) || p == 1)) return set_err(ctx, TSDR_EINVAL, "fft: fused loader needs one multi-pass transform");
-  MixDesc d{};
-  d.dir = dir < 0 ? -1 : 1;
-  d.N = N;
-  d.src_mode = SRC_C2C;
-  d.keep = keep ? keep : N;
-  d.src_w8 = src_mode == SRC_POWER && !is_pow2(src_n) ? 4.0 / (double)src_n : src_is_int_iq(src_mode) ? (double)src_scale : 0.0;
-  d.src_aux = src_aux;
-  if (epi && (batch != 1 || p == 1)) return set_err(ctx, TSDR_EINVAL, "fft: epilogue needs one multi-pass transform");
-  auto set_radix = [&](int i) {
-    d.R = pl.R[i];
-    d.nst = (int)pl.rad[i].size();
-    for (int s = 0; s < d.nst; ++s) d.rad[s] = pl.rad[i][s];
-    const unsigned __int128 inv = ((unsigned __int128)1 << 64) / d.R;
-    d.r_hi = (unsigned)(inv >> 32);
-    d.r_lo = (unsigned)inv;
-  };
-  if (p == 1) {
-    d.mode = FFT_ROWS;
-    set_radix(0);
-    d.logT = pick_logT(std::min(8, floor_log2(4096u / d.R)), 0, 1, batch);
-    d.scale = scale;
-    d.rows = (unsigned)batch;
-    if (batch >= (size_t(1) << 32)) return set_err(ctx, TSDR_EINVAL, "fft: too many rows");
-    const unsigned grid = (unsigned)ceil_div(batch, (size_t)1 << d.logT);
-    TSDR_LAUNCH(ctx, "fftm_rows", k_fft_mix, dim3(grid), dim3(256), mix_lds(d.R, d.logT), in, out, d);
-    return TSDR_OK;
-  }
-  float2 *work = first_pass > 0 ? const_cast<float2 *>(in) : (float2 *)ctx->scratch(WS_FFT_B, N * batch * sizeof(float2));
-  if (!work) return TSDR_ENOMEM;
-  size_t P = 1;  // R_1..R_{i-1}
-  size_t B = N;
-  const float2 *src = in;
-  for (int i = 0; i < first_pass && i < p - 1; ++i) { B /= pl.R[i]; P *= pl.R[i]; }
-  static const char *const kStridedName[MIX_MAX_PASS] = {"fftm_strided1", "fftm_strided2", "fftm_strided3",
-                                                         "fftm_strided4", "fftm_strided5", "fftm_strided6"};
-  for (int i = first_pass; i < p - 1; ++i) {
-    set_radix(i);
-    B /= d.R;
-    d.mode = FFT_STRIDED;
-    d.src_mode = i == 0 ? src_mode : SRC_C2C;
-    d.src_n = src_n;
-    const Mix3Entry *m3 = ctx->opt_fft_no_mix2 ? nullptr : mix3_lookup(d.R);
-    const Mix2Entry *m2 = (ctx->opt_fft_no_mix2 || m3) ? nullptr : mix2_lookup(d.R);
-    // (the two- and three-step kernels keep their full tile: a narrower one leaves most threads without a step-1 DFT)
-    d.logT = m3 ? m3->logT
-                : pick_logT(std::min({8, m2 ? floor_log2((unsigned)m2->tm) : floor_log2(4096u / d.R), ceil_log2((unsigned)B)}),
-                            m2 ? 8 : 4, batch * P, B);
-    d.scale = 1.0f;
-    d.A = (unsigned)P;
-    d.B = (unsigned)B;
-    d.tiles = (unsigned)ceil_div(B, (size_t)1 << d.logT);
-    d.Bnext = (unsigned)(B / pl.R[i + 1]);
-    d.Pprev = (unsigned)P;
-    {
-      const unsigned __int128 inv = ((unsigned __int128)1 << 64) / ((unsigned __int128)P * d.R * pl.R[i + 1]);
-      d.ntw_hi = (unsigned)(inv >> 32);
-      d.ntw_lo = (unsigned)inv;
-    }
-    d.nprev = i;
-    size_t wgt = 1;
-    for (int j = 0; j < i; ++j) { d.Rprev[j] = pl.R[j]; d.Wprev[j] = (unsigned)wgt; wgt *= pl.R[j]; }
-    const size_t grid = batch * d.A * d.tiles;
-    if (grid >= (size_t(1) << 31)) return set_err(ctx, TSDR_EINVAL, "fft: grid too large");
-    d.tw_sets = 0;
-    d.twg = nullptr;
-    if (m3) {
-      int rc3 = mix3_prepare(ctx, m3);
-      if (rc3) return rc3;
-      TSDR_LAUNCH(ctx, kStridedName[i], m3->strided, dim3((unsigned)grid), dim3(m3->nt), m3->lds, src, work, d);
-    } else if (m2) {
-      // how the two-step kernel gets its inter-pass twiddles (see the kernel): sets in LDS, or the column table
-      const unsigned T = 1u << d.logT;
-      if (d.Bnext % T == 0) d.tw_sets = 1;
-      else if (d.Bnext == 1) { const int rc = get_twg(ctx, d.R, d.B, &d.twg); if (rc) return rc; }
-      else if ((T - 1) / d.Bnext + 2 <= 4) d.tw_sets = (int)((T - 1) / d.Bnext + 2);
-      TSDR_LAUNCH(ctx, kStridedName[i], m2->strided, dim3((unsigned)grid), dim3(m2->nt), mix2_lds(d.R, m2->RA, d.logT, d.tw_sets), src, work, d);
-    } else {
-      TSDR_LAUNCH(ctx, kStridedName[i], k_fft_mix, dim3((unsigned)grid), dim3(256), mix_lds(d.R, d.logT), src, work, d);
-    }
-    src = work;
-    P *= d.R;
-  }
-  if (work_out) { *work_out = work; return TSDR_OK; }
-  set_radix(p - 1);
-  d.mode = FFT_LAST;
-  d.src_mode = SRC_C2C;
-  if (epi) d.epi = *epi;
-  d.R1 = pl.R[0];
-  const Mix3Entry *m3 = ctx->opt_fft_no_mix2 ? nullptr : mix3_lookup(d.R);
-  const Mix2Entry *m2 = (ctx->opt_fft_no_mix2 || m3) ? nullptr : mix2_lookup(d.R);
-  d.logT = m3 ? m3->logT
-              : pick_logT(std::min({8, m2 ? floor_log2((unsigned)m2->tm) : floor_log2(4096u / d.R), ceil_log2(d.R1)}), m2 ? 8 : 4,
-                          batch * (P / pl.R[0]), d.R1);
-  d.scale = scale;
-  d.Pprev = (unsigned)P;
-  d.nprev = p - 1;
-  {
-    size_t wgt = 1;
-    for (int j = 0; j < p - 1; ++j) { d.Rprev[j] = pl.R[j]; d.Wprev[j] = (unsigned)wgt; wgt *= pl.R[j]; }
-  }
-  d.Aprime = (unsigned)(P / pl.R[0]);
-  d.k1tiles = (unsigned)ceil_div((size_t)d.R1, (size_t)1 << d.logT);
-  const size_t grid = batch * d.Aprime * d.k1tiles;
-  if (grid >= (size_t(1) << 31)) return set_err(ctx, TSDR_EINVAL, "fft: grid too large");
-  if (m3) {
-    int rc3 = mix3_prepare(ctx, m3);
-    if (rc3) return rc3;
-    TSDR_LAUNCH(ctx, "fftm_last", m3->last, dim3((unsigned)grid), dim3(m3->nt), m3->lds, (const float2 *)work, out, d);
-  } else if (m2) {
-    TSDR_LAUNCH(ctx, "fftm_last", m2->last, dim3((unsigned)grid), dim3(m2->nt), mix2_lds(d.R, m2->RA, d.logT), (const float2 *)work, out, d);
-  } else {
-    TSDR_LAUNCH(ctx, "fftm_last", k_fft_mix, dim3((unsigned)grid), dim3(256), mix_lds(d.R, d.logT), (const float2 *)work, out, d);
+// kernels above 64 KiB of dynamic LDS have to be opted in once: every mode of a three-step entry together
+static int mix3_prepare(tsdr_ctx *ctx, int inst) {
+  for (mix_fn f : kMix3Fn[inst].fn) {
+    if (!f) continue;
+    int rc = lds_opt_in(ctx, (const void *)f, kMix3[inst].lds);
+    if (rc) return rc;
   }
   return TSDR_OK;
 }
 
+// Launches ONE step: the plan's sink (FftPlan::sink), called the moment a step is complete, so that the planner fills the next
+// pass's descriptor while this one runs -- as the drivers did that decided while they launched.
+struct FftBufs { tsdr_ctx *ctx; float2 *buf[5]; };   // buf: by FftBuf; FB_WORK is taken at the first step that names it
+static int launch_step(void *user, const FftPlan &pl, const FftStep &s) {
+  FftBufs &L = *static_cast<FftBufs *>(user);
+  tsdr_ctx *ctx = L.ctx;
+  float2 *const *buf = L.buf;
+  if (pl.work_bytes && !L.buf[FB_WORK]) {
+    L.buf[FB_WORK] = (float2 *)ctx->scratch(WS_FFT_B, pl.work_bytes);
+    if (!L.buf[FB_WORK]) return TSDR_ENOMEM;
+  }
+  assert(s.src != FB_NONE && buf[s.src] && (s.dst == FB_NONE || buf[s.dst]));
+  const float2 *src = buf[s.src];
+  float2 *dst = buf[s.dst];
+  const dim3 grid(s.grid), block(s.block);
+  if (s.kernel == FK_PASS) {
+    assert(s.inst >= 1 && s.inst <= 8 && s.mode >= FFT_STRIDED && s.mode <= FFT_ROWS);
+    if (int rc = ensure_tw_small(ctx)) return rc;
+    TSDR_LAUNCH(ctx, s.name, fft_pass_kernel(s.mode, s.inst), grid, block, s.lds, src, dst, s.p.pass, (const float2 *)ctx->tw_small);
+  } else if (s.kernel == FK_MID || s.kernel == FK_MID3) {
+    assert(s.inst >= 0 && s.inst < kNMid && (s.inst >= kNMid2) == (s.kernel == FK_MID3));
+    const mid_fn fn = s.kernel == FK_MID ? kMidFn[s.inst] : kMid3Fn[s.inst - kNMid2];
+    if (s.opt_in)
+      if (int rc = lds_opt_in(ctx, (const void *)fn, s.lds)) return rc;
+    TSDR_LAUNCH(ctx, s.name, fn, grid, block, s.lds, src, dst, s.p.mid);
+  } else {
+    mix_fn fn = k_fft_mix;
+    if (s.kernel == FK_MIX2) {
+      assert(s.inst >= 0 && s.inst < kNMix2 && (s.mode == FFT_STRIDED || s.mode == FFT_LAST));
+      fn = kMix2Fn[s.inst][s.mode];
+    } else if (s.kernel == FK_MIX3) {
+      assert(s.inst >= 0 && s.inst < kNMix3 && (s.mode <= FFT_LAST || (s.mode >= M3_ACC && s.mode <= M3_ROWS_IQ)));
+      fn = kMix3Fn[s.inst].fn[s.mode <= FFT_LAST ? s.mode : s.mode - M3_ACC + 2];
+    }
+    assert(fn && s.kernel >= FK_MIX && s.kernel <= FK_MIX3);   // (the row-only entries have no pass kernels, and no plan asks for one)
+    if (s.opt_in)
+      if (int rc = s.kernel == FK_MIX3 ? mix3_prepare(ctx, s.inst) : lds_opt_in(ctx, (const void *)fn, s.lds)) return rc;
+    if (s.twg_R) {   // the one pointer inside a descriptor that is the launcher's to set
+      MixDesc d = s.p.mix;
+      if (int rc = get_twg(ctx, s.twg_R, s.twg_Rn, &d.twg)) return rc;
+      TSDR_LAUNCH(ctx, s.name, fn, grid, block, s.lds, src, dst, d);
+    } else {
+      TSDR_LAUNCH(ctx, s.name, fn, grid, block, s.lds, src, dst, s.p.mix);
+    }
+  }
+  return TSDR_OK;
+}
 
+// runs plan(pl) with the launcher as the plan's sink; pl.nsteps then says how many steps were launched
+template <class Plan>
+static int fft_launch(tsdr_ctx *ctx, const float2 *in, float2 *out, float2 *mid, Plan &&plan, FftPlan &pl) {
+  FftBufs L{ctx, {nullptr, const_cast<float2 *>(in), out, nullptr, mid}};
+  pl.sink = launch_step;
+  pl.user = &L;
+  plan(pl);
+  if (pl.status) return pl.err[0] ? set_err(ctx, pl.status, "%s", pl.err) : pl.status;
+  if (pl.copy_bytes && in != out) TSDR_HIP(ctx, hipMemcpyAsync(out, in, pl.copy_bytes, hipMemcpyDeviceToDevice, ctx->stream));
+  return TSDR_OK;
+}
+
+// ---- host entry points (fft_dev.h) ------------------------------------------------------------------------------------------------
+int fft_run(tsdr_ctx *ctx, const FftReq &q) {
+  FftPlan pl;
+  return fft_launch(ctx, q.in, q.out, nullptr, [&](FftPlan &p) { plan_fft(p, q, fft_opts(ctx)); }, pl);
+}
+
+int fft_run_autocorr(tsdr_ctx *ctx, const FftReq &q, float2 *Zbuf, bool *done) {
+  FftPlan pl;
+  int rc = fft_launch(ctx, q.in, q.out, Zbuf, [&](FftPlan &p) { plan_autocorr(p, q, fft_opts(ctx)); }, pl);
+  *done = !rc && pl.nsteps > 0;
+  return rc;
+}
+
+// the whole-row launches: *did = false (nothing launched) when the length or count is not one they serve
+static int rows_run(tsdr_ctx *ctx, RowsReq r, const SigSrc &sig, size_t N, size_t rows, bool *did, unsigned *grid = nullptr) {
+  r.kind = sig.kind; r.sig_scale = sig.scale; r.N = N; r.rows = rows;
+  FftPlan pl;
+  int rc = fft_launch(ctx, sig.c32(), nullptr, nullptr, [&](FftPlan &p) { plan_rows(p, r, fft_opts(ctx)); }, pl);
+  *did = !rc && pl.nsteps > 0;
+  if (*did && grid) *grid = pl.step[0].grid;
+  return rc;
+}
 // getWelch's accumulation for any 2^a 3^b 5^c segment length up to 4096 without writing a segment spectrum: *nparts partial
 // power spectra of N floats each (natural order) land in `part` (room for fft_rows_welch_parts() of them)
-unsigned fft_rows_welch_parts(tsdr_ctx *ctx) { return (unsigned)(ctx->cu_count > 0 ? ctx->cu_count : 256) * 3u; }
+unsigned fft_rows_welch_parts(tsdr_ctx *ctx) { return welch_parts(fft_opts(ctx)); }
 int fft_rows_welch(tsdr_ctx *ctx, const SigSrc &sig, size_t N, size_t nbSeg, float *part, unsigned *nparts, bool *did) {
-  *did = false;
-  if (N < 2 || N > 4096 || nbSeg == 0 || nbSeg >= (size_t(1) << 31)) return TSDR_OK;
-  // the whole segment as ONE factor of the generic LDS-stage kernel (the pass planner caps factors at 256 / 2000: its costs
-  // are those of HBM-sized passes)
-  unsigned ex[3] = {0, 0, 0};
-  {
-    const unsigned pr[3] = {2, 3, 5};
-    size_t m = N;
-    for (int i = 0; i < 3; ++i)
-      while (m % pr[i] == 0) { m /= pr[i]; ++ex[i]; }
-    if (m != 1) return TSDR_OK;
-  }
-  std::vector<unsigned char> rad;
-  stage_radices(ex[0], ex[1], ex[2], rad);
-  if (rad.size() > MIX_MAX_STAGE) return TSDR_OK;
-  MixDesc d{};
-  d.dir = -1; d.N = N; d.src_mode = SRC_C2C; d.keep = N; d.mode = FFT_ROWS; d.scale = 1.0f;
-  d.R = (unsigned)N;
-  d.nst = (int)rad.size();
-  for (int s = 0; s < d.nst; ++s) d.rad[s] = rad[s];
-  const unsigned __int128 inv = ((unsigned __int128)1 << 64) / d.R;
-  d.r_hi = (unsigned)(inv >> 32);
-  d.r_lo = (unsigned)inv;
-  d.logT = floor_log2(4096u / d.R);
-  d.rows = (unsigned)nbSeg;
-  d.acc = part;
-  d.rows_real = rows_of(sig.kind);
-  if (sig.is_int()) d.src_w8 = (double)sig.scale;
-  if (const Mix3Entry *m3 = ctx->opt_fft_no_mix2 ? nullptr : welch3_lookup(d.R, true)) {
-    // 500 / 1000 / 2000 (and 256 / 512 / 2048 / 4096 / 4000): the three-register-step kernel, 8 (4, 2, 1) segments per workgroup
-    int rc3 = mix3_prepare(ctx, m3);
-    if (rc3) return rc3;
-    d.logT = m3->logT;
-    d.mode = FFT_LAST;
-    const unsigned ntiles3 = (unsigned)ceil_div(nbSeg, (size_t)1 << d.logT);
-    // (at most fft_rows_welch_parts() workgroups -- the caller's buffer holds that many partial spectra --, i.e. three per CU:
-    // every partial is one more row for k_welch_sum to add, and the short lengths' small tiles would otherwise put eight
-    // workgroups on a CU)
-    const unsigned per_cu3 = (unsigned)std::max<size_t>(1, std::min<size_t>(3, (size_t)(160 * 1024) / m3->lds));
-    const unsigned grid3 = std::min({ntiles3, (unsigned)(ctx->cu_count > 0 ? ctx->cu_count : 256) * per_cu3, fft_rows_welch_parts(ctx)});
-    TSDR_LAUNCH(ctx, "welch_rows_acc3", d.rows_real > ROWS_REAL ? m3->acc_iq : m3->acc, dim3(grid3), dim3(m3->nt), m3->lds, sig.c32(), (float2 *)nullptr, d);
-    *nparts = grid3;
-    *did = true;
-    return TSDR_OK;
-  }
-  const size_t lds = mix_lds(d.R, d.logT);
-  if (lds > 64 * 1024) {  // (4096-point tiles + tables: above what a kernel gets without opting in)
-    int rco = lds_opt_in(ctx, (const void *)k_fft_mix, lds);
-    if (rco) return rco;
-  }
-  const unsigned ntiles = (unsigned)ceil_div(nbSeg, (size_t)1 << d.logT);
-  const unsigned per_cu = (unsigned)std::max<size_t>(1, std::min<size_t>(3, (size_t)(150 * 1024) / lds));
-  const unsigned grid = std::min(ntiles, (unsigned)(ctx->cu_count > 0 ? ctx->cu_count : 256) * per_cu);
-  TSDR_LAUNCH(ctx, "welch_rows_acc", k_fft_mix, dim3(grid), dim3(256), lds, sig.c32(), (float2 *)nullptr, d);
-  *nparts = grid;
-  *did = true;
-  return TSDR_OK;
+  RowsReq r;
+  r.what = ROWS_TO_WELCH; r.acc = part;
+  return rows_run(ctx, r, sig, N, nbSeg, did, nparts);
 }
-
 // Batched row transforms (tsdr_fft_c2c with batch > 1) of the lengths the three-step kernels serve, in ONE launch: a row never
 // leaves the chip between its steps.  (The pass engines split a 512 .. 4096-point row into two passes whose strided one has only
 // 16-64 columns to work on: 67-197 us for 1e7 points against 35-50 us here; rows up to 256 points are one pass there already.)
 int fft_rows_store(tsdr_ctx *ctx, const SigSrc &in, float2 *out, size_t N, size_t batch, int dir, float scale, bool *did) {
-  *did = false;
-  if (N <= 256 || N > 4096 || batch < 2 || batch >= (size_t(1) << 31) || ctx->opt_fft_no_mix2) return TSDR_OK;
-  const Mix3Entry *m3 = welch3_lookup((unsigned)N, false);
-  if (!m3) return TSDR_OK;
-  MixDesc d{};
-  d.dir = dir < 0 ? -1 : 1; d.N = N; d.src_mode = SRC_C2C; d.keep = N; d.mode = FFT_LAST; d.scale = scale;
-  d.R = (unsigned)N;
-  const unsigned __int128 inv = ((unsigned __int128)1 << 64) / d.R;
-  d.r_hi = (unsigned)(inv >> 32);
-  d.r_lo = (unsigned)inv;
-  d.logT = m3->logT;
-  d.rows = (unsigned)batch;
-  d.rows_out = out;
-  d.rows_real = rows_of(in.kind);
-  if (in.is_int()) d.src_w8 = (double)in.scale;   // (forward only: no conjugation on the way in)
-  int rc = mix3_prepare(ctx, m3);
-  if (rc) return rc;
-  const unsigned ntiles = (unsigned)ceil_div(batch, (size_t)1 << d.logT);
-  const unsigned per_cu = (unsigned)std::max<size_t>(1, std::min<size_t>(3, (size_t)(160 * 1024) / m3->lds));
-  const unsigned grid = std::min(ntiles, (unsigned)(ctx->cu_count > 0 ? ctx->cu_count : 256) * per_cu);
-  TSDR_LAUNCH(ctx, "fft_rows3", d.rows_real > ROWS_REAL ? m3->rows_iq : m3->rows, dim3(grid), dim3(m3->nt), m3->lds, in.c32(), (float2 *)nullptr, d);
-  *did = true;
-  return TSDR_OK;
+  RowsReq r;
+  r.what = ROWS_TO_STORE; r.rows_out = out; r.dir = dir; r.scale = scale;
+  return rows_run(ctx, r, in, N, batch, did);
 }
-
 // getWaterfall for the segment lengths the three-step kernels serve (1024 has k_seg1024): segments -> Float64 power spectra,
 // fftshifted, in ONE launch -- the segment spectra never reach HBM (the route through a batched FFT + k_waterfall writes and
 // re-reads them: 109-250 us per C2 buffer at 512 .. 4096 against 40-60 us here)
 int fft_rows_waterfall(tsdr_ctx *ctx, const SigSrc &sig, size_t N, size_t nbSeg, double *wf, bool *did) {
-  *did = false;
-  if (N < 2 || N > 4096 || nbSeg == 0 || nbSeg >= (size_t(1) << 31) || ctx->opt_fft_no_mix2) return TSDR_OK;
-  const Mix3Entry *m3 = welch3_lookup((unsigned)N, false);
-  if (!m3) return TSDR_OK;
-  MixDesc d{};
-  d.dir = -1; d.N = N; d.src_mode = SRC_C2C; d.keep = N; d.mode = FFT_LAST; d.scale = 1.0f;
-  d.R = (unsigned)N;
-  const unsigned __int128 inv = ((unsigned __int128)1 << 64) / d.R;
-  d.r_hi = (unsigned)(inv >> 32);
-  d.r_lo = (unsigned)inv;
-  d.logT = m3->logT;
-  d.rows = (unsigned)nbSeg;
-  d.wf = wf;
-  d.rows_real = rows_of(sig.kind);
-  if (sig.is_int()) d.src_w8 = (double)sig.scale;
-  int rc = mix3_prepare(ctx, m3);
-  if (rc) return rc;
-  const unsigned ntiles = (unsigned)ceil_div(nbSeg, (size_t)1 << d.logT);
-  const unsigned per_cu = (unsigned)std::max<size_t>(1, (size_t)(160 * 1024) / m3->lds);
-  const unsigned grid = std::min(ntiles, (unsigned)(ctx->cu_count > 0 ? ctx->cu_count : 256) * per_cu);
-  TSDR_LAUNCH(ctx, "waterfall_rows3", d.rows_real > ROWS_REAL ? m3->wf_iq : m3->wf, dim3(grid), dim3(m3->nt), m3->lds, sig.c32(), (float2 *)nullptr, d);
-  *did = true;
-  return TSDR_OK;
+  RowsReq r;
+  r.what = ROWS_TO_WATERFALL; r.wf = wf;
+  return rows_run(ctx, r, sig, N, nbSeg, did);
 }
 
-int fft_mixed(tsdr_ctx *ctx, const float2 *in, float2 *out, size_t N, size_t batch, int dir, float scale, int src_mode,
-              size_t src_n, size_t keep, const FftEpilogue *epi, const float2 *src_aux, float src_scale) {
-  return fft_mixed_ex(ctx, in, out, N, batch, dir, scale, src_mode, src_n, keep, epi, src_aux, nullptr, 0, nullptr, src_scale);
+// what the planner answers about a length
+int fft_passes(size_t N) { return fft_split(N, true); }
+bool fft_mixed_ok(size_t N) {
+  MixPlan pl;
+  return fft_mixed_plan(N, &pl);
 }
-
-// The circular autocorrelation of n = 2*Mc real samples (x, or abs2 of IQ formed while loading) as
-//   forward passes 1..p-1  ->  [last forward pass + power spectrum + first inverse pass] (k_fft_mid)  ->  inverse passes 2..p
-// with the epilogue (abs2 / 10log10 of the wanted lags, optional findmax) on the last one.  *done = false (nothing
-// launched) when this length has no fused middle: the caller then runs the two transforms separately.
-int fft_mixed_autocorr(tsdr_ctx *ctx, const float2 *x, int src_mode, size_t src_n, size_t Mc, float2 *Zbuf, float2 *zbuf,
-                       float scale, size_t keep, const FftEpilogue *epi, bool *done, float src_scale) {
-  *done = false;
-  MixPlan F;
-  if (ctx->opt_fft_no_mix2 || !fft_mixed_plan(Mc, &F, fft_big_ok(ctx, Mc)) || F.p < 2 || Mc >= (size_t(1) << 31)) return TSDR_OK;
-  const int p = F.p;
-  // the factor that goes LAST in the forward split (and first in the inverse one) must have the fused kernel: of those
-  // that do, the one with the most twos (as the planner's own rule); the others keep their order
-  {
-    auto twos = [&](int i) { unsigned v = F.R[i], t = 0; while (v % 2 == 0 && t < 4) { v /= 2; ++t; } return t; };
-    int pick = -1;
-    for (int i = 0; i < p; ++i)
-      if (mid_lookup(F.R[i]) && (pick < 0 || twos(i) > twos(pick) || (twos(i) == twos(pick) && F.R[i] > F.R[pick]))) pick = i;
-    // (2e6 points: 1000 | 2000-mid | 1000 and 2000 | 1000-mid | 2000 measured the same, 74-75 us per search)
-    if (pick < 0) return TSDR_OK;
-    if (pick != p - 1) {
-      const unsigned r = F.R[pick];
-      const std::vector<unsigned char> rd = F.rad[pick];
-      for (int i = pick; i < p - 1; ++i) { F.R[i] = F.R[i + 1]; F.rad[i] = F.rad[i + 1]; }
-      F.R[p - 1] = r;
-      F.rad[p - 1] = rd;
-    }
-  }
-  const MidEntry *me = mid_lookup(F.R[p - 1]);
-  // inverse split: the forward's last factor first; of the others the one with the most twos last, the rest largest first
-  MixPlan I;
-  I.p = p;
-  I.R[0] = F.R[p - 1];
-  I.rad[0] = F.rad[p - 1];
-  {
-    std::vector<int> rest;
-    for (int i = 0; i < p - 1; ++i) rest.push_back(i);
-    auto twos = [&](int i) { unsigned v = F.R[i], t = 0; while (v % 2 == 0 && t < 4) { v /= 2; ++t; } return t; };
-    int last = rest[0];
-    for (int i : rest)
-      if (twos(i) > twos(last) || (twos(i) == twos(last) && F.R[i] > F.R[last])) last = i;
-    std::vector<int> order;
-    for (int i : rest) if (i != last) order.push_back(i);
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return F.R[a] > F.R[b]; });
-    order.push_back(last);
-    for (int o = 0; o < (int)order.size(); ++o) { I.R[o + 1] = F.R[order[o]]; I.rad[o + 1] = F.rad[order[o]]; }
-  }
-  MidDesc m{};
-  m.R = F.R[p - 1];
-  m.Bc = (unsigned)(Mc / m.R);
-  m.ndir = m.Bc / 2 + 1;
-  m.logT = floor_log2((unsigned)me->tm);
-  if (m.logT < 1) return TSDR_OK;
-  m.nprev = p - 1;
-  for (int j = 0; j < p - 1; ++j) m.Rprev[j] = F.R[j];
-  {
-    const unsigned __int128 inv = ((unsigned __int128)1 << 64) / m.R;
-    m.r_hi = (unsigned)(inv >> 32);
-    m.r_lo = (unsigned)inv;
-    const unsigned __int128 inv2 = ((unsigned __int128)1 << 64) / ((unsigned __int128)m.R * I.R[1]);
-    m.ntw_hi = (unsigned)(inv2 >> 32);
-    m.ntw_lo = (unsigned)inv2;
-  }
-  m.Bnext = m.Bc / I.R[1];
-  const unsigned Th = 1u << (m.logT - 1);
-  const unsigned sets = (Th - 1) / m.Bnext + 2;
-  m.tw_sets = sets <= 4 ? (int)sets : 0;
-  m.w8 = 4.0 / (double)Mc;
-  float2 *w = nullptr;
-  int rc = fft_mixed_ex(ctx, x, nullptr, Mc, 1, -1, 1.0f, src_mode, src_n, 0, nullptr, nullptr, &F, 0, &w, src_scale);
-  if (rc) return rc;
-  if (me->RA == 0) {  // three-step kernel
-    const size_t lds = me->lds3;
-    rc = lds_opt_in(ctx, (const void *)me->fn, lds);
-    if (rc) return rc;
-    const unsigned grid = (unsigned)ceil_div((size_t)m.ndir, (size_t)Th);
-    TSDR_LAUNCH(ctx, "fftm_mid", me->fn, dim3(grid), dim3(me->nt), lds, (const float2 *)w, Zbuf, m);
-  } else {
-    const size_t T = (size_t)1 << m.logT, RB = m.R / me->RA;
-    const size_t SA = (RB << m.logT) + (T < 32 ? T : 0);
-    const size_t lds = (std::max((size_t)m.R * (T + 1), (size_t)me->RA * SA) + (size_t)(1 + 2 * m.tw_sets) * m.R) * sizeof(float2) + 2 * T * 4;
-    const unsigned grid = (unsigned)ceil_div((size_t)m.ndir, (size_t)Th);
-    TSDR_LAUNCH(ctx, "fftm_mid", me->fn, dim3(grid), dim3(me->nt), lds, (const float2 *)w, Zbuf, m);
-  }
-  rc = fft_mixed_ex(ctx, Zbuf, zbuf, Mc, 1, +1, scale, SRC_C2C, 0, keep, epi, nullptr, &I, 1, nullptr);
-  if (rc) return rc;
-  *done = true;
-  return TSDR_OK;
+int fft_mixed_passes(tsdr_ctx *ctx, size_t N, size_t batch) {   // the split plan_fft makes for this call
+  MixPlan pl;
+  return fft_mixed_plan(N, &pl, fft_big_ok(fft_opts(ctx), N * batch)) ? pl.p : 0;
 }
 
 }  // namespace tsdr
@@ -1847,16 +1297,5 @@ int fft_mixed_autocorr(tsdr_ctx *ctx, const float2 *x, int src_mode, size_t src_
 extern "C" int tsdr_fft_plan(size_t n, unsigned *factors, int cap) {
   using namespace tsdr;
   if (n < 2) return 0;
-  if (is_pow2(n)) {  // fft.hip's split: the bits dealt evenly over ceil(log2 n / 8) passes
-    int l = 0;
-    while (((size_t)1 << l) < n) ++l;
-    const int p = l <= 8 ? 1 : (l + 7) / 8;
-    for (int i = 0; i < p && i < cap && factors; ++i) factors[i] = 1u << (l / p + (i < l % p ? 1 : 0));
-    return p;
-  }
-  MixPlan pl;
-  if (!fft_mixed_plan(n, &pl, n <= (size_t(1) << 22))) return 0;  // (as fft_big_ok with the default options, batch 1)
-  for (int i = 0; i < pl.p && i < cap && factors; ++i) factors[i] = pl.R[i];
-  return pl.p;
+  return fft_split(n, fft_big_ok(FftOpts{}, n), factors, cap);   // (the default options, one transform)
 }
-

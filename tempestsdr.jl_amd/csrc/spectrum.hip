@@ -469,8 +469,9 @@ static int spectrum_d(tsdr_ctx *ctx, const SigSrc &sig, size_t N, int lin, float
     epi.cnt = N;
     epi.k0 = N / 2;
     epi.log_scale = !lin;
-    return is_pow2(N) ? fft_pow2(ctx, sig.c32(), X, ilog2(N), 1, -1, 1.0f, src_of(sig.kind), 0, 0, &epi, nullptr, sig.scale)
-                      : fft_mixed(ctx, sig.c32(), X, N, 1, -1, 1.0f, src_of(sig.kind), 0, 0, &epi, nullptr, sig.scale);
+    FftReq q;
+    q.out = X; q.n = N; q.epi = &epi;
+    return fft_run(ctx, q.load(sig, src_of(sig.kind)));
   }
   // (one-launch and Bluestein lengths: integer samples are expanded into the workspace first, fft_any)
   int rc = fft_any(ctx, sig, X, N, 1, -1);
@@ -830,19 +831,19 @@ int tsdr_resampler_run_d(tsdr_resampler *r, const float *in, size_t n_in, float 
   if (passes >= 2) {
     // two transforms and nothing else: the zero-stuffing is the forward transform's loader, the filter the inverse
     // transform's, 2*upCoeff*real(.) the epilogue of its last pass
-    const bool p2 = is_pow2(N);
-    const float2 *x = reinterpret_cast<const float2 *>(in);
-    int rc = p2 ? fft_pow2(ctx, x, tmp, ilog2(N), 1, -1, 1.0f, SRC_STUFF, r->up, 0)
-                : fft_mixed(ctx, x, tmp, N, 1, -1, 1.0f, SRC_STUFF, r->up, 0);
+    FftReq f;
+    f.in = reinterpret_cast<const float2 *>(in); f.out = tmp; f.n = N; f.src_mode = SRC_STUFF; f.src_n = r->up;
+    int rc = fft_run(ctx, f);
     if (rc) return rc;
     FftEpilogue epi;
     epi.kind = EPI_REAL;
     epi.out = out;
     epi.cnt = N;
     epi.gain = (float)(2 * r->up);
-    const float inv = (float)(1.0 / (double)N);
-    return p2 ? fft_pow2(ctx, tmp, r->work, ilog2(N), 1, +1, inv, SRC_MULH, 0, 0, &epi, reinterpret_cast<const float2 *>(r->H))
-              : fft_mixed(ctx, tmp, r->work, N, 1, +1, inv, SRC_MULH, 0, 0, &epi, reinterpret_cast<const float2 *>(r->H));
+    FftReq b;
+    b.in = tmp; b.out = r->work; b.n = N; b.dir = +1; b.scale = (float)(1.0 / (double)N);
+    b.src_mode = SRC_MULH; b.src_aux = reinterpret_cast<const float2 *>(r->H); b.epi = &epi;
+    return fft_run(ctx, b);
   }
   TSDR_LAUNCH(ctx, "resampler_stuff", k_stuff, dim3(stream_grid(ctx, N)), dim3(256), 0, in, N, (unsigned)r->up, r->work);
   int rc = fft_any(ctx, SigSrc{r->work, SIG_CF32, 1.0f}, tmp, N, 1, -1);

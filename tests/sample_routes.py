@@ -85,6 +85,26 @@ def _fft(n, batch, direction):
     return prepare
 
 
+def _resampler(buffer_size, up):
+    """resampler!(out, in) with `in` 4 bytes off 8-byte alignment: the half-size route needs both pointers on 8 bytes, so this is
+    the full-size one -- two transforms of sizeFFT = buffer_size * up points, the zero-stuffing and the filter in their loaders"""
+    def prepare(ctx):
+        base, p, _ = _upload(ctx, "real", buffer_size, 1)
+        n = buffer_size * up
+        out = ctx.dev_alloc(4 * n)
+        h = C.c_void_p(0)
+        rc = ctx.lib.tsdr_resampler_init(ctx.h, buffer_size, up, C.byref(h))
+        assert rc == 0, (rc, ctx.lib.tsdr_last_error(ctx.h).decode())
+        call, fetch, free_ = _prepared(ctx, [base, out], [(out, n, np.uint32)],
+                                       lambda: ctx.lib.tsdr_resampler_run_d(h, C.c_void_p(p), buffer_size, C.c_void_p(out)))
+
+        def free():
+            free_()
+            ctx.lib.tsdr_resampler_free(h)
+        return call, fetch, free
+    return prepare
+
+
 def _demod(kind, src, n, lead):
     def prepare(ctx):
         base, p, scale = _upload(ctx, src, n, lead)
@@ -147,6 +167,8 @@ def cases():
             out.append((f"autocorr_search-{src}-{n}", _search("autocorr_search", src, n, True)))
     for src in INTS:
         out.append((f"autocorr_search_iq-{src}-4096", _search("autocorr_search_iq", src, 4096, True)))
+    for buffer_size, up in ((256, 2), (100, 3)):   # sizeFFT 512 = 32 x 16 and 300 = 25 x 12: two passes on either engine
+        out.append((f"resampler-{buffer_size}x{up}-in4", _resampler(buffer_size, up)))
     return out
 
 
