@@ -369,6 +369,7 @@ int tsdr_vsync_d(tsdr_sync *s, const float *img, int *s_yx_dev);
 /* copy of the beta_x (which=0) / beta_y (which=1) field, (w_max-w_min+1) x n col-major */
 int tsdr_sync_beta(tsdr_sync *s, int which, float *beta_host);
 /* fill_beta!(beta,c_v,Sync(w_min,w_max,n))           FrameSynchronisation.jl:94-112 */
+/* n <= 16384 (c_v is held in LDS): a longer vector returns TSDR_EINVAL before anything is launched; the _f64 form has no such limit */
 int tsdr_fill_beta(tsdr_ctx *ctx, const float *cv, int n, int w_min, int w_max, float *beta);
 /* circshift(image,(-s_y,-s_x))                                        GUI.jl:172 */
 int tsdr_circshift_neg(tsdr_ctx *ctx, const float *img, int h, int w, int s_y, int s_x, float *out);

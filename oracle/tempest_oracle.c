@@ -710,6 +710,7 @@ int orc_project(const orc_sync *s, const float *img, float *cv_f, float *ch_f) {
 
 /* circshift(image,(-s_y,-s_x)) -- GUI.jl:172: out[i,j] = in[i+s_y, j+s_x] (mod) */
 void orc_circshift_neg(const float *in, int h, int w, int s_y, int s_x, float *out) {
+  s_y %= h; s_x %= w; /* circshift takes any Int: reduced first, so that i + s_y stays inside an int */
   for (int j = 0; j < w; j++) {
     int sj = ((j + s_x) % w + w) % w;
     for (int i = 0; i < h; i++) {

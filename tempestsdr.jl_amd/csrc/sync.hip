@@ -573,7 +573,10 @@ __global__ __launch_bounds__(256) void k_circshift(const float *__restrict__ in,
   out[idx] = in[(size_t)sj * h + si];
 }
 
-// standalone fill_beta!: beta (W x n) from an already filtered projection (one lane per centre)
+// standalone fill_beta!: beta (W x n) from an already filtered projection (one lane per centre).  c_v is held in dynamic LDS, of
+// which a kernel gets 64 KiB without opting in: kFillBetaMaxN values (tsdr_fill_beta refuses more)
+constexpr int kFillBetaMaxN = 16384;
+static_assert((size_t)kFillBetaMaxN * sizeof(float) == 64 * 1024, "k_fill_beta: c_v must fit the 64 KiB of LDS exactly at the limit");
 __global__ __launch_bounds__(64) void k_fill_beta(const float *__restrict__ cvin, int n, int w_min, int w_max,
                                                   float *__restrict__ beta) {
   extern __shared__ float cv[];
@@ -1089,7 +1092,12 @@ int tsdr_sync_beta(tsdr_sync *s, int which, float *beta_host) {
 }
 
 int tsdr_fill_beta(tsdr_ctx *ctx, const float *cv, int n, int w_min, int w_max, float *beta) {
-  if (!ctx || !cv || !beta || n < 2 || w_min < 1 || w_max < w_min || w_max >= n) return TSDR_EINVAL;
+  if (!ctx) return TSDR_EINVAL;
+  if (!cv || !beta || n < 2 || w_min < 1 || w_max < w_min || w_max >= n)
+    return set_err(ctx, TSDR_EINVAL, "fill_beta needs c_v, beta and 2 <= n, 1 <= w_min <= w_max < n (got n = %d, w_min = %d, w_max = %d)", n, w_min, w_max);
+  // k_fill_beta keeps c_v in LDS, n * 4 of the 64 KiB a kernel gets without opting in: a longer vector is refused here,
+  // loudly, not at launch
+  if (n > kFillBetaMaxN) return set_err(ctx, TSDR_EINVAL, "fill_beta supports vectors of up to %d values (got %d)", kFillBetaMaxN, n);
   const size_t W = (size_t)(w_max - w_min + 1);
   return host_map(ctx, cv, (size_t)n * 4, beta, W * n * 4, [&](void *i, void *o) {
     TSDR_LAUNCH(ctx, "fill_beta", k_fill_beta, dim3((unsigned)ceil_div((size_t)n, 64)), dim3(64), (size_t)n * 4,

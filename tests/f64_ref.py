@@ -79,6 +79,8 @@ def taps():
 
 
 def fma(a, b, c):
+    if not (math.isfinite(a) and math.isfinite(b) and math.isfinite(c)):
+        return a * b + c   # NaN / Inf operands: no rounding is involved, the IEEE result of the unfused form is the fused one
     return float(Fraction(a) * Fraction(b) + Fraction(c))
 
 
