@@ -113,6 +113,22 @@ int tsdr_get_precision(tsdr_ctx *ctx);
  *                 BEFORE this call refills it (FrameSynchronisation.jl:66), so it is the previous image's; 1: s_y of the
  *                 current image (what the code presumably meant; NOT what TempestSDR.jl does).  Takes effect from the
  *                 next call; the pending value is kept up to date in either mode.
+ *   "vsync_blank_dark" 0 (default): the blanking interval is the BRIGHTEST band of the picture -- findmax over beta on both axes,
+ *                 the reference's binding `arg_area_blank = findmax` (FrameSynchronisation.jl:51-53).  1: it is the DARKEST band --
+ *                 findmin, the other value that one-word binding takes: the first minimum in column-major order, only its
+ *                 column used; among columns reaching the minimum the smallest wins; NaN is minimal and the first NaN's column
+ *                 wins.  Applies to tsdr_vsync / _d / _f64 / _f64_d and to the frame loop on every route (tsdr_frames*, _scan_d,
+ *                 _submit_*, tsdr_group_frames).  beta itself, tsdr_sync_beta* and tsdr_fill_beta* do not change, nor does the
+ *                 stale-s_y ordering: "vsync_current_sy" combines with the polarity independently, and a fresh or reset SyncXY
+ *                 still gives s_y = 1 (findmin of the all-zero beta_y is index (1,1) too).  Setting it first waits for the buffers
+ *                 already submitted (tsdr_frames_submit_*), which keep the polarity they were submitted with.  PENDING s_y: the
+ *                 state keeps the pending s_y as an index, not as beta, so the first s_y after the polarity changes is still the
+ *                 old polarity's; tsdr_sync_reset restores reference-equal behaviour.  The keys of tsdr_frames_scan_d stay opaque
+ *                 64-bit words whose low word carries the column; tsdr_frames_combine_d needs no polarity.  SYNC GUARD under 1: a
+ *                 frame is re-evaluated unless (second - best) > thr * second on both axes, best = the smallest column minimum,
+ *                 second = the smallest column minimum of any OTHER column; NaN, Inf and all-equal frames are flagged as under 0;
+ *                 tsdr_sync_guard_margins reports (second - best) / second for such calls; threshold, counters and the adaptive
+ *                 whole-buffer route are shared with the bright polarity.  No environment variable presets this option.
  *   "fast_walk_only" 1: the TSDR_FAST frame loop without a raster runs the raster walk with out == NULL (rounds 1-2) instead
  *                 of the tap-based kernel with its own partial sums.  Default 0.  Results within the FAST tolerance either way.
  *   "sync_guard_auto" 1 (default): the adaptive whole-buffer TSDR_EXACT route described above; 0: flagged frames are always
@@ -585,9 +601,10 @@ int tsdr_group_set_precision(tsdr_group *g, int mode);                  /* tsdr_
  *                    reached the array, so one thread driving all members serialises their transfers.  0: the caller's thread
  *                    drives every member in turn (rounds 1-5; the A/B).  With 1, members that SHARE a device (a device listed
  *                    more than once) are driven by the caller's thread: they share one link.  2: member threads always.
- *   "pin_host"       1: the caller's arrays (>= 1 MiB) are page-locked for all devices (hipHostRegister, portable) for the
- *                    duration of the call -- DMA straight from / into the array instead of through bounce buffers.  Default 0:
- *                    registering and releasing a capture buffer costs more than the staged copy it replaces. */
+ *   "pin_host"       accepted, without effect: the caller's arrays are no longer page-locked.  (1 used to hipHostRegister arrays
+ *                    of >= 1 MiB for the duration of the call.  It measured slower than the staged copy, and releasing a range
+ *                    the runtime itself had pinned for an earlier copy of the same array left that pin without its mapping:
+ *                    the next large copy of the array faulted.) */
 int tsdr_group_set_option(tsdr_group *g, const char *name, int value);
 /* extract_configuration's inner step, GUI.jl:73-81 -- arguments as tsdr_autocorr_search_d, x and out on the HOST (out may be
  * NULL).  The circular autocorrelation (Autocorrelations.jl:27-29) is a sum over m: member g receives its range of m plus a

@@ -106,7 +106,7 @@ class Context:
         return "exact" if self.lib.tsdr_get_precision(self.h) == _lib.EXACT else "fast"
 
     def set_option(self, name, value):
-        """switches ("ac_mixed", "fft_no_mix2", "sync_guard_ppb", "sync_guard_auto", ...) -- tsdr_set_option"""
+        """switches ("ac_mixed", "fft_no_mix2", "sync_guard_ppb", "sync_guard_auto", "vsync_blank_dark", ...) -- tsdr_set_option"""
         self.call("tsdr_set_option", name.encode(), int(value))
 
     def sync_guard_stats(self, reset=False):

@@ -80,6 +80,7 @@ struct tsdr_ctx {
   int opt_ac_mixed = 1;     // autocorrelation of n = 2*(2^a3^b5^c) samples: native mixed-radix route (0: zero-padded power of two)
   int opt_fft_no_mix2 = 0;  // 1: every mixed-radix factor through the generic LDS-stage kernel
   int opt_fft_big = 1;      // mixed-radix planner may use factors of 500 / 1000 / 2000 (three-register-step kernels)
+  int opt_vsync_blank_dark = 0;  // 1: the blanking interval is the DARKEST band: findmin instead of findmax on both axes (FrameSynchronisation.jl:51-53)
   int opt_vsync_current_sy = 0;  // 1: vsync / the frame loop return s_y of the CURRENT image (the corrected ordering, off by default)
   int opt_fast_walk_only = 0;    // 1: the raster-free FAST frame path runs the raster walk with out == null (round 2's route; A/B)
   int opt_down_spp_max_pct = 200; // raster-free FAST route: k_down_fused up to this many samples per raster pixel (percent), the raster walk above
@@ -112,6 +113,7 @@ struct tsdr_ctx {
   unsigned guard_win_c = 0, guard_win_f = 0; // frames checked / flagged since the last decision
   bool guard_exact_now = false;
   unsigned long long guard_auto_buffers = 0, guard_auto_switches = 0;
+  int guard_last_dark = 0;                  // polarity ("vsync_blank_dark") of those records
   size_t guard_last_off = (size_t)-1;       // byte offset inside WS_GUARD of the most recent guarded call's top-2 records (tsdr_sync_guard_margins)
   int guard_last_frames = 0, guard_last_nbx = 0, guard_last_nby = 0;
   struct Buf { void *p = nullptr; size_t cap = 0; } ws[tsdr::WS_COUNT];

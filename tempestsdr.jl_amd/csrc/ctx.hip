@@ -288,6 +288,11 @@ int tsdr_set_option(tsdr_ctx *ctx, const char *name, int value) {
     if (rc) return rc;
     ctx->opt_vsync_current_sy = value != 0;
   }
+  else if (!strcmp(name, "vsync_blank_dark")) {
+    int rc = tsdr::pipe_drain(ctx);   // (submitted buffers keep the old polarity; later calls are ordered behind them)
+    if (rc) return rc;
+    ctx->opt_vsync_blank_dark = value != 0;
+  }
   else if (!strcmp(name, "fft_big")) ctx->opt_fft_big = value != 0;
   else if (!strcmp(name, "down_xcd")) ctx->opt_down_xcd = value != 0;
   else if (!strcmp(name, "down_spp_max_pct")) ctx->opt_down_spp_max_pct = value < 0 ? 0 : value;
@@ -402,6 +407,13 @@ int tsdr_sync_guard_margins(tsdr_ctx *ctx, int max_frames, float *margins, int *
       if (holders >= 2) gs = gb;
       else for (int i = 0; i < nb; ++i) { const unsigned c = e[i].x == gb ? e[i].y : e[i].x; gs = c > gs ? c : gs; }
       float b, s2;
+      if (ctx->guard_last_dark) {  // complemented words (findmin): (second - best) / second; a NaN minimum is the all-ones word
+        const unsigned ub = ~gb, us = ~gs;
+        memcpy(&b, &ub, 4); memcpy(&s2, &us, 4);
+        const float m = (s2 - b) / s2;
+        margins[2 * f + axis] = (gb != 0xFFFFFFFFu && m >= 0.f && m <= 1.f) ? m : 0.f;
+        continue;
+      }
       memcpy(&b, &gb, 4); memcpy(&s2, &gs, 4);
       margins[2 * f + axis] = b != 0.f ? (b - s2) / b : 0.f;
     }

@@ -183,6 +183,7 @@ static int guard_plan(FrameJob &j) {
   // (an offset, not the pointer: the workspace may be reallocated by a later, larger call)
   ctx->guard_last_off = (size_t)((const char *)j.gp.top2 - (const char *)ctx->ws[WS_GUARD].p);
   ctx->guard_last_frames = F; ctx->guard_last_nbx = nbx; ctx->guard_last_nby = nby;
+  ctx->guard_last_dark = ctx->opt_vsync_blank_dark;
   return TSDR_OK;
 }
 

@@ -63,11 +63,11 @@ struct tsdr_group {
   int opt_threads = 1;             // "member_threads" 1: member threads when the members sit on distinct devices (members sharing a
                                    // device share its link: their staged copies only contend -- sharded search 4.1 against 2.3 ms
                                    // with four members on one device); 2: always (tests); 0: never (rounds 1-5; the A/B)
-  // "pin_host" 1: the caller's arrays are page-locked (hipHostRegister, portable) for the duration of the call -- DMA straight
-  // from / into the array at the link's rate instead of through bounce buffers.  Off by default: registering and releasing
-  // 80 MB costs more than the staged copy it replaces (measured, NOTEBOOK round 6).  (Registrations that OUTLIVE the call were
-  // built and withdrawn: a later copy -- the caller's own, or the single-context entry points' -- whose range only partly
-  // overlaps a registered one fails with hipErrorInvalidValue.)
+  // "pin_host": accepted and remembered, but the caller's arrays are NO LONGER page-locked (see pin_host below).  It used to
+  // hipHostRegister them for the duration of the call -- DMA straight from / into the array instead of through bounce buffers;
+  // off by default even then: registering and releasing 80 MB cost more than the staged copy it replaced (NOTEBOOK round 6).
+  // (Registrations that OUTLIVE the call had been built and withdrawn before: a later copy whose range only partly overlaps a
+  // registered one fails with hipErrorInvalidValue.)
   int opt_pin_host = 0;
   struct Pin { const char *p; size_t bytes; };
   std::vector<Pin> pins;
@@ -239,11 +239,16 @@ void stop_members(tsdr_group *g) {
   g->mem.clear();
 }
 
-// "pin_host": [p, p + bytes) page-locked for every device of the node until the call returns (CallScope)
+// "pin_host": WITHDRAWN -- the caller's arrays are copied through the runtime's own staging whatever the option says.
+// It registered [p, p + bytes) (hipHostRegister, portable) and released it when the call returned.  A caller's array is not
+// the library's to register: the HIP runtime pins pageable arrays of 1 MiB and more itself when it copies them and keeps such
+// pins, keyed by the host address, for the next copy of the same array.  Registering a range that starts at the same address
+// and releasing it again takes the pages' lock and device mapping from under the pin the runtime still holds; the runtime's
+// next copy of that array -- any entry point's, any context's -- then runs its DMA through a mapping that is gone: "an illegal
+// memory access" from a hipMemcpyAsync with no kernel in flight.  That is where the suite faulted three times, on three
+// different trees, always at the first >= 1 MiB upload of the array a sharded search had registered and released (NOTEBOOK).
 void pin_host(tsdr_group *g, const void *ptr, size_t bytes) {
-  if (!g->opt_pin_host || !ptr || bytes < (1u << 20)) return;
-  if (hipHostRegister((void *)ptr, bytes, hipHostRegisterPortable) == hipSuccess) g->pins.push_back({(const char *)ptr, bytes});
-  (void)hipGetLastError();   // (an array that cannot be registered is copied through the bounce buffers as before)
+  (void)g; (void)ptr; (void)bytes;
 }
 void unpin_all(tsdr_group *g) {
   for (auto &e : g->pins) (void)hipHostUnregister((void *)e.p);
@@ -428,8 +433,8 @@ int tsdr_group_set_precision(tsdr_group *g, int mode) {
 int tsdr_group_set_option(tsdr_group *g, const char *name, int value) {
   if (!g || !name) return TSDR_EINVAL;
   // the group's own switches: "member_threads" (1: one host thread per member drives its stage, default; 0: the caller's
-  // thread drives them all in turn) and "pin_host" (1: the caller's arrays are page-locked at first use and stay so until the
-  // group is destroyed; the caller keeps them alive that long)
+  // thread drives them all in turn) and "pin_host" (accepted for compatibility; the caller's arrays are no longer
+  // page-locked: pin_host above)
   if (!strcmp(name, "member_threads")) { g->opt_threads = value < 0 ? 0 : value > 2 ? 2 : value; return TSDR_OK; }
   if (!strcmp(name, "pin_host")) {
     g->opt_pin_host = value != 0;

@@ -11,13 +11,23 @@
 // by ONE launch (k_guard, sync.hip): a small persistent grid whose workgroups all leave at once when no frame is flagged,
 // and otherwise work through a dependency-ordered queue of (frame, tile / row block / centre block) items.  Such a frame then carries EXACT pixels and the
 // oracle's indices; all other frames keep FAST pixels and have margins no rounding difference can bridge.
+//
+// Option "vsync_blank_dark" (findmin, FrameSynchronisation.jl:51-53): the records hold complemented words (sync.hip:
+// beta_word), so the same merge finds `best` = the smallest column minimum and `second` = the smallest column minimum of any
+// OTHER column; a frame is re-evaluated unless (second - best) > thr * second on both axes.  NaN (the all-ones word), Inf
+// and all-equal frames are flagged as under findmax.  Thresholds, counters and the adaptive route are shared.
+// Measured (tools/measure_beta_error.py, 12 frames per card, 1056x628 @ 2 MS/s and C2, raster-writing and raster-free routes, one
+// MI355X): largest relative FAST-vs-EXACT difference at the column MAXIMA 1.14e-6 ("box" / "plateau" cards, findmax), at the
+// column MINIMA 9.0e-7 ("box_dark" / "plateau_dark", findmin) -- both a factor 17 .. 22 below the 2e-5 default, which
+// therefore serves both polarities.
 #pragma once
 #include <hip/hip_runtime.h>
 
 namespace tsdr {
 
 struct GuardArgs {
-  const uint2 *top2 = nullptr;  // [frames][nbx + nby] {best, second-best-other-column} words from k_beta; null: no guard
+  const uint2 *top2 = nullptr;  // [frames][nbx + nby] {best, second-best-other-column} words from k_beta (of the launch's
+                                // polarity: larger word = better column); null: no guard
   int nbx = 0, nby = 0;         // k_beta workgroups per frame along x / y
   float thr = 0.f;              // relative margin below which a frame is re-evaluated
   int *flags = nullptr;         // [frames] out: 1 = re-evaluated
@@ -34,8 +44,9 @@ struct GuardArgs {
 constexpr int kGuardChunk = 256;   // frames per guard_image launch
 
 #ifdef __HIPCC__
-// the scan of one axis' records: largest column maximum, largest one of any other column -> flagged?
-template <int NB>
+// the scan of one axis' records: best column extremum, best one of any other column -> flagged?
+// DARK: the words are complemented beta bits (findmin); the merge is the same, the margin is taken relative to `second`
+template <int NB, bool DARK = false>
 __device__ inline bool guard_axis(const uint2 *e, int nb, float thr) {
   unsigned gb = 0u, gs = 0u;
   if (NB > 0) {  // compile-time count: every record is requested before the first compare
@@ -53,20 +64,26 @@ __device__ inline bool guard_axis(const uint2 *e, int nb, float thr) {
       else gs = max(gs, v.x);                              // (v.x == gb: another column holds the same maximum, an exact tie)
     }
   }
+  if (DARK) {
+    const float b = __uint_as_float(~gb), s2 = __uint_as_float(~gs);
+    // (gb all ones: a NaN holds the minimum -- its complement would read as 0.0; gs == 0, no other column, reads as NaN)
+    return gb == 0xFFFFFFFFu || !((s2 - b) > thr * s2);  // also catches Inf / all-equal images
+  }
   const float b = __uint_as_float(gb), s2 = __uint_as_float(gs);
   return !((b - s2) > thr * b);  // also catches NaN / Inf / all-zero images
 }
 
 // true when frame f needs the exact re-evaluation (one lane does a whole frame: two short scans of the records)
+template <bool DARK = false>
 __device__ inline bool guard_eval(const GuardArgs &g, int f, bool *y_too = nullptr) {
   const uint2 *base = g.top2 + (size_t)f * (size_t)(g.nbx + g.nby);
   bool bx, by;  // (both axes are always evaluated: no divergent second scan)
   if (g.nbx == 13 && g.nby == 10) {  // the 600 x 800 rendering image (the only SyncXY the frame loop accepts)
-    bx = guard_axis<13>(base, 13, g.thr);
-    by = guard_axis<10>(base + 13, 10, g.thr);
+    bx = guard_axis<13, DARK>(base, 13, g.thr);
+    by = guard_axis<10, DARK>(base + 13, 10, g.thr);
   } else {
-    bx = guard_axis<0>(base, g.nbx, g.thr);
-    by = guard_axis<0>(base + g.nbx, g.nby, g.thr);
+    bx = guard_axis<0, DARK>(base, g.nbx, g.thr);
+    by = guard_axis<0, DARK>(base + g.nbx, g.nby, g.thr);
   }
   if (y_too) *y_too = by;
   return bx || by;

@@ -29,6 +29,9 @@
 // wavefront on a packed key (beta bits << 32 | ~c): beta >= +0 so its bit pattern is order-preserving, NaN
 // patterns sort above +Inf (Julia's findmax treats NaN as maximal), and ~c makes the smallest column win
 // ties = first maximum in column-major order (only the column of the maximum is ever used, :66,:76).
+// Option "vsync_blank_dark" (the reference's arg_area_blank = findmin, :51-53) is the DARK instantiation of the same
+// kernels: the value word is complemented (NaN -> all ones, Julia's findmin treats NaN as minimal), so the same cleared
+// keys, the same max folds and the same atomicMax return the first MINIMUM in column-major order.
 #include <algorithm>
 #include <cstdlib>
 #include <mutex>
@@ -189,9 +192,16 @@ static inline dim3 proj_block() { return dim3(64); }
 static inline size_t proj_lds_bytes() { return 0; }
 #endif
 
+// beta as a word whose unsigned order is the polarity's preference (larger word = better): beta >= +0, so its bits are
+// order-preserving; findmax takes them as they are (NaN above +Inf), findmin their complement (NaN = all ones, on top)
+template <bool DARK>
+__device__ inline unsigned beta_word(float v) {
+  if (DARK) return (v != v) ? 0xFFFFFFFFu : ~__float_as_uint(v);
+  return (v != v) ? 0x7FC00000u : __float_as_uint(v);
+}
+template <bool DARK = false>
 __device__ inline unsigned long long pack_key(float v, int c) {
-  unsigned bits = (v != v) ? 0x7FC00000u : __float_as_uint(v);
-  return ((unsigned long long)bits << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)c);
+  return ((unsigned long long)beta_word<DARK>(v) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)c);
 }
 
 // x / d for a small positive integer d, given rd = RN(1/d): Markstein's correction returns RN(x/d) exactly
@@ -290,14 +300,15 @@ struct BetaArgs {
   unsigned long long *keys;
   int write_frame;
   float *bx, *by;
-  uint2 *top2;       // sync guard (or null): per (frame, workgroup of the frame) {largest column maximum, second largest among
-                     // OTHER columns} of the workgroup's 64 centres, as order-preserving words
+  uint2 *top2;       // sync guard (or null): per (frame, workgroup of the frame) {best column extremum, best among OTHER
+                     // columns} of the workgroup's 64 centres, as beta_word words of the launch's polarity (0: no column)
 };
 
 __device__ inline int gridDim_x_of_frame(const SyncGeom &g) { return ((g.x_t + 63) >> 6) + ((g.y_t + 63) >> 6); }
 
 // body of one k_beta workgroup: blk = block index within the frame (x-axis blocks first), f = frame
-template <int NWV>
+// DARK: the polarity (beta_word); the per-column extremum over the widths is then the column MINIMUM
+template <int NWV, bool DARK = false>
 __device__ __forceinline__ void beta_wg(const BetaArgs &A, int blk, int f, float *sh) {
   const float *__restrict__ proj = A.proj;
   const size_t proj_stride = A.proj_stride;
@@ -389,7 +400,7 @@ __device__ __forceinline__ void beta_wg(const BetaArgs &A, int blk, int f, float
   for (; i < ia; ++i) { s = __fmaf_rn(2.0f, plo[-i], s); s = __fmaf_rn(2.0f, phi[i], s); }
   const float s_share = s;  // running sum at the start of the share (kept for the IEEE re-run)
   float *bout = (f == write_frame && c0 < n) ? (axis == 0 ? bx : by) + (size_t)c0 * W : nullptr;
-  unsigned kb = 0u;          // largest beta of the share as an order-preserving word (beta >= +0; NaN above +Inf)
+  unsigned kb = 0u;          // best beta of the share as an order-preserving word (beta_word: 0 is below every value)
   float amin = 1.0f, amax = 1.0f;
   for (int i0 = ia; i0 < ib; i0 += 64) {
     const int i1 = min(i0 + 64, ib);
@@ -420,8 +431,7 @@ __device__ __forceinline__ void beta_wg(const BetaArgs &A, int blk, int f, float
           amin = fminf(amin, fminf(fabsf(x1), fabsf(s)));
           amax = fmaxf(amax, fmaxf(fabsf(x1), fabsf(s)));
           if (bout) bout[i + u] = v;
-          const unsigned bits = (v != v) ? 0x7FC00000u : __float_as_uint(v);
-          kb = max(kb, bits);
+          kb = max(kb, beta_word<DARK>(v));
         }
       }
     }
@@ -438,12 +448,11 @@ __device__ __forceinline__ void beta_wg(const BetaArgs &A, int blk, int f, float
       float v = __fadd_rn(__fdiv_rn(__fsub_rn(S, s), (float)(2 * (n - w))), __fdiv_rn(s, (float)(2 * w)));
       v = __fmul_rn(v, v);
       if (bout) bout[i] = v;
-      const unsigned bits = (v != v) ? 0x7FC00000u : __float_as_uint(v);
-      kb = max(kb, bits);
+      kb = max(kb, beta_word<DARK>(v));
     }
   }
-  // per-centre maximum over the wavefronts' width shares, then the workgroup's first maximum (smallest column on ties)
-  // and -- for the sync guard -- the largest value any OTHER column of the workgroup reaches
+  // per-centre best word over the wavefronts' width shares, then the workgroup's first best (smallest column on ties)
+  // and -- for the sync guard -- the best word any OTHER column of the workgroup reaches
   colk[q][lane] = (c0 < n && ia < ib) ? kb : 0u;
   __syncthreads();
   if (q == 0) {
@@ -465,10 +474,10 @@ __device__ __forceinline__ void beta_wg(const BetaArgs &A, int blk, int f, float
   }
 }
 
-template <int NWV>
+template <int NWV, bool DARK = false>
 __global__ __launch_bounds__(64 * NWV) void k_beta(BetaArgs A) {
   extern __shared__ float sh[];
-  beta_wg<NWV>(A, (int)blockIdx.x, (int)blockIdx.y, sh);
+  beta_wg<NWV, DARK>(A, (int)blockIdx.x, (int)blockIdx.y, sh);
 }
 
 __device__ inline int key_col1(unsigned long long key) {  // 1-based column of the packed argmax
@@ -655,10 +664,13 @@ int sync_scan_d(tsdr_sync *s, const float *img, size_t img_stride, int frames, u
   size_t lds = 0;
   unsigned nbb = 0;
   beta_args(s, proj, pl, keys, frames, &B, &nbb, &lds, top2);
+  const bool dark = ctx->opt_vsync_blank_dark != 0;   // (setting the option drains the pipeline: one polarity per buffer)
   if (ctx->opt_beta_waves == 4) {
-    TSDR_LAUNCH(ctx, "sync_beta", k_beta<4>, dim3(nbb, (unsigned)frames), dim3(64 * 4), lds, B);
+    void (*const kfn)(BetaArgs) = dark ? k_beta<4, true> : k_beta<4, false>;
+    TSDR_LAUNCH(ctx, "sync_beta", kfn, dim3(nbb, (unsigned)frames), dim3(64 * 4), lds, B);
   } else {
-    TSDR_LAUNCH(ctx, "sync_beta", k_beta<kBetaWaves>, dim3(nbb, (unsigned)frames), dim3(64 * kBetaWaves), lds, B);
+    void (*const kfn)(BetaArgs) = dark ? k_beta<kBetaWaves, true> : k_beta<kBetaWaves, false>;
+    TSDR_LAUNCH(ctx, "sync_beta", kfn, dim3(nbb, (unsigned)frames), dim3(64 * kBetaWaves), lds, B);
   }
   return TSDR_OK;
 }
@@ -720,6 +732,8 @@ __device__ inline void guard_signal(unsigned *ctr) {
 
 #ifndef TSDR_ROWSUM_CHUNK8
 // (launch bound: one workgroup per CU is all the launch asks for, so the bodies may use up to 256 registers: no spills)
+// DARK: the polarity of the flagged-frame scan (guard_axis) and of the re-evaluated frames' beta scan
+template <bool DARK>
 __global__ __launch_bounds__(512, 2) void k_guard(GuardAllArgs a) {
   extern __shared__ double glds[];
   __shared__ int list[kGuardChunk];
@@ -744,7 +758,7 @@ __global__ __launch_bounds__(512, 2) void k_guard(GuardAllArgs a) {
       for (int base = 0; base < a.frames; base += 64) {
         const int f = base + tid;
         bool bad_y = false;
-        const bool bad = f < a.frames && guard_eval(gl, f, &bad_y);
+        const bool bad = f < a.frames && guard_eval<DARK>(gl, f, &bad_y);
         const unsigned long long m = __ballot(bad);
         if (bad) list[n + (int)__builtin_popcountll(m & ((1ull << tid) - 1ull))] = f | (bad_y ? 0x40000000 : 0);
         n += (int)__builtin_popcountll(m);
@@ -807,10 +821,10 @@ __global__ __launch_bounds__(512, 2) void k_guard(GuardAllArgs a) {
       const int nbx = (a.x_t + 63) >> 6;
       if (need_y) {
         guard_wait(doneB + j, (unsigned)a.nB);
-        beta_wg<8>(a.B, blk, list[j] & 0x3FFFFFFF, reinterpret_cast<float *>(glds));
+        beta_wg<8, DARK>(a.B, blk, list[j] & 0x3FFFFFFF, reinterpret_cast<float *>(glds));
       } else if (blk < nbx) {
         guard_wait(doneA + j, (unsigned)a.tilesA);
-        beta_wg<8>(a.B, blk, list[j] & 0x3FFFFFFF, reinterpret_cast<float *>(glds));
+        beta_wg<8, DARK>(a.B, blk, list[j] & 0x3FFFFFFF, reinterpret_cast<float *>(glds));
       }
     }
     __syncthreads();  // the item's LDS is free again
@@ -886,11 +900,12 @@ int sync_guard_d(tsdr_sync *s, const float *iq, IqFmt iqf, size_t S, int y_t, in
     // workgroup with 52 KiB of LDS, not their number, so it bought nothing there and cost C3, where a frame is flagged every
     // other buffer, 0.11 instead of 0.057 ms per step.)
     const unsigned grid = g.count_only ? 1u : (unsigned)ncu;
+    void (*const kfn)(GuardAllArgs) = ctx->opt_vsync_blank_dark ? k_guard<true> : k_guard<false>;
     if (lds > 64 * 1024) {   // above what a kernel gets without opting in
-      int rco = lds_opt_in(ctx, (const void *)k_guard, kGuardLdsMax);
+      int rco = lds_opt_in(ctx, (const void *)kfn, kGuardLdsMax);
       if (rco) return rco;
     }
-    TSDR_LAUNCH(ctx, "sync_guard", k_guard, dim3(grid), dim3(512), lds, a);
+    TSDR_LAUNCH(ctx, "sync_guard", kfn, dim3(grid), dim3(512), lds, a);
   }
   return TSDR_OK;
 #endif
@@ -1012,7 +1027,7 @@ int tsdr_sync_reset(tsdr_sync *s) {
     TSDR_HIP(ctx, hipMemsetAsync(s->beta_x, 0, nbx * 4, ctx->stream));
     TSDR_HIP(ctx, hipMemsetAsync(s->beta_y, 0, nby * 4, ctx->stream));
   }
-  const int one[4] = {1, 1, 0, 0};  // findmax of an all-zero beta_y is index (1,1)
+  const int one[4] = {1, 1, 0, 0};  // findmax -- and findmin -- of an all-zero beta_y is index (1,1)
   s->cur = 0;
   TSDR_HIP(ctx, hipMemcpyAsync(s->pending, one, 16, hipMemcpyHostToDevice, ctx->stream));
   { int _w = tsdr::wait_stream(ctx, ctx->stream, __func__); if (_w) return _w; }

@@ -7,7 +7,8 @@
 //   * Sigma = sum(c_v): lane m accumulates c_v[m], c_v[m+64], ... from 0.0, the 64 partials folded by the tree 32, 16, .., 1;
 //   * beta = ((S - s)/(2(n-w)) + s/(2w))^2 with correctly rounded divisions, the running blank sum s as the reference's
 //     sequential recurrence over w;
-//   * findmax: the first maximum in column-major order, NaN maximal; only its column is used (:66, :76).
+//   * findmax: the first maximum in column-major order, NaN maximal; only its column is used (:66, :76).  With the option
+//     "vsync_blank_dark" findmin instead (:51-53): the first minimum, NaN minimal -- the DARK instantiations below.
 // As in tsdr_vsync, s_y is read from beta_y BEFORE this call refills it (:66): the first call after create / reset returns 1.
 // The taps exp(-2k^2/25)/sum are computed on the host in f64 and kept in f64 (:124-129).
 // Not a streaming path: one projection launch per axis, one FIR launch, one beta launch for both axes (a thread per centre
@@ -19,13 +20,14 @@
 
 namespace tsdr {
 
-struct Best64 { double v; int c; int pad; };  // a workgroup's first maximum: value, 1-based column
+struct Best64 { double v; int c; int pad; };  // a workgroup's first maximum (DARK: minimum): value, 1-based column
 
-// a beats b: NaN above everything, then the larger value, ties (and two NaNs) to the smaller column
+// a beats b: NaN before everything, then the larger (DARK: smaller) value, ties (and two NaNs) to the smaller column
+template <bool DARK>
 __device__ inline bool beats64(double av, int ac, double bv, int bc) {
   const bool an = isnan(av), bn = isnan(bv);
   if (an != bn) return an;
-  if (!an && av != bv) return av > bv;
+  if (!an && av != bv) return DARK ? av < bv : av > bv;
   return ac < bc;
 }
 
@@ -95,6 +97,7 @@ struct Beta64Args { Beta64Axis ax[2]; };
 __device__ inline int mod_idx64(int k1, int n) { int m = (k1 - 1) % n; if (m < 0) m += n; return m; }
 
 // fill_beta! for one axis per blockIdx.y: a lane per centre c; every wavefront forms Sigma in sum64 order itself
+template <bool DARK>
 __global__ __launch_bounds__(256) void k_beta64(Beta64Args A) {
   const Beta64Axis &X = A.ax[blockIdx.y];
   const int n = X.n, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -122,15 +125,15 @@ __global__ __launch_bounds__(256) void k_beta64(Beta64Args A) {
       const double v = __dadd_rn(__ddiv_rn(__dsub_rn(S, s), (double)(2 * (n - w))), __ddiv_rn(s, (double)(2 * w)));
       const double b = __dmul_rn(v, v);
       col[cnt] = b;
-      if (!have || (!isnan(bv) && (isnan(b) || b > bv))) { bv = b; have = true; }
+      if (!have || (!isnan(bv) && (isnan(b) || (DARK ? b < bv : b > bv)))) { bv = b; have = true; }
     }
     bc = c;
   }
-  // first maximum of the workgroup: wavefront shuffles, then the four wavefronts in order through LDS
+  // first maximum (DARK: minimum) of the workgroup: wavefront shuffles, then the four wavefronts in order through LDS
   for (int off = 32; off > 0; off >>= 1) {
     const double ov = __shfl_xor(bv, off, 64);
     const int oc = __shfl_xor(bc, off, 64);
-    if (oc != 0x7fffffff && (bc == 0x7fffffff || beats64(ov, oc, bv, bc))) { bv = ov; bc = oc; }
+    if (oc != 0x7fffffff && (bc == 0x7fffffff || beats64<DARK>(ov, oc, bv, bc))) { bv = ov; bc = oc; }
   }
   __shared__ double sv[4];
   __shared__ int sc[4];
@@ -138,21 +141,22 @@ __global__ __launch_bounds__(256) void k_beta64(Beta64Args A) {
   __syncthreads();
   if (threadIdx.x == 0) {
     for (int k = 1; k < (int)(blockDim.x >> 6); ++k)
-      if (sc[k] != 0x7fffffff && beats64(sv[k], sc[k], bv, bc)) { bv = sv[k]; bc = sc[k]; }
+      if (sc[k] != 0x7fffffff && beats64<DARK>(sv[k], sc[k], bv, bc)) { bv = sv[k]; bc = sc[k]; }
     X.blk[blockIdx.x].v = bv; X.blk[blockIdx.x].c = bc;
   }
 }
 
 // the two columns: s_x = argmax of the new beta_x; s_y = the PENDING argmax of beta_y (the previous call's, :66), and the new
-// one becomes pending.  current_sy: the option "vsync_current_sy" (s_y of this image).
+// one becomes pending.  current_sy: the option "vsync_current_sy" (s_y of this image).  DARK: argmin on both axes.
+template <bool DARK>
 __global__ void k_pick64(const Best64 *__restrict__ bx, int nbx, const Best64 *__restrict__ by, int nby, int *__restrict__ pending,
                          int *__restrict__ out, int current_sy) {
   if (threadIdx.x != 0) return;
   double v = bx[0].v; int c = bx[0].c;
-  for (int k = 1; k < nbx; ++k) if (beats64(bx[k].v, bx[k].c, v, c)) { v = bx[k].v; c = bx[k].c; }
+  for (int k = 1; k < nbx; ++k) if (beats64<DARK>(bx[k].v, bx[k].c, v, c)) { v = bx[k].v; c = bx[k].c; }
   const int sx = c;
   v = by[0].v; c = by[0].c;
-  for (int k = 1; k < nby; ++k) if (beats64(by[k].v, by[k].c, v, c)) { v = by[k].v; c = by[k].c; }
+  for (int k = 1; k < nby; ++k) if (beats64<DARK>(by[k].v, by[k].c, v, c)) { v = by[k].v; c = by[k].c; }
   const int old_sy = pending[0];
   pending[0] = c;
   if (out) { out[0] = current_sy ? c : old_sy; out[1] = sx; }
@@ -217,8 +221,11 @@ int tsdr_vsync_f64_d(tsdr_sync *s, const double *img, int *s_yx_dev) {
   const int nbx = beta_blocks(x), nby = beta_blocks(y);
   A.ax[0] = Beta64Axis{cvf, x, s->wmin_x, s->wmax_x, s->beta64_x, reinterpret_cast<Best64 *>(s->blk64)};
   A.ax[1] = Beta64Axis{chf, y, s->wmin_y, s->wmax_y, s->beta64_y, reinterpret_cast<Best64 *>(s->blk64) + nbx};
-  TSDR_LAUNCH(ctx, "vsync_f64_beta", k_beta64, dim3((unsigned)std::max(nbx, nby), 2), dim3(256), 0, A);
-  TSDR_LAUNCH(ctx, "vsync_f64_pick", k_pick64, dim3(1), dim3(64), 0, (const Best64 *)A.ax[0].blk, nbx, (const Best64 *)A.ax[1].blk, nby,
+  const bool dark = ctx->opt_vsync_blank_dark != 0;
+  void (*const kbeta)(Beta64Args) = dark ? k_beta64<true> : k_beta64<false>;
+  void (*const kpick)(const Best64 *, int, const Best64 *, int, int *, int *, int) = dark ? k_pick64<true> : k_pick64<false>;
+  TSDR_LAUNCH(ctx, "vsync_f64_beta", kbeta, dim3((unsigned)std::max(nbx, nby), 2), dim3(256), 0, A);
+  TSDR_LAUNCH(ctx, "vsync_f64_pick", kpick, dim3(1), dim3(64), 0, (const Best64 *)A.ax[0].blk, nbx, (const Best64 *)A.ax[1].blk, nby,
               s->pending, s_yx_dev, ctx->opt_vsync_current_sy);
   return TSDR_OK;
 }
@@ -260,7 +267,7 @@ int tsdr_fill_beta_f64(tsdr_ctx *ctx, const double *cv, int n, int w_min, int w_
     Beta64Args A;
     A.ax[0] = Beta64Axis{(const double *)i, n, w_min, w_max, (double *)o, blk};
     A.ax[1] = A.ax[0];
-    TSDR_LAUNCH(ctx, "fill_beta_f64", k_beta64, dim3((unsigned)beta_blocks(n), 1), dim3(256), 0, A);
+    TSDR_LAUNCH(ctx, "fill_beta_f64", k_beta64<false>, dim3((unsigned)beta_blocks(n), 1), dim3(256), 0, A);
     return (int)TSDR_OK;
   });
 }

@@ -23,6 +23,7 @@ export SyncXY, vsync
 export hip_frames!, hip_frames_submit!, hip_frames_submit_sc16!, hip_frames_submit_iq!, hip_frames_flush, hip_synchronize   # fused GUI.jl:163-178 loop body (optional fast path; pipelined form)
 export hip_extract_configuration, sync_guard_stats, sync_guard_auto, wait_stats   # fused GUI.jl:67-81 search; counters of the FAST loop's sync guard
 export hip_set_precision, hip_set_option                              # TSDR_EXACT / TSDR_FAST and the library's options, per task context
+export arg_area_blank!                                                # FrameSynchronisation.jl:53's binding: findmax (bright blanking) or findmin
 export HipGroup, hip_group                                            # one process, several GPUs (RCCL inside the library): `devices = ...`
 export hip_abs2, hip_imresize, hip_sync_beta, hip_fill_beta                 # Float64 / ComplexF64 helpers (abs2, imresize, beta fields, fill_beta!)
 
@@ -513,11 +514,26 @@ function hip_set_precision(mode::Symbol)
     return mode
 end
 
-"`tsdr_set_option` on this task's context: \"sync_guard_ppb\", \"sync_guard_auto\", \"vsync_current_sy\", \"ac_mixed\", ... (include/tempest_hip.h)"
+"`tsdr_set_option` on this task's context: \"sync_guard_ppb\", \"sync_guard_auto\", \"vsync_current_sy\", \"vsync_blank_dark\", \"ac_mixed\", ... (include/tempest_hip.h)"
 function hip_set_option(name::AbstractString, value::Integer)
     c = ctx()
     check(c, ccall((:tsdr_set_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Cint), c.h, name, value), "set_option($name)")
     return nothing
+end
+
+"""
+    arg_area_blank!(findmax)     # the blanking interval is the brightest band (default; the reference as it stands)
+    arg_area_blank!(findmin)     # it is the darkest band
+
+The reference's one-word binding `arg_area_blank = findmax` (FrameSynchronisation.jl:51-53) as a setting of this task's
+context: option "vsync_blank_dark" of `tsdr_set_option`.  Applies to `vsync` and the frame loop from the next call on; buffers
+already submitted keep theirs.  The pending s_y is kept as an index: the first s_y after a change is the old polarity's
+(reset the SyncXY for reference-equal behaviour).
+"""
+function arg_area_blank!(f::Function)
+    f === findmin || f === findmax || throw(ArgumentError("arg_area_blank! takes findmin or findmax"))
+    hip_set_option("vsync_blank_dark", f === findmin ? 1 : 0)
+    return f
 end
 
 "(frames checked, frames re-evaluated in the exact sequence) by the TSDR_FAST frame loop's sync guard on this task's context"

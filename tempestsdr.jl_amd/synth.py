@@ -2,7 +2,8 @@
 
 A test card (bars + checker + text-like block) sits inside an x_t x y_t TOTAL raster whose
 blanking is white (the reference's vsync looks for a bright band: arg_area_blank = findmax,
-FrameSynchronisation.jl:53).  The pixel stream runs at f_pix = x_t*y_t*fv; each IQ sample is
+FrameSynchronisation.jl:53) or, with the "_dark" profiles, black (findmin: the library's option
+"vsync_blank_dark").  The pixel stream runs at f_pix = x_t*y_t*fv; each IQ sample is
 the box average of the pixel stream over one sample period, AM-modulated on a slowly rotating
 carrier, plus complex Gaussian noise.  Everything is keyed by a counter-based RNG
 (SplitMix64 of seed and sample index) so any slice can be regenerated identically.
@@ -52,17 +53,23 @@ def gaussian_complex(seed, n0, n):
 #              triangle in c with its apex on the band -- a clear, unique answer.  (Frames of one buffer still drift by
 #              Fs/fv - round(Fs/fv) samples each, so the apex crosses the column grid: C2's default offset is chosen so
 #              that the ten phases of its 0.9-column drift stay 0.05 columns away from a two-column tie.)
+#   "box_dark", "plateau_dark": the same two profiles with every blanking level mirrored (1 - level): porches at 0.7 and a
+#              black (0.0) band, or the whole interval at 0.0 -- the blanking is the DARKEST band of the picture, what the
+#              reference's arg_area_blank = findmin is for.  The active area (the card) is the same.
 BLANK_BOX = dict(porch=0.3, bx=0.1013, by=0.0217, px=0.35, py=0.3, row0_frac=400 / 1125, col0_frac=1101 / 2576)
 
 
 def test_card(x_t, y_t, active_w=None, active_h=None, row0=0, col0=0, seed=SEED, blank="box"):
-    """(y_t, x_t) float32 in [0,1]: test card in the active area, blanking per `blank` ("box" or "plateau", above), then
-    rolled by (row0, col0) so start-of-frame sits at a known non-zero offset."""
+    """(y_t, x_t) float32 in [0,1]: test card in the active area, blanking per `blank` ("box", "plateau" or their "_dark"
+    mirrors, above), then rolled by (row0, col0) so start-of-frame sits at a known non-zero offset."""
     if active_w is None:
         active_w = int(round(x_t * 0.78))
     if active_h is None:
         active_h = int(round(y_t * 0.955))
     img = np.ones((y_t, x_t), np.float32)
+    dark = blank in ("box_dark", "plateau_dark")
+    if dark:
+        blank = blank[:-5]
     if blank == "box":
         b = BLANK_BOX
         nbx, nby = x_t - active_w, y_t - active_h
@@ -78,6 +85,8 @@ def test_card(x_t, y_t, active_w=None, active_h=None, row0=0, col0=0, seed=SEED,
         img[active_h:, active_w:] = np.maximum(ty[:, None], tx[None, :])
     elif blank != "plateau":
         raise ValueError(f"unknown blanking profile {blank!r}")
+    if dark:
+        img = np.float32(1.0) - img
     yy, xx = np.mgrid[0:active_h, 0:active_w]
     bars = (7 - (xx * 8) // active_w).astype(np.float32) / 7.0 * 0.8  # 8 grey bars, bright -> dark
     card = bars.copy()
@@ -96,16 +105,16 @@ def test_card(x_t, y_t, active_w=None, active_h=None, row0=0, col0=0, seed=SEED,
 
 def synth_leak(Fs, x_t, y_t, fv, n_samples, *, n0=0, card="box", seed=SEED, snr_db=20.0, amp=5e-3, df=1e3,
                phi0=0.3, row0=None, col0=None, chunk=1 << 20):
-    """complex64 IQ[n0 : n0+n_samples] of the synthetic leak.  card: a blanking profile name ("box", the default, or
-    "plateau": see test_card) or a ready (y_t, x_t) image.  row0 / col0: start-of-frame offset in raster lines / pixels
-    (defaults: 37 / 211 for "plateau", the fractions of BLANK_BOX for "box")."""
+    """complex64 IQ[n0 : n0+n_samples] of the synthetic leak.  card: a blanking profile name ("box", the default,
+    "plateau", "box_dark" or "plateau_dark": see test_card) or a ready (y_t, x_t) image.  row0 / col0: start-of-frame offset
+    in raster lines / pixels (defaults: 37 / 211 for the plateau profiles, the fractions of BLANK_BOX for the box ones)."""
     if card is None:
         card = "box"
     if isinstance(card, str):
         if row0 is None:
-            row0 = 37 if card == "plateau" else int(round(BLANK_BOX["row0_frac"] * y_t))
+            row0 = 37 if card.startswith("plateau") else int(round(BLANK_BOX["row0_frac"] * y_t))
         if col0 is None:
-            col0 = 211 if card == "plateau" else int(round(BLANK_BOX["col0_frac"] * x_t))
+            col0 = 211 if card.startswith("plateau") else int(round(BLANK_BOX["col0_frac"] * x_t))
         card = test_card(x_t, y_t, row0=row0 % y_t, col0=col0 % x_t, seed=seed, blank=card)
     flat = card.reshape(-1).astype(np.float64)  # line-major pixel stream of one frame
     P = flat.size
