@@ -4,7 +4,11 @@
 // hash over the canonical dump of the step's kernel parameters.
 //   fft_plan_dump              every case (tests/test_fft_plan_host.py compares this with tests/golden/fft_plans_v1.txt)
 //   fft_plan_dump --full ID    the canonical parameter dump of one case
+//   fft_plan_dump --rows WHAT KIND N ROWS CUS    one whole-row request (WHAT: welch | store | wfall; KIND: SIG_* as a number) on a device of
+//                              CUS compute units: the step's profile name, kernel, grid, and the tiles its workgroups walk
+//                              (tests/test_grid_cap_host.py: ntiles > grid is a tile loop that takes a second trip)
 // Build, host only:  hipcc --cuda-host-only -std=c++17 -ffp-contract=off -Iinclude tools/host_plan/fft_plan_dump_main.hip -o fft_plan_dump
+#include <cstdlib>
 #include <cstring>
 
 #include "../../tempestsdr.jl_amd/csrc/fft_plan.h"
@@ -84,9 +88,35 @@ static fft_plan_dump::Outcome run(const fft_plan_dump::Case &c) {
   return out;
 }
 
+// plan_rows for one request given on the command line
+static int rows_query(char **a) {
+  using namespace fft_plan_dump;
+  Case c;
+  c.what = !std::strcmp(a[0], "welch") ? W_WELCH : !std::strcmp(a[0], "store") ? W_STORE : !std::strcmp(a[0], "wfall") ? W_WATERFALL : -1;
+  if (c.what < 0) { std::fprintf(stderr, "--rows: WHAT is welch, store or wfall\n"); return 2; }
+  c.sig_kind = std::atoi(a[1]); c.n = std::strtoull(a[2], nullptr, 10); c.batch = std::strtoull(a[3], nullptr, 10); c.cu_count = std::atoi(a[4]);
+  c.src_scale = c.sig_kind >= 2 ? 1.0f / 128.0f : 1.0f;
+  FftOpts o;
+  o.cu_count = c.cu_count;
+  RowsReq r;
+  r.what = c.what == W_WELCH ? ROWS_TO_WELCH : c.what == W_STORE ? ROWS_TO_STORE : ROWS_TO_WATERFALL;
+  r.kind = c.sig_kind; r.sig_scale = c.src_scale; r.N = (size_t)c.n; r.rows = (size_t)c.batch;
+  r.acc = reinterpret_cast<float *>(0x52000000ull); r.rows_out = reinterpret_cast<float2 *>(0x20000000ull); r.wf = reinterpret_cast<double *>(0x54000000ull);
+  FftPlan pl;
+  plan_rows(pl, r, o);
+  if (pl.status) { std::printf("status=%d err=\"%s\"\n", pl.status, pl.err); return 0; }
+  if (pl.nsteps != 1) { std::printf("declined\n"); return 0; }
+  const FftStep &s = pl.step[0];
+  const unsigned long long per_tile = 1ull << s.p.mix.logT;
+  std::printf("%s %s grid=%u block=%u rows_per_tile=%llu ntiles=%llu\n", s.name, kernel_text(s).c_str(), s.grid, s.block, per_tile,
+              (c.batch + per_tile - 1) / per_tile);
+  return 0;
+}
+
 int main(int argc, char **argv) {
+  if (argc == 7 && !std::strcmp(argv[1], "--rows")) return rows_query(argv + 2);
   const char *want = (argc == 3 && !std::strcmp(argv[1], "--full")) ? argv[2] : nullptr;
-  if (argc != 1 && !want) { std::fprintf(stderr, "usage: %s [--full ID]\n", argv[0]); return 2; }
+  if (argc != 1 && !want) { std::fprintf(stderr, "usage: %s [--full ID | --rows WHAT KIND N ROWS CUS]\n", argv[0]); return 2; }
   bool found = false;
   for (const fft_plan_dump::Case &c : fft_plan_dump::cases()) {
     if (want && c.id != want) continue;

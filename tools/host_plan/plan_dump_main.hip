@@ -3,7 +3,10 @@
 // LDS bytes and a 64-bit FNV-1a hash over the canonical dump of the step's kernel parameters.
 //   plan_dump              every case (tests/test_image_plan_host.py compares this with tests/golden/image_plans_v1.txt)
 //   plan_dump --full ID    the canonical parameter dump of one case
+//   plan_dump --one FMT EXACT S Y_T X_T FRAMES RASTER IMAGES CUS    the line of one IQ request given on the command line (FMT: 0 cf32,
+//                          1 sc16, 2 sc8, 3 uc8; tests/test_grid_cap_host.py: the direct raster kernel's grid against its work)
 // Build, host only:  hipcc --cuda-host-only -std=c++17 -ffp-contract=off -Iinclude tools/host_plan/plan_dump_main.hip -o plan_dump
+#include <cstdlib>
 #include <cstring>
 
 #include "../../tempestsdr.jl_amd/csrc/image_plan.h"
@@ -67,8 +70,16 @@ static plan_dump::Outcome run(const plan_dump::Case &c) {
 }
 
 int main(int argc, char **argv) {
+  if (argc == 11 && !std::strcmp(argv[1], "--one")) {
+    plan_dump::Case c;
+    c.id = "one"; c.cplx = 1; c.fmt = std::atoi(argv[2]); c.scale = c.fmt ? 1.0f / 128.0f : 1.0f; c.exact = std::atoi(argv[3]);
+    c.S = std::strtoull(argv[4], nullptr, 10); c.y_t = std::atoi(argv[5]); c.x_t = std::atoi(argv[6]); c.frames = std::atoi(argv[7]);
+    c.raster = std::atoi(argv[8]); c.images = std::atoi(argv[9]); c.cu_count = std::atoi(argv[10]);
+    std::puts(plan_dump::line(c.id.c_str(), run(c)).c_str());
+    return 0;
+  }
   const char *want = (argc == 3 && !std::strcmp(argv[1], "--full")) ? argv[2] : nullptr;
-  if (argc != 1 && !want) { std::fprintf(stderr, "usage: %s [--full ID]\n", argv[0]); return 2; }
+  if (argc != 1 && !want) { std::fprintf(stderr, "usage: %s [--full ID | --one FMT EXACT S Y_T X_T FRAMES RASTER IMAGES CUS]\n", argv[0]); return 2; }
   bool found = false;
   for (const plan_dump::Case &c : plan_dump::cases()) {
     if (want && c.id != want) continue;
