@@ -530,6 +530,9 @@ int tsdr_frames_submit_iq_d(tsdr_ctx *ctx, tsdr_sync *sync, const void *iq, int 
  * (-1 while measuring); ms_per_buffer[c] = mean interval between the tails of successive buffers under candidate c (0: not
  * yet measured), min(cap, 8) entries; text: the same as one line, with the candidates' names. */
 int tsdr_frames_pipeline_info(tsdr_ctx *ctx, int *trials_left, int *chosen, float *ms_per_buffer, int cap, char *text, size_t text_cap);
+/* frame averaging at the monitor's own resolution: the aligned IIR on the y_t x x_t rasters (one streaming launch), and the frame
+ * loop that feeds it chunk by chunk -- their contract (SEMANTICS / SHIFT UNITS / EDGE CASES / COST / THE WHOLE LOOP) */
+#include "tempest_hip_hires.h"
 
 /* ---- host -> device staging ring ---------------------------------------
  * The consumer side of AtomicCircularBuffer (AtomicAbstractSDRs.jl:64-190): `depth` slots of nEch samples in

@@ -218,6 +218,17 @@ _SIGS_CPLX = {
     "tsdr_autocorr_cplx_f64_d": (C.c_int, [vp, vp] + _AC),
 }
 
+# include/tempest_hip_hires.h (the third header tempest_hip.h includes): the aligned IIR on the y_t x x_t rasters and the frame loop
+# that feeds it
+_ACC = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_float, vp]   # rasters, n, y_t, x_t, shifts, units, img_h, img_w, alpha, state
+_SIGS_HIRES = {
+    "tsdr_raster_accum": (C.c_int, [vp] + _ACC),
+    "tsdr_raster_accum_d": (C.c_int, [vp] + _ACC),
+    "tsdr_frames_hires_iq_d": (C.c_int, [vp, vp, vp, C.c_int, C.c_float, c_sz, c_sz, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, C.c_float,
+                                         vp, vp, c_i]),
+}
+SHIFT_RASTER, SHIFT_IMAGE = 0, 1  # TSDR_SHIFT_*
+
 
 def exported_names():
     """Every symbol include/tempest_hip.h declares (kept in sync by tests/test_abi.py)."""
@@ -232,6 +243,11 @@ def exported_names_iq():
 def exported_names_cplx():
     """Every symbol include/tempest_hip_cplx.h declares (kept in sync by tests/test_autocorr_complex_host.py)."""
     return sorted(_SIGS_CPLX)
+
+
+def exported_names_hires():
+    """Every symbol include/tempest_hip_hires.h declares (kept in sync by tests/test_hires_host.py)."""
+    return sorted(_SIGS_HIRES)
 
 
 def _share_torch_hip_runtime():
@@ -259,7 +275,7 @@ def load():
             f"{LIB_PATH} not found: build it with `python tempestsdr.jl_amd/build.py` "
             "(there is no CPU fallback)")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_IQ.items()) + list(_SIGS_CPLX.items()):
+    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_IQ.items()) + list(_SIGS_CPLX.items()) + list(_SIGS_HIRES.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI is incomplete
         fn.restype = res
         fn.argtypes = args

@@ -567,6 +567,30 @@ class Context:
             out["raster"] = [raster[f].reshape((int(y_t), int(x_t)), order="F") for f in range(nb)]
         return out
 
+    # -- the same average at the monitor's own resolution (include/tempest_hip_hires.h; hires.py) -----------
+    def raster_accumulate(self, rasters, state, alpha, shifts=None, units="raster", grid=(RENDER_H, RENDER_W)):
+        """state (y_t x x_t, Fortran-order float32, in place) <- alpha*state + (1-alpha)*circshift(raster, -shift), raster by
+        raster: GUI.jl:172,175 at raster size.  shifts: one (s_y, s_x) per raster in raster lines / pixels (units="raster") or as
+        indices of a `grid` sync image (units="image", what the frame loop's sync_idx holds); None: no shift."""
+        return hires.raster_accumulate(self, rasters, state, alpha, shifts, units, grid)
+
+    def raster_accumulate_d(self, rasters, n_frames, y_t, x_t, alpha, state, shifts=None, units="raster", grid=(RENDER_H, RENDER_W)):
+        """device-pointer form of raster_accumulate: enqueues on the context's stream and returns"""
+        return hires.raster_accum_d(self, rasters, n_frames, y_t, x_t, alpha, state, shifts, units, grid)
+
+    def frames_hires(self, sync, iq, S, y_t, x_t, alpha, imageOut, alpha_hires, hires_state, iq_fmt=None, iq_scale=1.0, do_align=True,
+                     want_frames=True):
+        """Context.frames plus hires_state (y_t x x_t, in place): the buffer's rasters, registered by the loop's own sync indices
+        and averaged with alpha_hires.  Returns dict(n_frames, frames, sync_idx)."""
+        return hires.frames_hires(self, sync, iq, S, y_t, x_t, alpha, imageOut, alpha_hires, hires_state, iq_fmt, iq_scale, do_align,
+                                  want_frames)
+
+    def frames_hires_d(self, sync, iq, fmt, scale, nEch, S, y_t, x_t, alpha, do_align, state, alpha_hires, hires_state, frames_out=None,
+                       sync_idx=None):
+        """device-pointer form of frames_hires (iq: nEch samples of format `fmt`): enqueues and returns the number of frames"""
+        return hires.frames_hires_d(self, sync, iq, fmt, scale, nEch, S, y_t, x_t, alpha, do_align, state, alpha_hires, hires_state,
+                                    frames_out, sync_idx)
+
 
 def frames_d(ctx, sync, iq, nEch, S, y_t, x_t, alpha, do_align, state, frames_out=None, raster_out=None, sync_idx=None):
     """Device-pointer form of Context.frames: every array argument is a device buffer (torch tensor
@@ -636,6 +660,8 @@ def _int_iq(sig, iq_fmt, what):
 from .iq import DEMOD_IQ, demod_iq_d, expand_iq_d, spectrum_iq_d, waterfall_iq_d, welch_iq_d  # noqa: E402
 # calculate_autocorrelation of complex input (the entry points of include/tempest_hip_cplx.h): autocorr_cplx.py
 from . import autocorr_cplx  # noqa: E402
+# the aligned IIR on the full-size rasters and the loop that feeds it (the entry points of include/tempest_hip_hires.h): hires.py
+from . import hires  # noqa: E402
 
 
 def frames_iq_d(ctx, sync, iq, fmt, scale, nEch, S, y_t, x_t, alpha, do_align, state, frames_out=None, raster_out=None, sync_idx=None,

@@ -34,6 +34,8 @@ enum Slot {
   WS_F64_B,       // call never moves a workspace the f32 paths hold
   WS_F64_C,
   WS_IQX,         // integer IQ expanded to ComplexF32 for the transform routes without a loader hook (tsdr_*_iq_d)
+  WS_HIRES,       // tsdr_frames_hires_iq_d: the rasters of one chunk of frames (raster_accum.hip)
+  WS_HIRES_IDX,   // ... and the buffer's sync indices when the caller passes none
   WS_COUNT
 };
 
@@ -82,6 +84,7 @@ struct tsdr_ctx {
   int opt_fft_big = 1;      // mixed-radix planner may use factors of 500 / 1000 / 2000 (three-register-step kernels)
   int opt_vsync_blank_dark = 0;  // 1: the blanking interval is the DARKEST band: findmin instead of findmax on both axes (FrameSynchronisation.jl:51-53)
   int opt_vsync_current_sy = 0;  // 1: vsync / the frame loop return s_y of the CURRENT image (the corrected ordering, off by default)
+  int opt_hires_chunk_frames = 0; // tsdr_frames_hires_iq_d: frames per chunk (0: the whole buffer in one chunk, the measured optimum)
   int opt_fast_walk_only = 0;    // 1: the raster-free FAST frame path runs the raster walk with out == null (round 2's route; A/B)
   int opt_down_spp_max_pct = 200; // raster-free FAST route: k_down_fused up to this many samples per raster pixel (percent), the raster walk above
                                   // (round 4: 50 -> 200 once wide rows stage with 16 loads in flight: C3 0.40 -> 0.24 ms per buffer)

@@ -714,5 +714,7 @@ end
 include("TempestHIP_iq.jl")
 # calculate_autocorrelation of ComplexF32 / ComplexF64 / integer IQ vectors (include/tempest_hip_cplx.h)
 include("TempestHIP_cplx.jl")
+# frame averaging at the monitor's own resolution: hip_raster_accumulate!, hip_frames_hires! (include/tempest_hip_hires.h)
+include("TempestHIP_hires.jl")
 
 end # module
