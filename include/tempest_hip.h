@@ -533,6 +533,8 @@ int tsdr_frames_pipeline_info(tsdr_ctx *ctx, int *trials_left, int *chosen, floa
 /* frame averaging at the monitor's own resolution: the aligned IIR on the y_t x x_t rasters (one streaming launch), and the frame
  * loop that feeds it chunk by chunk -- their contract (SEMANTICS / SHIFT UNITS / EDGE CASES / COST / THE WHOLE LOOP) */
 #include "tempest_hip_hires.h"
+/* registration of those rasters to the raster pixel: profiles, scores, the ordered choice, and the loop's option "hires_refine" */
+#include "tempest_hip_register.h"
 
 /* ---- host -> device staging ring ---------------------------------------
  * The consumer side of AtomicCircularBuffer (AtomicAbstractSDRs.jl:64-190): `depth` slots of nEch samples in

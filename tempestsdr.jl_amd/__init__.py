@@ -7,7 +7,7 @@ The directory name carries a dot, so it cannot be imported with a plain `import`
 
 Contents: csrc/ (hand-written HIP kernels + the C ABI), _lib.py (ctypes binding),
 api.py (host mirror with the reference's function names), hires.py (frame averaging at the
-monitor's own resolution), synth.py (synthetic leak
+monitor's own resolution), register.py (its registration to the raster pixel), synth.py (synthetic leak
 generator for tests/bench), video_configurations.py and dat_files.py (the callers'
 data formats either side of the hot path), parallel.py (one-process-per-GPU sharding),
 julia/TempestHIP.jl (the `ccall` shim the Julia runtime loads).

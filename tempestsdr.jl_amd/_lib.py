@@ -229,6 +229,15 @@ _SIGS_HIRES = {
 }
 SHIFT_RASTER, SHIFT_IMAGE = 0, 1  # TSDR_SHIFT_*
 
+# include/tempest_hip_register.h (included after tempest_hip_hires.h): registration of the full-size rasters to the raster pixel
+_REG = [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]  # rasters, n, y_t, x_t, ref, shifts, units, img_h, img_w, d_y, d_x, shifts_out, scores
+_SIGS_REGISTER = {
+    "tsdr_raster_profiles_d": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "tsdr_raster_register_d": (C.c_int, [vp] + _REG),
+    "tsdr_raster_register": (C.c_int, [vp] + _REG),
+    "tsdr_frames_hires_shifts": (C.c_int, [vp, C.c_int, c_i, c_i]),
+}
+
 
 def exported_names():
     """Every symbol include/tempest_hip.h declares (kept in sync by tests/test_abi.py)."""
@@ -248,6 +257,11 @@ def exported_names_cplx():
 def exported_names_hires():
     """Every symbol include/tempest_hip_hires.h declares (kept in sync by tests/test_hires_host.py)."""
     return sorted(_SIGS_HIRES)
+
+
+def exported_names_register():
+    """Every symbol include/tempest_hip_register.h declares (kept in sync by tests/test_register_host.py)."""
+    return sorted(_SIGS_REGISTER)
 
 
 def _share_torch_hip_runtime():
@@ -275,7 +289,8 @@ def load():
             f"{LIB_PATH} not found: build it with `python tempestsdr.jl_amd/build.py` "
             "(there is no CPU fallback)")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_IQ.items()) + list(_SIGS_CPLX.items()) + list(_SIGS_HIRES.items()):
+    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_IQ.items()) + list(_SIGS_CPLX.items()) + list(_SIGS_HIRES.items()) + \
+            list(_SIGS_REGISTER.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI is incomplete
         fn.restype = res
         fn.argtypes = args

@@ -591,6 +591,25 @@ class Context:
         return hires.frames_hires_d(self, sync, iq, fmt, scale, nEch, S, y_t, x_t, alpha, do_align, state, alpha_hires, hires_state,
                                     frames_out, sync_idx)
 
+    # -- registration of those rasters to the raster pixel (include/tempest_hip_register.h; register.py) -----------
+    def raster_profiles(self, rasters):
+        """-> (col (n, x_t), row (n, y_t)) float64: the sums over rows and over columns of n rasters (y_t, x_t)"""
+        return register.raster_profiles(self, rasters)
+
+    def raster_register(self, rasters, d_y, d_x, ref=None, shifts=None, units="raster", grid=(RENDER_H, RENDER_W), want_scores=False):
+        """-> (n, 2) int32 shifts in raster units: the coarse `shifts` (None: 0) refined by at most d_y lines / d_x pixels against
+        `ref` (None, or a flat picture: the first raster)"""
+        return register.raster_register(self, rasters, d_y, d_x, ref, shifts, units, grid, want_scores)
+
+    def raster_register_d(self, rasters, n_frames, y_t, x_t, d_y, d_x, shifts_out, ref=None, shifts=None, units="raster",
+                          grid=(RENDER_H, RENDER_W), scores=None):
+        """device-pointer form of raster_register: enqueues on the context's stream and returns"""
+        return register.raster_register_d(self, rasters, n_frames, y_t, x_t, d_y, d_x, shifts_out, ref, shifts, units, grid, scores)
+
+    def hires_shifts(self, max_frames=1 << 16):
+        """(n, 2) int32: the raster-unit shifts the most recent frames_hires call averaged its rasters with (synchronises)"""
+        return register.hires_shifts(self, max_frames)
+
 
 def frames_d(ctx, sync, iq, nEch, S, y_t, x_t, alpha, do_align, state, frames_out=None, raster_out=None, sync_idx=None):
     """Device-pointer form of Context.frames: every array argument is a device buffer (torch tensor
@@ -662,6 +681,8 @@ from .iq import DEMOD_IQ, demod_iq_d, expand_iq_d, spectrum_iq_d, waterfall_iq_d
 from . import autocorr_cplx  # noqa: E402
 # the aligned IIR on the full-size rasters and the loop that feeds it (the entry points of include/tempest_hip_hires.h): hires.py
 from . import hires  # noqa: E402
+# their registration to the raster pixel (the entry points of include/tempest_hip_register.h): register.py
+from . import register  # noqa: E402
 
 
 def frames_iq_d(ctx, sync, iq, fmt, scale, nEch, S, y_t, x_t, alpha, do_align, state, frames_out=None, raster_out=None, sync_idx=None,

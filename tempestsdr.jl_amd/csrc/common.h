@@ -36,6 +36,10 @@ enum Slot {
   WS_IQX,         // integer IQ expanded to ComplexF32 for the transform routes without a loader hook (tsdr_*_iq_d)
   WS_HIRES,       // tsdr_frames_hires_iq_d: the rasters of one chunk of frames (raster_accum.hip)
   WS_HIRES_IDX,   // ... and the buffer's sync indices when the caller passes none
+  WS_HIRES_SHIFTS,  // ... and the raster-unit shifts its frames were averaged with (tsdr_frames_hires_shifts)
+  WS_REG_PART,    // raster_register.hip: per-tile partial sums of the profiles (f64), column partials then row partials
+  WS_REG_PROF,    // ... the profiles of a registration's frames and of its reference (f64)
+  WS_REG_SCORES,  // ... its scores when the caller asks for none
   WS_COUNT
 };
 
@@ -85,7 +89,10 @@ struct tsdr_ctx {
   int opt_vsync_blank_dark = 0;  // 1: the blanking interval is the DARKEST band: findmin instead of findmax on both axes (FrameSynchronisation.jl:51-53)
   int opt_vsync_current_sy = 0;  // 1: vsync / the frame loop return s_y of the CURRENT image (the corrected ordering, off by default)
   int opt_hires_chunk_frames = 0; // tsdr_frames_hires_iq_d: frames per chunk (0: the whole buffer in one chunk, the measured optimum)
-  int opt_fast_walk_only = 0;    // 1: the raster-free FAST frame path runs the raster walk with out == null (round 2's route; A/B)
+  int opt_hires_refine = 0;       // tsdr_frames_hires_iq_d: 0..8, the registration's search radius in cells of the 600x800 sync grid (0: off;
+                                  // include/tempest_hip_register.h)
+  int hires_shifts_n = 0;         // frames of the most recent tsdr_frames_hires_iq_d whose applied shifts WS_HIRES_SHIFTS holds
+  int opt_fast_walk_only = 0;   // 1: the raster-free FAST frame path runs the raster walk with out == null (round 2's route; A/B)
   int opt_down_spp_max_pct = 200; // raster-free FAST route: k_down_fused up to this many samples per raster pixel (percent), the raster walk above
                                   // (round 4: 50 -> 200 once wide rows stage with 16 loads in flight: C3 0.40 -> 0.24 ms per buffer)
   int opt_down_xcd = 1;      // raster-free FAST kernel: XCD-aware tile order

@@ -3,11 +3,15 @@
 //   k_raster_accum          A = alpha*A + (1-alpha)*circshift(R_f, -r_f) over the y_t x x_t rasters of n frames, frames in order;
 //                           one launch, one lane per output pixel, n*4P + 8P bytes
 //   tsdr_frames_hires_iq_d  the frame loop in chunks of k frames: tsdr_frames_iq_d with the chunk's rasters in context
-//                           workspace, then one k_raster_accum over them with the loop's own sync indices
+//                           workspace, then one k_raster_accum over them with the loop's own sync indices -- or, under the option
+//                           "hires_refine", with those indices refined to the raster pixel (raster_register.hip)
 //
 // It cannot be part of the raster launch: a frame's shift is known only after vsync has seen its whole 600x800 image, and the
 // IIR is a recurrence across frames.  So it is a second stage over rasters the first stage has written.
+#include <algorithm>
+
 #include "common.h"
+#include "raster_shift.h"
 
 using namespace tsdr;
 
@@ -31,22 +35,6 @@ struct AccumArgs {
   int n, y_t, x_t, units, img_h, img_w;
   float alpha;
 };
-
-// floored modulus of a 64-bit value by a positive int
-__device__ inline int mod_floor(long long v, int m) {
-  const long long r = v % (long long)m;
-  return (int)(r < 0 ? r + m : r);
-}
-
-// one frame's shift in raster lines / pixels, 0 <= r < size (tempest_hip_hires.h, SHIFT UNITS).  |2*a*size + img| < 2^63 for
-// every int a and every size, img < 2^31.
-__device__ inline int resolve_shift(int a, int size, int units, int img) {
-  if (units == TSDR_SHIFT_RASTER) return mod_floor((long long)a, size);
-  const long long num = 2ll * (long long)a * (long long)size + (long long)img, den = 2ll * (long long)img;
-  long long q = num / den;
-  if (num % den < 0) --q;   // floored division
-  return mod_floor(q, size);
-}
 
 // SHIFTED: shifts given.  The (r_y, r_x) of a frame are the same for every pixel, and the rule above costs a 64-bit division:
 // each workgroup resolves them once per frame -- thread t the frame f0 + t of a tile of kShiftTile frames -- into LDS, and the
@@ -103,18 +91,8 @@ __global__ __launch_bounds__(kThreads) void k_raster_accum(AccumArgs A) {
 // everything tempest_hip_hires.h (EDGE CASES) refuses, before anything is enqueued or staged
 int accum_check(tsdr_ctx *ctx, const char *fn, const float *rasters, int n_frames, int y_t, int x_t, const int *shifts, int shift_units,
                 int img_h, int img_w, const float *state) {
-  if (!ctx) return TSDR_EINVAL;
-  if (y_t <= 0 || x_t <= 0) return set_err(ctx, TSDR_EINVAL, "%s: y_t and x_t must be positive (got %d, %d)", fn, y_t, x_t);
-  if (n_frames < 0) return set_err(ctx, TSDR_EINVAL, "%s: n_frames is negative (%d)", fn, n_frames);
-  if ((size_t)y_t * (size_t)x_t >= (size_t)1 << 31) return set_err(ctx, TSDR_EINVAL, "%s: y_t * x_t must be below 2^31", fn);
+  if (int rc = raster_args_check(ctx, fn, rasters, n_frames, y_t, x_t, shifts, shift_units, img_h, img_w)) return rc;
   if (!state) return set_err(ctx, TSDR_EINVAL, "%s: state is NULL", fn);
-  if (n_frames > 0 && !rasters) return set_err(ctx, TSDR_EINVAL, "%s: rasters is NULL", fn);
-  if (shift_units != TSDR_SHIFT_RASTER && shift_units != TSDR_SHIFT_IMAGE)
-    return set_err(ctx, TSDR_EINVAL, "%s: unknown shift_units %d", fn, shift_units);
-  if (shift_units == TSDR_SHIFT_IMAGE && (img_h <= 0 || img_w <= 0))
-    return set_err(ctx, TSDR_EINVAL, "%s: TSDR_SHIFT_IMAGE needs a positive img_h x img_w (got %d x %d)", fn, img_h, img_w);
-  TSDR_PTR_ALIGNED(ctx, fn, rasters, 4);
-  TSDR_PTR_ALIGNED(ctx, fn, shifts, 4);
   TSDR_PTR_ALIGNED(ctx, fn, state, 4);
   return TSDR_OK;
 }
@@ -130,6 +108,22 @@ int accum_launch(tsdr_ctx *ctx, const float *rasters, int n_frames, int y_t, int
 }
 
 }  // namespace
+
+int tsdr::raster_args_check(tsdr_ctx *ctx, const char *fn, const float *rasters, int n_frames, int y_t, int x_t, const int *shifts,
+                            int shift_units, int img_h, int img_w) {
+  if (!ctx) return TSDR_EINVAL;
+  if (y_t <= 0 || x_t <= 0) return set_err(ctx, TSDR_EINVAL, "%s: y_t and x_t must be positive (got %d, %d)", fn, y_t, x_t);
+  if (n_frames < 0) return set_err(ctx, TSDR_EINVAL, "%s: n_frames is negative (%d)", fn, n_frames);
+  if ((size_t)y_t * (size_t)x_t >= (size_t)1 << 31) return set_err(ctx, TSDR_EINVAL, "%s: y_t * x_t must be below 2^31", fn);
+  if (n_frames > 0 && !rasters) return set_err(ctx, TSDR_EINVAL, "%s: rasters is NULL", fn);
+  if (shift_units != TSDR_SHIFT_RASTER && shift_units != TSDR_SHIFT_IMAGE)
+    return set_err(ctx, TSDR_EINVAL, "%s: unknown shift_units %d", fn, shift_units);
+  if (shift_units == TSDR_SHIFT_IMAGE && (img_h <= 0 || img_w <= 0))
+    return set_err(ctx, TSDR_EINVAL, "%s: TSDR_SHIFT_IMAGE needs a positive img_h x img_w (got %d x %d)", fn, img_h, img_w);
+  TSDR_PTR_ALIGNED(ctx, fn, rasters, 4);
+  TSDR_PTR_ALIGNED(ctx, fn, shifts, 4);
+  return TSDR_OK;
+}
 
 extern "C" {
 
@@ -167,6 +161,7 @@ int tsdr_frames_hires_iq_d(tsdr_ctx *ctx, tsdr_sync *sync, const void *iq, int i
   TSDR_IQ_ARG(ctx, "frames_hires", iq, iq_fmt, scale, fmt);
   if (S == 0 || !imageOut_state || (nEch && !iq)) return TSDR_EINVAL;
   const size_t nb = nEch / S, P = (size_t)y_t * (size_t)x_t, npx = (size_t)TSDR_RENDER_H * TSDR_RENDER_W;
+  ctx->hires_shifts_n = 0;   // (tsdr_frames_hires_shifts: nothing applied yet)
   if (nb == 0 || nb > (size_t)1 << 20)   // nothing to average: tsdr_frames_iq_d's own answer (pending submissions, n_frames = 0, refusals)
     return tsdr_frames_iq_d(ctx, sync, iq, iq_fmt, scale, nEch, S, y_t, x_t, alpha, do_align, imageOut_state, frames_out, nullptr,
                             sync_idx, n_frames);
@@ -180,7 +175,13 @@ int tsdr_frames_hires_iq_d(tsdr_ctx *ctx, tsdr_sync *sync, const void *iq, int i
   float *rasters = (float *)ctx->scratch(WS_HIRES, k * P * 4);
   int *idx = sync_idx;
   if (do_align && !idx) idx = (int *)ctx->scratch(WS_HIRES_IDX, nb * 8);
-  if (!rasters || (do_align && !idx)) return TSDR_ENOMEM;
+  // the shifts each frame is averaged with, in raster units, kept for tsdr_frames_hires_shifts; with "hires_refine" they are the
+  // registration's (raster_register.hip) and what the accumulator consumes
+  int *applied = do_align ? (int *)ctx->scratch(WS_HIRES_SHIFTS, nb * 8) : nullptr;
+  if (!rasters || (do_align && (!idx || !applied))) return TSDR_ENOMEM;
+  const int refine = do_align ? ctx->opt_hires_refine : 0;
+  const int d_y = (int)std::min<long long>(((long long)refine * y_t + TSDR_RENDER_H - 1) / TSDR_RENDER_H, (y_t - 1) / 2);
+  const int d_x = (int)std::min<long long>(((long long)refine * x_t + TSDR_RENDER_W - 1) / TSDR_RENDER_W, (x_t - 1) / 2);
   if (n_frames) *n_frames = 0;
   for (size_t f0 = 0; f0 < nb; f0 += k) {
     const size_t cnt = nb - f0 < k ? nb - f0 : k;
@@ -190,9 +191,19 @@ int tsdr_frames_hires_iq_d(tsdr_ctx *ctx, tsdr_sync *sync, const void *iq, int i
                               &nf);
     if (rc) return rc;
     if ((size_t)nf != cnt) return set_err(ctx, TSDR_EHIP, "frames_hires: a chunk of %zu frames produced %d", cnt, nf);
-    rc = accum_launch(ctx, rasters, nf, y_t, x_t, do_align ? idx + 2 * f0 : nullptr, TSDR_SHIFT_IMAGE, TSDR_RENDER_H, TSDR_RENDER_W,
-                      alpha_hires, hires_state);
+    if (refine) {   // registered to the pixel against the state as this chunk finds it, then averaged with those shifts
+      rc = register_launch(ctx, rasters, nf, y_t, x_t, hires_state, idx + 2 * f0, TSDR_SHIFT_IMAGE, TSDR_RENDER_H, TSDR_RENDER_W, d_y, d_x,
+                           applied + 2 * f0, nullptr);
+      if (rc) return rc;
+      rc = accum_launch(ctx, rasters, nf, y_t, x_t, applied + 2 * f0, TSDR_SHIFT_RASTER, 0, 0, alpha_hires, hires_state);
+    } else {
+      rc = accum_launch(ctx, rasters, nf, y_t, x_t, do_align ? idx + 2 * f0 : nullptr, TSDR_SHIFT_IMAGE, TSDR_RENDER_H, TSDR_RENDER_W,
+                        alpha_hires, hires_state);
+      if (!rc && do_align)
+        rc = resolve_launch(ctx, nf, y_t, x_t, idx + 2 * f0, TSDR_SHIFT_IMAGE, TSDR_RENDER_H, TSDR_RENDER_W, applied + 2 * f0);
+    }
     if (rc) return rc;
+    if (do_align) ctx->hires_shifts_n += nf;
     if (n_frames) *n_frames += nf;
   }
   return TSDR_OK;

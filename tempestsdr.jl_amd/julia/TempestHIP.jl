@@ -716,5 +716,7 @@ include("TempestHIP_iq.jl")
 include("TempestHIP_cplx.jl")
 # frame averaging at the monitor's own resolution: hip_raster_accumulate!, hip_frames_hires! (include/tempest_hip_hires.h)
 include("TempestHIP_hires.jl")
+# registration of those rasters to the raster pixel: hip_raster_register!, hip_hires_refine! (include/tempest_hip_register.h)
+include("TempestHIP_register.jl")
 
 end # module
