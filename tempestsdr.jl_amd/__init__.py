@@ -7,7 +7,7 @@ The directory name carries a dot, so it cannot be imported with a plain `import`
 
 Contents: csrc/ (hand-written HIP kernels + the C ABI), _lib.py (ctypes binding),
 api.py (host mirror with the reference's function names), hires.py (frame averaging at the
-monitor's own resolution), register.py (its registration to the raster pixel), synth.py (synthetic leak
+monitor's own resolution), register.py (its registration to the raster pixel), display.py (ROI crop, range stretch and 8-bit output of any picture), synth.py (synthetic leak
 generator for tests/bench), video_configurations.py and dat_files.py (the callers'
 data formats either side of the hot path), parallel.py (one-process-per-GPU sharding),
 julia/TempestHIP.jl (the `ccall` shim the Julia runtime loads).
@@ -17,3 +17,4 @@ from ._lib import RENDER_H, RENDER_W, TempestHIPError  # noqa: F401
 from .api import (Context, Group, Resampler, StagingRing, SyncXY, amDemod, calculate_autocorrelation, default_context,  # noqa: F401
                   downgradeImage, fmDemod, getSpectrum, getWaterfall, getWelch, init_resampler, invert_amDemod,
                   naiveResampler, sig_to_image, vsync, zoom_autocorr)
+from .display import display_u8, display_u8_d  # noqa: F401

@@ -238,6 +238,17 @@ _SIGS_REGISTER = {
     "tsdr_frames_hires_shifts": (C.c_int, [vp, C.c_int, c_i, c_i]),
 }
 
+# include/tempest_hip_display.h (included after tempest_hip_register.h): ROI crop, range stretch and 8-bit output of f32 pictures
+_DISP = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_double, C.c_double,
+         C.c_int, vp, vp]  # images, n, h, w, i0, j0, rh, rw, range_mode, lo, hi, p_lo, p_hi, flags, out, ranges_out
+_SIGS_DISPLAY = {
+    "tsdr_display_u8_d": (C.c_int, [vp] + _DISP),
+    "tsdr_display_u8": (C.c_int, [vp] + _DISP),
+}
+RANGE_FIXED, RANGE_MINMAX, RANGE_PERCENTILE = 0, 1, 2  # TSDR_RANGE_*
+DISPLAY_INVERT, DISPLAY_SHARED = 1, 2  # TSDR_DISPLAY_* flags
+DISPLAY_BINS = 4096
+
 
 def exported_names():
     """Every symbol include/tempest_hip.h declares (kept in sync by tests/test_abi.py)."""
@@ -262,6 +273,11 @@ def exported_names_hires():
 def exported_names_register():
     """Every symbol include/tempest_hip_register.h declares (kept in sync by tests/test_register_host.py)."""
     return sorted(_SIGS_REGISTER)
+
+
+def exported_names_display():
+    """Every symbol include/tempest_hip_display.h declares (kept in sync by tests/test_display_host.py)."""
+    return sorted(_SIGS_DISPLAY)
 
 
 def _share_torch_hip_runtime():
@@ -290,7 +306,7 @@ def load():
             "(there is no CPU fallback)")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(_SIGS.items()) + list(_SIGS_IQ.items()) + list(_SIGS_CPLX.items()) + list(_SIGS_HIRES.items()) + \
-            list(_SIGS_REGISTER.items()):
+            list(_SIGS_REGISTER.items()) + list(_SIGS_DISPLAY.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI is incomplete
         fn.restype = res
         fn.argtypes = args

@@ -610,6 +610,17 @@ class Context:
         """(n, 2) int32: the raster-unit shifts the most recent frames_hires call averaged its rasters with (synchronises)"""
         return register.hires_shifts(self, max_frames)
 
+    # -- display export of any of those pictures (include/tempest_hip_display.h; display.py) ----------------------
+    def display_u8(self, images, roi=None, mode="minmax", lo=0.0, hi=1.0, p=(0.01, 0.99), invert=False, shared=False):
+        """-> (bytes (n, rh, rw) uint8, ranges (n, 2) float32): the ROI (i0, j0, rh, rw; None: everything) of n pictures (h, w)
+        mapped to 0 .. 255 over a "fixed" range (lo, hi), the ROI's finite "minmax", or its "percentile" fractions p"""
+        return display.display_u8(self, images, roi, mode, lo, hi, p, invert, shared)
+
+    def display_u8_d(self, images, n_images, h, w, out, roi=None, mode="minmax", lo=0.0, hi=1.0, p=(0.01, 0.99), invert=False,
+                     shared=False, ranges_out=None):
+        """device-pointer form of display_u8: enqueues on the context's stream and returns"""
+        return display.display_u8_d(self, images, n_images, h, w, out, roi, mode, lo, hi, p, invert, shared, ranges_out)
+
 
 def frames_d(ctx, sync, iq, nEch, S, y_t, x_t, alpha, do_align, state, frames_out=None, raster_out=None, sync_idx=None):
     """Device-pointer form of Context.frames: every array argument is a device buffer (torch tensor
@@ -683,6 +694,8 @@ from . import autocorr_cplx  # noqa: E402
 from . import hires  # noqa: E402
 # their registration to the raster pixel (the entry points of include/tempest_hip_register.h): register.py
 from . import register  # noqa: E402
+# the display export of any picture (the entry points of include/tempest_hip_display.h): display.py
+from . import display  # noqa: E402
 
 
 def frames_iq_d(ctx, sync, iq, fmt, scale, nEch, S, y_t, x_t, alpha, do_align, state, frames_out=None, raster_out=None, sync_idx=None,

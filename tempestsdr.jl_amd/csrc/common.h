@@ -34,6 +34,7 @@ enum Slot {
   WS_F64_B,       // call never moves a workspace the f32 paths hold
   WS_F64_C,
   WS_IQX,         // integer IQ expanded to ComplexF32 for the transform routes without a loader hook (tsdr_*_iq_d)
+  WS_DISPLAY,     // display.hip: per group the finite minimum / maximum / count, the range, and the 4096 histogram counters
   WS_HIRES,       // tsdr_frames_hires_iq_d: the rasters of one chunk of frames (raster_accum.hip)
   WS_HIRES_IDX,   // ... and the buffer's sync indices when the caller passes none
   WS_HIRES_SHIFTS,  // ... and the raster-unit shifts its frames were averaged with (tsdr_frames_hires_shifts)
@@ -92,6 +93,7 @@ struct tsdr_ctx {
   int opt_hires_refine = 0;       // tsdr_frames_hires_iq_d: 0..8, the registration's search radius in cells of the 600x800 sync grid (0: off;
                                   // include/tempest_hip_register.h)
   int hires_shifts_n = 0;         // frames of the most recent tsdr_frames_hires_iq_d whose applied shifts WS_HIRES_SHIFTS holds
+  int opt_display_hist_agg = 0;   // tsdr_display_u8*: 1 = a wave whose lanes all hold one histogram bin adds their number once (display.hip; A/B)
   int opt_fast_walk_only = 0;   // 1: the raster-free FAST frame path runs the raster walk with out == null (round 2's route; A/B)
   int opt_down_spp_max_pct = 200; // raster-free FAST route: k_down_fused up to this many samples per raster pixel (percent), the raster walk above
                                   // (round 4: 50 -> 200 once wide rows stage with 16 loads in flight: C3 0.40 -> 0.24 ms per buffer)

@@ -299,6 +299,7 @@ int tsdr_set_option(tsdr_ctx *ctx, const char *name, int value) {
     if (value < 0 || value > 8) return tsdr::set_err(ctx, TSDR_EINVAL, "hires_refine must be in [0, 8]");
     ctx->opt_hires_refine = value;
   }
+  else if (!strcmp(name, "display_hist_agg")) ctx->opt_display_hist_agg = value != 0;
   else if (!strcmp(name, "down_xcd")) ctx->opt_down_xcd = value != 0;
   else if (!strcmp(name, "down_spp_max_pct")) ctx->opt_down_spp_max_pct = value < 0 ? 0 : value;
   else if (!strcmp(name, "raster_split")) ctx->opt_raster_split = value < 0 || value > 2 ? 0 : value;

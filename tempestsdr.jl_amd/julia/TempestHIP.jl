@@ -718,5 +718,7 @@ include("TempestHIP_cplx.jl")
 include("TempestHIP_hires.jl")
 # registration of those rasters to the raster pixel: hip_raster_register!, hip_hires_refine! (include/tempest_hip_register.h)
 include("TempestHIP_register.jl")
+# display export of any of those pictures: hip_display_u8!, hip_display_u8_d! (include/tempest_hip_display.h)
+include("TempestHIP_display.jl")
 
 end # module
