@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/tempest_hip.h"
+#include "loop_policy.h"
 
 namespace tsdr {
 
@@ -72,6 +73,32 @@ struct BluesteinPlan {
   float2 *bfft = nullptr;   // FFT_L of the wrapped conj chirp
 };
 
+// The frame loop pipelined across buffers (tsdr_frames_submit_d, frames.hip): successive buffers on internal HIP streams so that
+// the latency-bound tail of one (vsync statistics, sync guard, shift + IIR) runs beside the image launch of the next.  WHICH
+// streams, and in which arrangement, is the tuner's business (loop_policy.h); this is what of the pipeline needs HIP.
+struct Pipeline {
+  hipStream_t pool[kPoolN + kPoolH] = {};  // created at the first submission (frames.hip:pipe_init)
+  hipStream_t lane[4] = {};         // the streams of the arrangement in use (members of pool): [0], [1], [3] equal lanes / [0] image lane, [2] tail lane
+  hipEvent_t ev_img[kPipeSlots] = {}, ev_tail[kPipeSlots] = {};  // recorded behind a slot's image launch / its shift + IIR
+  bool ev_tail_used[kPipeSlots] = {};
+  hipEvent_t lane_in = nullptr;     // "inputs ready" point of the context's stream
+  hipEvent_t tune_ev[kTrial] = {};  // timing events of a trial (two are recorded: PipeTuner::submitted)
+  unsigned long long n = 0;         // submissions since the last flush point
+  unsigned long long seq = 0;       // submissions since the lanes were last run empty (slot = seq % kPipeSlots)
+  PipeKey key;                      // what the slot offsets of the submissions in flight were computed from
+  int last_slot = -1;               // slot of the latest submission: its tail is behind everything submitted
+  int cand_now = -1;                // arrangement (index into kCands) of the submissions in flight
+  bool one_lane = false;            // ... is the one-stream arrangement (no event per buffer; pipe_drain records one when asked)
+  PipeTuner tuner;
+  void release() {                  // tsdr_destroy, with every lane idle
+    for (auto &l : pool) if (l) (void)hipStreamDestroy(l);
+    for (auto &e : tune_ev) if (e) (void)hipEventDestroy(e);
+    for (auto &e : ev_img) if (e) (void)hipEventDestroy(e);
+    for (auto &e : ev_tail) if (e) (void)hipEventDestroy(e);
+    if (lane_in) (void)hipEventDestroy(lane_in);
+  }
+};
+
 }  // namespace tsdr
 
 struct tsdr_ctx {
@@ -108,23 +135,18 @@ struct tsdr_ctx {
   float guard_thr = 2e-5f;
   unsigned *guard_sync[4] = {};             // work-queue words of the guard kernel (zero between launches), one set per pipeline lane
   unsigned long long *guard_stats = nullptr;
-  // adaptive route (option "sync_guard_auto"): when more than guard_auto_hi of the recent frames were flagged, re-evaluating
-  // them one by one costs more than running whole buffers in the exact sequence, so the FAST frame loop does that until the
-  // share (still counted, on the exact statistics) falls below guard_auto_lo.  Decided on the host, DETERMINISTICALLY (round 5):
+  // adaptive route (option "sync_guard_auto", loop_policy.h:GuardRoute).  Decided on the host, DETERMINISTICALLY (round 5):
   // every guarded call's guard launch writes ITS OWN {frames, flagged} into a pinned ring entry tagged with the call's
   // sequence number; the decision for call k folds the entries of calls <= k - kGuardLag, in submission order, waiting for
   // them if need be (call k - 3 is long complete in any steady state: it is the pipeline's own slot-reuse distance).  The same
   // sequence of buffers therefore takes the same route on every run, whatever the host / GPU timing.
   int opt_guard_auto = 1;
-  float guard_auto_hi = 0.15f, guard_auto_lo = 0.05f;
+  tsdr::GuardRoute guard;
   int opt_guard_nowait = 0;                  // measurement switch (TSDR_GUARD_NOWAIT): the decision never waits for an entry
   static constexpr int kGuardRing = 16, kGuardLag = 3;
-  unsigned long long *guard_ring = nullptr;  // pinned: tag (seq + 1, 16 bits) << 48 | frames << 24 | flagged
+  unsigned long long *guard_ring = nullptr;  // pinned: GuardRoute::decode
   unsigned long long guard_seq = 0;          // guarded calls issued so far (the next one's sequence number)
   unsigned long long guard_consumed = 0;     // entries folded into the window so far
-  unsigned guard_win_c = 0, guard_win_f = 0; // frames checked / flagged since the last decision
-  bool guard_exact_now = false;
-  unsigned long long guard_auto_buffers = 0, guard_auto_switches = 0;
   int guard_last_dark = 0;                  // polarity ("vsync_blank_dark") of those records
   size_t guard_last_off = (size_t)-1;       // byte offset inside WS_GUARD of the most recent guarded call's top-2 records (tsdr_sync_guard_margins)
   int guard_last_frames = 0, guard_last_nbx = 0, guard_last_nby = 0;
@@ -150,41 +172,7 @@ struct tsdr_ctx {
   int amax_slot = 0;
   bool amax_dirty = false;   // a fused findmax may have left keys in the slot words (autocorr.hip:amax_begin clears them)
   unsigned long long amax_seq = 0;
-  // frame loop pipelined across buffers (tsdr_frames_submit_d, frames.hip): successive buffers on internal HIP streams so that
-  // the latency-bound tail of one (vsync statistics, sync guard, shift + IIR) runs beside the image launch of the next.
-  // WHICH streams, and in which arrangement, is measured, not assumed (frames.hip:pipe_pick): how well two HIP streams of a
-  // process overlap depends on the hardware queues they were mapped to, i.e. on what else the process created before.
-  static constexpr int kPipeSlots = 3;   // image / key / projection / guard-record slots in rotation
-  static constexpr int kPoolN = 6, kPoolH = 2;   // candidate streams: normal priority / highest priority
-  static constexpr int kTuneCands = 8, kTrial = 15;
-  unsigned long long pipe_n = 0;    // submissions since the last flush point
-  unsigned long long pipe_seq = 0;  // submissions since the lanes were last run empty (slot = pipe_seq % kPipeSlots)
-  // what the slot offsets of the submissions in flight were computed from: frames per buffer (the image slots are that many
-  // frames apart), the tile plan of (S, y_t, x_t, raster or not, precision) for the projection sums, the SyncXY object's block
-  // counts for the guard records.  A change of any of them runs the pipeline empty first.
-  struct PipeKey {
-    size_t nb = 0, S = 0; int y_t = 0, x_t = 0, raster = -1, prec = -1, align = -1, iq_kind = 0; const void *sync = nullptr;
-    bool operator==(const PipeKey &o) const {
-      return nb == o.nb && S == o.S && y_t == o.y_t && x_t == o.x_t && raster == o.raster && prec == o.prec && align == o.align && iq_kind == o.iq_kind && sync == o.sync;
-    }
-    // the same loop at a slightly different geometry (GUI.jl:492-506: the interactive y_t / x_t corrections move one line at a
-    // time): same frames per buffer, raster or not, precision, alignment, input format; S and the raster size within 10 %.
-    // What was measured for one holds for the other (the launches have the same shapes and durations within a few percent).
-    bool near(const PipeKey &o) const {
-      if (!(nb == o.nb && raster == o.raster && prec == o.prec && align == o.align && iq_kind == o.iq_kind)) return false;
-      const double s = (double)S / (double)(o.S ? o.S : 1), p = ((double)y_t * x_t) / ((double)o.y_t * o.x_t > 0 ? (double)o.y_t * o.x_t : 1.0);
-      return s > 0.9 && s < 1.1 && p > 0.9 && p < 1.1;
-    }
-  } pipe_key;
-  hipStream_t pool[kPoolN + kPoolH] = {};  // created at the first submission (frames.hip:pipe_init)
-  hipStream_t lane[4] = {};         // the streams of the arrangement in use (members of pool): [0], [1], [3] equal lanes / [0] image lane, [2] tail lane
-  hipEvent_t ev_img[kPipeSlots] = {}, ev_tail[kPipeSlots] = {};  // recorded behind a slot's image launch / its shift + IIR
-  bool ev_tail_used[kPipeSlots] = {};
-  hipEvent_t lane_in = nullptr;     // "inputs ready" point of the context's stream
-  int pipe_last_slot = -1;          // slot of the latest submission: its tail is behind everything submitted
-  int pipe_cand_now = -1;           // arrangement (index into frames.hip:kCands) of the submissions in flight
-  bool pipe_one_lane = false;       // ... is the one-stream arrangement (no event per buffer; pipe_drain records one when asked)
-  int pipe_lane = 0;                // lane of the call being enqueued (per-lane guard queue words, workspace raster)
+  tsdr::Pipeline pipe;              // tsdr_frames_submit_d: the internal streams, their events, and the choice of arrangement
   int opt_pipe_mode = -1;           // -1: the measured choice; 0: image lane + tail lane; 1: whole buffers alternate between opt_pipe_lanes
                                     // equal lanes, only shift + IIR chained; 2: one internal stream (the sequential order)
   int opt_pipe_lanes = 2;           // equal lanes of the forced arrangement 1: 2 or 3
@@ -193,19 +181,7 @@ struct tsdr_ctx {
                                     // a marker packet of its own behind it (the event is an argument of sync.hip:shift_iir_d)
   int opt_pipe_dev_events = 1;      // the pipeline's hand-over events release to device scope (TSDR_PIPE_DEV_EVENTS=0: the default system scope; A/B)
   int opt_pipe_tune = 1;            // 0: "pipe_mode" -1 means arrangement 0 with rasters, 1 without (rounds 1-4), nothing is measured
-  struct PipeTune {                 // the measured choice for one PipeKey
-    PipeKey key; int state = 0;     // 0: nothing measured; 1: trials running; 2: settled
-    int cand = 0, pos = 0, chosen = -1, round = 0;   // round 0: warm-up trial of candidate 0; 1, 2: the two measured passes
-    int interrupts = 0;             // times another configuration cut into this one's trials (4: settle on the sequential order)
-    bool inherited = false;         // settled by taking over a neighbouring configuration's choice (PipeKey::near), not by trials
-    float ms[kTuneCands] = {};      // mean interval between the tails of successive buffers, per arrangement
-  } tune;
-  int opt_pipe_pin = -1;            // "pipe_pin" k >= 0: arrangement k of frames.hip:kCands, nothing measured; -1: not pinned
-  bool tune_force = false;          // "pipe_measure" 1: the next configuration is measured whatever is known about it or its neighbours
-  unsigned long long tune_runs = 0; // measurements (full sets of trials) started on this context so far
-  std::vector<PipeTune> tune_done;  // settled measurements of earlier configurations (a caller that goes back to one -- GUI.jl's
-                                    // y_t / x_t corrections, a raster asked for now and then -- does not measure it again); <= 16
-  hipEvent_t tune_ev[kTrial] = {};
+  int opt_pipe_pin = -1;            // "pipe_pin" k >= 0: arrangement k of loop_policy.h:kCands, nothing measured; -1: not pinned
   // Every host-side wait of this library is bounded (round 6): a stream that does not complete within opt_wait_ms returns
   // TSDR_EHIP with the waiting stage in tsdr_last_error instead of holding the caller's thread (a GUI task inside a ccall) for
   // good.  0: unbounded (plain hipStreamSynchronize).  Option "wait_ms" / TSDR_WAIT_MS.
@@ -230,6 +206,9 @@ int lds_opt_in(tsdr_ctx *ctx, const void *fn, size_t bytes);
 // frames.hip: order the context's stream behind every buffer submitted to the pipeline (tsdr_frames_submit_d)
 int pipe_drain(tsdr_ctx *ctx);
 int pipe_sync_lanes(tsdr_ctx *ctx);    // bounded host-side wait for the pipeline's internal streams (TSDR_EHIP when one is stuck)
+static inline PipeOpts pipe_opts(const tsdr_ctx *c) {
+  return PipeOpts{c->opt_pipe_mode, c->opt_pipe_lanes, c->opt_pipe_priority, c->opt_pipe_tune, c->opt_pipe_pin};
+}
 // bounded host-side waits (ctx.hip): poll a marker event, first spinning, then in short sleeps; TSDR_EHIP + message after
 // ctx->opt_wait_ms.  `what` names the stage for tsdr_last_error.
 int wait_stream(tsdr_ctx *ctx, hipStream_t s, const char *what);

@@ -206,7 +206,7 @@ tsdr_ctx *tsdr_create(int device) {
   if (const char *e = getenv("TSDR_GUARD_NOWAIT")) ctx->opt_guard_nowait = atoi(e) != 0;
   if (const char *e = getenv("TSDR_PIPE_DEV_EVENTS")) ctx->opt_pipe_dev_events = atoi(e) != 0;
   if (const char *e = getenv("TSDR_PIPE_TUNE")) ctx->opt_pipe_tune = atoi(e) != 0;
-  if (const char *e = getenv("TSDR_PIPE_PIN")) ctx->opt_pipe_pin = atoi(e) < 0 || atoi(e) >= tsdr_ctx::kTuneCands ? -1 : atoi(e);
+  if (const char *e = getenv("TSDR_PIPE_PIN")) ctx->opt_pipe_pin = atoi(e) < 0 || atoi(e) >= tsdr::kTuneCands ? -1 : atoi(e);
   if (const char *e = getenv("TSDR_PIPE_EXT_EVENT")) ctx->opt_pipe_ext_event = atoi(e) != 0;
   if (const char *e = getenv("TSDR_PIPE_LANES")) ctx->opt_pipe_lanes = atoi(e) == 3 ? 3 : 2;
   if (const char *e = getenv("TSDR_WAIT_MS")) ctx->opt_wait_ms = atoi(e) < 0 ? 0 : atoi(e);
@@ -225,11 +225,7 @@ void tsdr_destroy(tsdr_ctx *ctx) {
     return;
   }
   if (ctx->wait_ev) (void)hipEventDestroy(ctx->wait_ev);
-  for (auto &l : ctx->pool) if (l) (void)hipStreamDestroy(l);
-  for (auto &e : ctx->tune_ev) if (e) (void)hipEventDestroy(e);
-  for (auto &e : ctx->ev_img) if (e) (void)hipEventDestroy(e);
-  for (auto &e : ctx->ev_tail) if (e) (void)hipEventDestroy(e);
-  if (ctx->lane_in) (void)hipEventDestroy(ctx->lane_in);
+  ctx->pipe.release();
   for (auto &b : ctx->ws) if (b.p) (void)hipFree(b.p);
   for (auto &r : ctx->prof) { (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1); }
   for (auto e : ctx->ev_pool) (void)hipEventDestroy(e);
@@ -310,38 +306,30 @@ int tsdr_set_option(tsdr_ctx *ctx, const char *name, int value) {
     ctx->opt_raster_v4 = value < 0 ? 0 : value;   // 0 (default): k_raster_fast; 32: k_raster_fast4, four wavefronts of 32 pixel columns per tile; other > 0: eight of 16
   }
   else if (!strcmp(name, "beta_waves")) ctx->opt_beta_waves = value == 8 ? 8 : 4;
-  else if (!strcmp(name, "pipe_mode") || !strcmp(name, "pipe_lanes") || !strcmp(name, "pipe_priority") || !strcmp(name, "pipe_tune")) {
-    int rc = tsdr::pipe_drain(ctx);   // (the next submission sees another arrangement and runs the lanes empty itself)
-    if (rc) return rc;
-    if (name[5] == 'm') ctx->opt_pipe_mode = value < 0 ? -1 : value > 2 ? 2 : value;
-    else if (name[5] == 'l') ctx->opt_pipe_lanes = value == 3 ? 3 : 2;
-    else if (name[5] == 'p') ctx->opt_pipe_priority = value != 0;
-    else { ctx->opt_pipe_tune = value != 0; ctx->tune = tsdr_ctx::PipeTune{}; ctx->tune_done.clear(); }   // (setting it also discards what was measured)
+  // the pipeline's options: submitted buffers keep the old setting (the next submission sees another arrangement and runs the
+  // lanes empty itself)
+  else if (!strcmp(name, "pipe_mode")) { if (int rc = tsdr::pipe_drain(ctx)) return rc; ctx->opt_pipe_mode = value < 0 ? -1 : value > 2 ? 2 : value; }
+  else if (!strcmp(name, "pipe_lanes")) { if (int rc = tsdr::pipe_drain(ctx)) return rc; ctx->opt_pipe_lanes = value == 3 ? 3 : 2; }
+  else if (!strcmp(name, "pipe_priority")) { if (int rc = tsdr::pipe_drain(ctx)) return rc; ctx->opt_pipe_priority = value != 0; }
+  else if (!strcmp(name, "pipe_tune")) { if (int rc = tsdr::pipe_drain(ctx)) return rc; ctx->opt_pipe_tune = value != 0; ctx->pipe.tuner.reset(); }
+  else if (!strcmp(name, "pipe_pin")) {   // the arrangement (index into the candidates tsdr_frames_pipeline_info lists); -1: back to the measured choice
+    if (int rc = tsdr::pipe_drain(ctx)) return rc;
+    if (value >= tsdr::kTuneCands) return tsdr::set_err(ctx, TSDR_EINVAL, "pipe_pin must be -1 .. %d", tsdr::kTuneCands - 1);
+    ctx->opt_pipe_pin = value < 0 ? -1 : value;
   }
-  else if (!strcmp(name, "pipe_pin") || !strcmp(name, "pipe_measure")) {
-    int rc = tsdr::pipe_drain(ctx);
-    if (rc) return rc;
-    if (name[5] == 'p') {   // the arrangement (index into the candidates tsdr_frames_pipeline_info lists), nothing measured; -1: back to the measured choice
-      if (value >= tsdr_ctx::kTuneCands) return tsdr::set_err(ctx, TSDR_EINVAL, "pipe_pin must be -1 .. %d", tsdr_ctx::kTuneCands - 1);
-      ctx->opt_pipe_pin = value < 0 ? -1 : value;
-    } else if (value) {     // measure (again) at the next submission: what is known about the current configuration is dropped
-      ctx->tune = tsdr_ctx::PipeTune{};
-      ctx->tune_force = true;
-    }
-  }
+  else if (!strcmp(name, "pipe_measure")) { if (int rc = tsdr::pipe_drain(ctx)) return rc; if (value) ctx->pipe.tuner.measure_now(); }
   else if (!strcmp(name, "pipe_ext_event")) ctx->opt_pipe_ext_event = value != 0;
   else if (!strcmp(name, "wait_ms")) ctx->opt_wait_ms = value < 0 ? 0 : value;
   else if (!strcmp(name, "sync_guard_ppb")) {
     if (value < 0 || value > 100000000) return tsdr::set_err(ctx, TSDR_EINVAL, "sync_guard_ppb must be in [0, 1e8]");
     ctx->guard_thr = (float)value * 1e-9f;
     // the adaptive route's history belongs to the old threshold: start over on the fast route
-    ctx->guard_exact_now = false;
+    ctx->guard.restart();
     ctx->guard_consumed = ctx->guard_seq;   // (the calls in flight were counted against the old threshold: never folded)
-    ctx->guard_win_c = ctx->guard_win_f = 0;
   }
   else if (!strcmp(name, "sync_guard_auto")) {
     ctx->opt_guard_auto = value != 0;
-    if (!value) ctx->guard_exact_now = false;
+    ctx->guard.set_auto(value != 0);
   }
   else return tsdr::set_err(ctx, TSDR_EINVAL, "unknown option '%s'", name);
   return TSDR_OK;
@@ -349,9 +337,9 @@ int tsdr_set_option(tsdr_ctx *ctx, const char *name, int value) {
 
 int tsdr_sync_guard_auto(tsdr_ctx *ctx, int *exact_now, unsigned long long *buffers_exact, unsigned long long *switches) {
   if (!ctx) return TSDR_EINVAL;
-  if (exact_now) *exact_now = ctx->guard_exact_now ? 1 : 0;
-  if (buffers_exact) *buffers_exact = ctx->guard_auto_buffers;
-  if (switches) *switches = ctx->guard_auto_switches;
+  if (exact_now) *exact_now = ctx->guard.exact_now ? 1 : 0;
+  if (buffers_exact) *buffers_exact = ctx->guard.buffers_exact;
+  if (switches) *switches = ctx->guard.switches;
   return TSDR_OK;
 }
 

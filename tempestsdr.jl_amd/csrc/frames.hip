@@ -24,12 +24,12 @@ namespace tsdr {
 // resample.hip: launch what image_plan.h:plan_images decided.  Where the plan says so (plan.sums.ncp != 0) the image kernel
 // also leaves the projection partial sums of every image in `proj` and clears the two argmax keys of every frame in `keys`.
 int launch_images(tsdr_ctx *ctx, const ImagePlan &plan, const float *in, float *raster, size_t raster_stride, float *down,
-                  size_t down_stride, float *proj, unsigned long long *keys);
+                  size_t down_stride, float *proj, unsigned long long *keys, int lane);
 int sync_scan_d(tsdr_sync *s, const float *img, size_t img_stride, int frames, unsigned long long *keys, float *proj,
                 const ProjLayout *have, uint2 *top2);
 void sync_beta_blocks(const tsdr_sync *s, int *nbx, int *nby);
 int sync_guard_d(tsdr_sync *s, const float *iq, IqFmt iqf, size_t S, int y_t, int x_t, int frames, float *img, size_t img_stride,
-                 unsigned long long *keys, float *proj, const GuardArgs &g, bool *can, bool plan_only);
+                 unsigned long long *keys, float *proj, const GuardArgs &g, bool *can, bool plan_only, int lane);
 int sync_workspace(tsdr_sync *s, int frames, int slot, int nslots, const ProjLayout *pl_in, float **proj,
                    unsigned long long **keys);
 int sync_use_lane(tsdr_sync *s, int lane);
@@ -70,8 +70,8 @@ struct GuardPlan {
 };
 
 // One buffer's work: what the caller asked for, and what job_prepare leaves for the launches.  The steps below take
-// everything from here -- the IQ format and the precision the buffer runs in included -- and nothing from mutable fields
-// of the context, except the stream their launches go to (launch_stream / pipe_lane: LaneScope).
+// everything from here -- the IQ format, the precision the buffer runs in and the lanes whose workspaces it uses included --
+// and nothing from mutable fields of the context, except the stream their launches go to (launch_stream: LaneScope).
 struct FrameJob {
   tsdr_ctx *ctx; tsdr_sync *sync;
   const float *iq; IqFmt fmt;
@@ -79,6 +79,8 @@ struct FrameJob {
   float *img; unsigned long long *keys;            // the buffer's 600x800 images and argmax keys (slot `slot`)
   float *raster_out, *state, *frames_out; int *sync_idx;
   int slot, nslots;                                // which part of the sync / guard workspaces this buffer uses
+  int lane_img, lane_tail;                         // Pipeline::lane index its image step / its tail runs on (0 outside the pipeline):
+                                                   // the fallback's workspace raster, the guard's queue words
   // job_prepare:
   int precision = TSDR_FAST;                       // the context's, or TSDR_EXACT for this buffer alone
   GuardPlan gp;
@@ -86,9 +88,8 @@ struct FrameJob {
   ImagePlan images;                                // what job_images will launch, and what that produces
 };
 
-// the adaptive route's decision (common.h): evaluated over windows of at least kGuardAutoWindow frames, from the per-call
-// counts of the calls up to `upto` (exclusive), folded in submission order
-constexpr unsigned kGuardAutoWindow = 60;
+// the adaptive route's decision (loop_policy.h:GuardRoute), from the ring entries of the calls up to `upto` (exclusive), folded
+// in submission order
 static void guard_auto_update(tsdr_ctx *ctx, unsigned long long upto) {
   if (!ctx->guard_ring) return;
   using clk = std::chrono::steady_clock;
@@ -111,7 +112,7 @@ static void guard_auto_update(tsdr_ctx *ctx, unsigned long long upto) {
     const auto bound = std::chrono::milliseconds(ctx->guard_late ? 2 : 50);
     for (unsigned it = 1; !seen; ++it) {
       w = __atomic_load_n(e, __ATOMIC_ACQUIRE);
-      seen = (w >> 48) == want;
+      seen = GuardRoute::decode(w).tag == want;
       if (seen) break;
       if (ctx->opt_guard_nowait) return;   // (measurement switch: fold what has arrived, never wait -- not reproducible)
       if ((it & 0x3FFu) != 0) continue;
@@ -120,23 +121,17 @@ static void guard_auto_update(tsdr_ctx *ctx, unsigned long long upto) {
       const bool over = now - t_start > bound;
       if (!over && now < t_look) continue;
       bool idle = !over && hipStreamQuery(ctx->stream) == hipSuccess;
-      if (!over) for (auto l : ctx->pool) if (l && idle) idle = hipStreamQuery(l) == hipSuccess;
+      if (!over) for (auto l : ctx->pipe.pool) if (l && idle) idle = hipStreamQuery(l) == hipSuccess;
       (void)hipGetLastError();
-      if (idle || over) { w = __atomic_load_n(e, __ATOMIC_ACQUIRE); seen = (w >> 48) == want; break; }
+      if (idle || over) { w = __atomic_load_n(e, __ATOMIC_ACQUIRE); seen = GuardRoute::decode(w).tag == want; break; }
       t_look = now + std::chrono::milliseconds(2);
     }
     ctx->guard_late = !seen;
     if (!seen) { ++ctx->guard_uncounted; continue; }
-    if (!ctx->opt_guard_auto) continue;
-    ctx->guard_win_c += (unsigned)((w >> 24) & 0xFFFFFFull);
-    ctx->guard_win_f += (unsigned)(w & 0xFFFFFFull);
-    if (ctx->guard_win_c < kGuardAutoWindow) continue;
-    const float share = (float)ctx->guard_win_f / (float)ctx->guard_win_c;
-    if (!ctx->guard_exact_now && share > ctx->guard_auto_hi) { ctx->guard_exact_now = true; ++ctx->guard_auto_switches; }
-    else if (ctx->guard_exact_now && share < ctx->guard_auto_lo) { ctx->guard_exact_now = false; ++ctx->guard_auto_switches; }
-    ctx->guard_win_c = ctx->guard_win_f = 0;
+    const GuardRoute::Entry en = GuardRoute::decode(w);
+    ctx->guard.fold(en.frames, en.flagged, ctx->opt_guard_auto != 0);
   }
-  if (!ctx->opt_guard_auto) ctx->guard_exact_now = false;
+  if (!ctx->opt_guard_auto) ctx->guard.set_auto(false);
 }
 
 // The guard's part of job_prepare.  This is where a buffer's precision is decided.
@@ -151,7 +146,7 @@ static int guard_plan(FrameJob &j) {
   GuardArgs g;
   g.nbx = nbx; g.nby = nby; g.thr = ctx->guard_thr;
   bool can = false;
-  int rc = sync_guard_d(j.sync, nullptr, j.fmt, j.S, j.y_t, j.x_t, F, nullptr, 0, nullptr, nullptr, g, &can, true);
+  int rc = sync_guard_d(j.sync, nullptr, j.fmt, j.S, j.y_t, j.x_t, F, nullptr, 0, nullptr, nullptr, g, &can, true, j.lane_tail);
   if (rc) return rc;
   if (!can) { j.precision = TSDR_EXACT; return TSDR_OK; }
   if (!ctx->guard_stats) {
@@ -162,10 +157,10 @@ static int guard_plan(FrameJob &j) {
   }
   // this call is guarded call number guard_seq: its route follows from the calls up to guard_seq - kGuardLag
   if (ctx->guard_seq >= (unsigned long long)tsdr_ctx::kGuardLag) guard_auto_update(ctx, ctx->guard_seq - tsdr_ctx::kGuardLag + 1);
-  if (ctx->opt_guard_auto && ctx->guard_exact_now) {  // this buffer: the exact sequence as a whole; flagged frames are only counted
+  if (ctx->opt_guard_auto && ctx->guard.exact_now) {  // this buffer: the exact sequence as a whole; flagged frames are only counted
     j.precision = TSDR_EXACT;
     g.count_only = 1;
-    ++ctx->guard_auto_buffers;
+    ++ctx->guard.buffers_exact;
   }
   const size_t per = ((size_t)F * 4 + 15) / 16 * 16 + (size_t)F * (size_t)(nbx + nby) * 8;
   char *w = (char *)ctx->scratch(WS_GUARD, (size_t)j.nslots * per);
@@ -217,14 +212,14 @@ static int job_prepare(FrameJob &j) {
 }
 
 static int job_images(FrameJob &j) {
-  return launch_images(j.ctx, j.images, j.iq, j.raster_out, (size_t)j.y_t * j.x_t, j.img, kNpx, j.proj, j.keys);
+  return launch_images(j.ctx, j.images, j.iq, j.raster_out, (size_t)j.y_t * j.x_t, j.img, kNpx, j.proj, j.keys, j.lane_img);
 }
 
 static int job_stats(FrameJob &j) {
   if (!j.do_align) return TSDR_OK;
   int rc = sync_scan_d(j.sync, j.img, kNpx, j.F, j.keys, j.proj, j.images.sums.ncp ? &j.images.sums : nullptr, j.gp.on ? j.gp.top2 : nullptr);
   if (rc || !j.gp.on) return rc;
-  return sync_guard_d(j.sync, j.iq, j.fmt, j.S, j.y_t, j.x_t, j.F, j.img, kNpx, j.keys, j.proj, j.gp.g, nullptr, false);
+  return sync_guard_d(j.sync, j.iq, j.fmt, j.S, j.y_t, j.x_t, j.F, j.img, kNpx, j.keys, j.proj, j.gp.g, nullptr, false, j.lane_tail);
 }
 
 static int job_combine(FrameJob &j, hipEvent_t done) {
@@ -251,7 +246,7 @@ static int frames_scan(tsdr_ctx *ctx, tsdr_sync *sync, const float *iq, IqFmt fm
   if (n_frames) *n_frames = (int)nb;
   if (nb == 0) return TSDR_OK;
   if (!img_out || (do_align && !keys_out)) return TSDR_EINVAL;
-  FrameJob j{ctx, sync, iq, fmt, S, y_t, x_t, (int)nb, do_align, 0.0f, img_out, keys_out, raster_out, nullptr, nullptr, nullptr, 0, 1};
+  FrameJob j{ctx, sync, iq, fmt, S, y_t, x_t, (int)nb, do_align, 0.0f, img_out, keys_out, raster_out, nullptr, nullptr, nullptr, 0, 1, 0, 0};
   rc = job_prepare(j);
   if (!rc) rc = job_images(j);
   if (!rc) rc = job_stats(j);
@@ -294,7 +289,7 @@ static int frames_run(tsdr_ctx *ctx, tsdr_sync *sync, const float *iq, IqFmt fmt
   TSDR_PTR_ALIGNED(ctx, "frames", sync_idx, 4);
   const size_t nb = nEch / S;
   if (nb > (size_t)1 << 20) return set_err(ctx, TSDR_EINVAL, "too many frames in one buffer");
-  if (ctx->pipe_n) {  // buffers submitted through the pipeline come first (SyncXY and imageOut state are sequential)
+  if (ctx->pipe.n) {  // buffers submitted through the pipeline come first (SyncXY and imageOut state are sequential)
     int rcd = pipe_drain(ctx);
     if (rcd) return rcd;
   }
@@ -337,15 +332,8 @@ int tsdr_frames_d(tsdr_ctx *ctx, tsdr_sync *sync, const float *iq, size_t nEch, 
 //    Whole buffers rotate over nl equal lanes; only shift + IIR waits, through an event, for the previous buffer's on another
 //    lane.  beta matrices, guard queue words and workspaces exist per lane.  nl = 1 is the sequential order.
 //
-// WHICH arrangement on WHICH streams is measured (round 5).  Rounds 3-4 chose by geometry -- A on a high-priority tail stream
-// with rasters (+6-8 % on the builder's boxes), B without (+13 %) -- and the driver's box then measured A 2 % BELOW one call
-// per buffer.  The cause is not the box: how two streams of a process overlap depends on the hardware queues HIP mapped them
-// to, i.e. on how many streams the process had created before (tools/r05_queue_probe.sh: the same code with 5 idle streams
-// created first runs A at 0.269 instead of 0.151 ms per buffer, with 1 runs B at 0.095 instead of 0.076).  So, like the
-// reference's own FFTW.PATIENT plans (Resampler.jl:31,39), the pipeline measures: the first submissions of a configuration
-// run kTrial buffers through each candidate of kCands -- results are identical in every arrangement -- timing the interval
-// between the tails of successive buffers with HIP events, then settle on the fastest (the sequential order among them, so a
-// process in which nothing overlaps falls back to it by itself).  tsdr_frames_pipeline_info reports the measurements.
+// WHICH arrangement on WHICH streams is measured, not assumed: loop_policy.h (PipeTuner, the candidates kCands);
+// tsdr_frames_pipeline_info reports the measurements.
 //
 // The caller's inputs are ordered through the context's stream: a submission waits for whatever that stream holds at
 // the time of the call (nothing when it is idle, the steady state), and tsdr_frames_flush orders the context's stream
@@ -355,38 +343,25 @@ int tsdr_frames_d(tsdr_ctx *ctx, tsdr_sync *sync, const float *iq, size_t nEch, 
 }  // extern "C"
 
 namespace tsdr {
-struct PipeCand { const char *name; int sym, nl, s[3]; };
-// sym: whole buffers rotate over nl equal lanes pool[s[0 .. nl)]; !sym: image lane pool[s[0]], tail lane pool[s[1]].
-// pool[0 .. kPoolN) are normal-priority streams, pool[kPoolN ..) streams of the highest priority.
-static const PipeCand kCands[tsdr_ctx::kTuneCands] = {
-    {"one stream (sequential order)", 1, 1, {0, 0, 0}},
-    {"image lane + high-priority tail lane", 0, 2, {0, tsdr_ctx::kPoolN, 0}},
-    {"image lane + tail lane", 0, 2, {2, 3, 0}},
-    {"image lane + high-priority tail lane (other streams)", 0, 2, {4, tsdr_ctx::kPoolN + 1, 0}},
-    {"two equal lanes", 1, 2, {0, 1, 0}},
-    {"two equal lanes (other streams)", 1, 2, {2, 3, 0}},
-    {"two equal lanes (third pair)", 1, 2, {4, 5, 0}},
-    {"three equal lanes", 1, 3, {0, 1, 2}},
-};
-
 static int pipe_init(tsdr_ctx *ctx) {
-  if (ctx->lane_in) return TSDR_OK;
+  Pipeline &P = ctx->pipe;
+  if (P.lane_in) return TSDR_OK;
   // (hand-overs between streams of ONE device: a device-scope release when the event is recorded, not the default system-scope
   // one, whose cache write-back holds up the lane behind every buffer; the host sees results through the context's stream, whose
   // synchronisation fences as always)
   const unsigned evf = hipEventDisableTiming | (ctx->opt_pipe_dev_events ? hipEventReleaseToDevice : 0u);
-  for (int k = 0; k < tsdr_ctx::kPipeSlots; ++k) {
-    TSDR_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_img[k], evf));
-    TSDR_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_tail[k], evf));
+  for (int k = 0; k < kPipeSlots; ++k) {
+    TSDR_HIP(ctx, hipEventCreateWithFlags(&P.ev_img[k], evf));
+    TSDR_HIP(ctx, hipEventCreateWithFlags(&P.ev_tail[k], evf));
   }
-  for (auto &e : ctx->tune_ev) TSDR_HIP(ctx, hipEventCreate(&e));
+  for (auto &e : P.tune_ev) TSDR_HIP(ctx, hipEventCreate(&e));
   int lo = 0, hi = 0;
   TSDR_HIP(ctx, hipDeviceGetStreamPriorityRange(&lo, &hi));   // (numerically: hi <= lo)
-  for (int i = 0; i < tsdr_ctx::kPoolN + tsdr_ctx::kPoolH; ++i) {
-    if (i < tsdr_ctx::kPoolN) TSDR_HIP(ctx, hipStreamCreateWithFlags(&ctx->pool[i], hipStreamNonBlocking));
-    else TSDR_HIP(ctx, hipStreamCreateWithPriority(&ctx->pool[i], hipStreamNonBlocking, hi));
+  for (int i = 0; i < kPoolN + kPoolH; ++i) {
+    if (i < kPoolN) TSDR_HIP(ctx, hipStreamCreateWithFlags(&P.pool[i], hipStreamNonBlocking));
+    else TSDR_HIP(ctx, hipStreamCreateWithPriority(&P.pool[i], hipStreamNonBlocking, hi));
   }
-  TSDR_HIP(ctx, hipEventCreateWithFlags(&ctx->lane_in, hipEventDisableTiming));
+  TSDR_HIP(ctx, hipEventCreateWithFlags(&P.lane_in, hipEventDisableTiming));
   return TSDR_OK;
 }
 
@@ -394,94 +369,32 @@ static int pipe_init(tsdr_ctx *ctx) {
 // synchronises, retargets or destroys the context, or that touches a SyncXY state / the IIR state outside the pipeline,
 // calls this first.
 int pipe_drain(tsdr_ctx *ctx) {
-  if (!ctx || ctx->pipe_n == 0) return TSDR_OK;
+  if (!ctx || ctx->pipe.n == 0) return TSDR_OK;
+  Pipeline &P = ctx->pipe;
   // the tails run in submission order (stream order or chained by events): the latest one is behind everything else
-  if (ctx->pipe_last_slot >= 0) {
+  if (P.last_slot >= 0) {
     // (the one-stream arrangement records no event per buffer -- nothing but this point ever waits for it -- so that it costs
     // exactly what one tsdr_frames_d per buffer costs: the event is recorded here, behind everything on its lane)
-    if (ctx->pipe_one_lane) TSDR_HIP(ctx, hipEventRecord(ctx->ev_tail[ctx->pipe_last_slot], ctx->lane[0]));
-    TSDR_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_tail[ctx->pipe_last_slot], 0));
+    if (P.one_lane) TSDR_HIP(ctx, hipEventRecord(P.ev_tail[P.last_slot], P.lane[0]));
+    TSDR_HIP(ctx, hipStreamWaitEvent(ctx->stream, P.ev_tail[P.last_slot], 0));
   }
-  ctx->pipe_n = 0;
+  P.n = 0;
   return TSDR_OK;
 }
 
 // host-side wait for the lanes (workspace reallocation, destruction, a change of arrangement)
 int pipe_sync_lanes(tsdr_ctx *ctx) {
-  for (auto l : ctx->pool) if (l) { int rc = wait_stream(ctx, l, "pipeline lane"); if (rc) return rc; }
+  for (auto l : ctx->pipe.pool) if (l) { int rc = wait_stream(ctx, l, "pipeline lane"); if (rc) return rc; }
   return TSDR_OK;
 }
 
-// the arrangement of this submission: forced ("pipe_mode" >= 0), the geometry rule of rounds 3-4 ("pipe_tune" = 0), or the
-// measured one.  May run the pipeline empty (a trial boundary).  Returns an index into kCands, or a negative status.
-static int pipe_pick(tsdr_ctx *ctx, const tsdr_ctx::PipeKey &key) {
-  if (ctx->opt_pipe_pin >= 0) return ctx->opt_pipe_pin;
-  if (ctx->opt_pipe_mode == 0) return ctx->opt_pipe_priority ? 1 : 2;
-  if (ctx->opt_pipe_mode == 1) return ctx->opt_pipe_lanes == 3 ? 7 : 4;
-  if (ctx->opt_pipe_mode == 2) return 0;
-  if (!ctx->opt_pipe_tune) return key.raster ? 1 : 4;
-  tsdr_ctx::PipeTune &t = ctx->tune;
-  if (t.state == 0 || !(t.key == key)) {   // another configuration: one measured before, a neighbour of one, or measure now
-    // what is known about the previous one is kept -- settled or half-way through its trials (a caller that alternates between
-    // two configurations resumes each one's trials where it left them instead of starting over on every change); the table
-    // holds the 8 most recently used configurations
-    if (t.state != 0) {
-      if (ctx->tune_done.size() >= 8) ctx->tune_done.erase(ctx->tune_done.begin());
-      if (t.state == 1) {                    // (the trial that was interrupted is run again from its first buffer)
-        t.pos = 0;
-        // a caller that keeps cutting in (two configurations in strict alternation) would never settle and would run the lanes
-        // empty at every change: after four interruptions the configuration keeps the sequential order
-        if (++t.interrupts >= 4) { t.state = 2; t.chosen = 0; }
-      }
-      ctx->tune_done.push_back(t);
-    }
-    t = tsdr_ctx::PipeTune{};
-    bool found = false;
-    if (ctx->tune_force) {   // "measure now": what the table holds for this configuration goes, neighbours are not consulted
-      for (size_t i = ctx->tune_done.size(); i-- > 0;) if (ctx->tune_done[i].key == key) ctx->tune_done.erase(ctx->tune_done.begin() + (long)i);
-      ctx->tune_force = false;
-      t.key = key; t.state = 1; ++ctx->tune_runs;
-      found = true;
-    }
-    for (size_t i = 0; i < ctx->tune_done.size() && !found; ++i)
-      if (ctx->tune_done[i].key == key) { t = ctx->tune_done[i]; ctx->tune_done.erase(ctx->tune_done.begin() + (long)i); found = true; }
-    for (size_t i = ctx->tune_done.size(); i-- > 0 && !found;)   // (the most recent neighbour first)
-      if (ctx->tune_done[i].state == 2 && ctx->tune_done[i].key.near(key)) { t = ctx->tune_done[i]; t.key = key; t.inherited = true; found = true; }
-    if (!found) { t.key = key; t.state = 1; ++ctx->tune_runs; }
-  }
-  if (t.state == 1 && t.pos == tsdr_ctx::kTrial) {   // this arrangement's trial is complete
-    int rc = pipe_drain(ctx);
-    if (rc) return rc;
-    rc = pipe_sync_lanes(ctx);
-    if (rc) return rc;
-    // mean interval between the tails of successive buffers over a whole number of lane rotations (12 intervals: with two or
-    // three lanes the tails complete in bursts, so a median of single intervals says nothing), after 3 buffers of ramp-up
-    float ms = 0.f;
-    const bool okev = hipEventElapsedTime(&ms, ctx->tune_ev[2], ctx->tune_ev[tsdr_ctx::kTrial - 1]) == hipSuccess;
-    (void)hipGetLastError();
-    t.pos = 0;
-    if (t.round == 0) {
-      // the very first trial (the device's clocks and caches as the caller left them) only warms up: measured again, in turn
-      t.round = 1;
-    } else {
-      const float v = okev ? ms / (float)(tsdr_ctx::kTrial - 3) : 1e30f;
-      t.ms[t.cand] = t.round == 1 ? v : std::min(t.ms[t.cand], v);   // two passes over the candidates, the better of the two
-      if (++t.cand == tsdr_ctx::kTuneCands) {
-        t.cand = 0;
-        if (++t.round == 3) {
-          int best = 0;
-          for (int c = 1; c < tsdr_ctx::kTuneCands; ++c) if (t.ms[c] < t.ms[best]) best = c;
-          // the sequential order unless something beats it by more than the measurement's noise
-          t.chosen = t.ms[best] < 0.985f * t.ms[0] ? best : 0;
-          t.state = 2;
-        }
-      }
-    }
-  }
-  return t.state == 2 ? t.chosen : t.cand;
+// run the pipeline empty: a change of configuration or arrangement, a trial boundary of the measurement
+static int pipe_quiesce(tsdr_ctx *ctx) {
+  if (int rc = pipe_drain(ctx)) return rc;
+  return pipe_sync_lanes(ctx);
 }
 
-// A submission that fails half-way has launches on the lanes that no later drain would order (pipe_n is not advanced):
+// A submission that fails half-way has launches on the lanes that no later drain would order (Pipeline::n is not advanced):
 // the error path waits for the lanes on the host, so that the state handed back is quiescent.
 struct SubmitGuard {
   tsdr_ctx *ctx; bool ok = false;
@@ -491,8 +404,8 @@ struct SubmitGuard {
 
 struct LaneScope {  // launches of this scope go to a lane: the one piece of ambient state the steps read (TSDR_LAUNCH)
   tsdr_ctx *ctx; hipStream_t saved;
-  LaneScope(tsdr_ctx *c, int lane) : ctx(c), saved(c->launch_stream) { c->launch_stream = c->lane[lane]; c->pipe_lane = lane; }
-  ~LaneScope() { ctx->launch_stream = saved; ctx->pipe_lane = 0; }
+  LaneScope(tsdr_ctx *c, int lane) : ctx(c), saved(c->launch_stream) { c->launch_stream = c->pipe.lane[lane]; }
+  ~LaneScope() { ctx->launch_stream = saved; }
 };
 
 // The caller's inputs: whatever the context's stream holds now (uploads, a producer's kernels, an earlier call's launches)
@@ -500,8 +413,8 @@ struct LaneScope {  // launches of this scope go to a lane: the one piece of amb
 static int fence_inputs(tsdr_ctx *ctx, hipStream_t lane) {
   if (hipStreamQuery(ctx->stream) == hipSuccess) return TSDR_OK;
   (void)hipGetLastError();  // (hipErrorNotReady is a status here, not a failure for the next launch check to find)
-  TSDR_HIP(ctx, hipEventRecord(ctx->lane_in, ctx->stream));
-  TSDR_HIP(ctx, hipStreamWaitEvent(lane, ctx->lane_in, 0));
+  TSDR_HIP(ctx, hipEventRecord(ctx->pipe.lane_in, ctx->stream));
+  TSDR_HIP(ctx, hipStreamWaitEvent(lane, ctx->pipe.lane_in, 0));
   return TSDR_OK;
 }
 }  // namespace tsdr
@@ -524,14 +437,24 @@ static int frames_submit(tsdr_ctx *ctx, tsdr_sync *sync, const float *iq, IqFmt 
   if (nb > (size_t)1 << 20) return set_err(ctx, TSDR_EINVAL, "too many frames in one buffer");
   if (n_frames) *n_frames = (int)nb;
   if (nb == 0) return TSDR_OK;
-  constexpr int NS = tsdr_ctx::kPipeSlots;
+  constexpr int NS = kPipeSlots;
   rc = pipe_init(ctx);
   if (rc) return rc;
-  tsdr_ctx::PipeKey key;
+  Pipeline &P = ctx->pipe;
+  const PipeOpts opts = pipe_opts(ctx);
+  PipeKey key;
   key.nb = nb; key.S = S; key.y_t = y_t; key.x_t = x_t; key.raster = raster_out ? 1 : 0; key.prec = ctx->precision;
   key.align = do_align ? 1 : 0; key.sync = (const void *)sync; key.iq_kind = fmt.kind;
-  const int cand = pipe_pick(ctx, key);
-  if (cand < 0) return cand;
+  P.tuner.select(key, opts);
+  if (P.tuner.trial_complete()) {   // (a wait that fails leaves the trial complete: the next submission tries again)
+    rc = pipe_quiesce(ctx);
+    if (rc) return rc;
+    float ms = 0.f;
+    const bool okev = hipEventElapsedTime(&ms, P.tune_ev[2], P.tune_ev[kTrial - 1]) == hipSuccess;
+    (void)hipGetLastError();
+    P.tuner.record_trial(okev, ms);
+  }
+  const int cand = P.tuner.candidate();
   const PipeCand &pc = kCands[cand];
   const bool sym = pc.sym != 0;
   const int nl = pc.nl;
@@ -540,104 +463,83 @@ static int frames_submit(tsdr_ctx *ctx, tsdr_sync *sync, const float *iq, IqFmt 
   // these (GUI.jl's FLAG_CONFIG_UPDATE, its y_t / x_t corrections, a trial boundary of the measurement) would compute slot
   // offsets that overlap what an in-flight tail on another lane still reads -- the pipeline runs empty first (a
   // configuration change, not a steady-state event).
-  if (!(ctx->pipe_key == key) || ctx->pipe_cand_now != cand) {
-    rc = pipe_drain(ctx);
+  if (!(P.key == key) || P.cand_now != cand) {
+    rc = pipe_quiesce(ctx);
     if (rc) return rc;
-    rc = pipe_sync_lanes(ctx);
-    if (rc) return rc;
-    for (bool &u : ctx->ev_tail_used) u = false;
-    ctx->pipe_seq = 0;
-    ctx->pipe_last_slot = -1;
-    if (sym) { ctx->lane[0] = ctx->pool[pc.s[0]]; ctx->lane[1] = ctx->pool[pc.s[1]]; ctx->lane[3] = ctx->pool[pc.s[2]]; }
-    else { ctx->lane[0] = ctx->pool[pc.s[0]]; ctx->lane[2] = ctx->pool[pc.s[1]]; }
-    ctx->pipe_one_lane = sym && nl == 1;
+    for (bool &u : P.ev_tail_used) u = false;
+    P.seq = 0;
+    P.last_slot = -1;
+    if (sym) { P.lane[0] = P.pool[pc.s[0]]; P.lane[1] = P.pool[pc.s[1]]; P.lane[3] = P.pool[pc.s[2]]; }
+    else { P.lane[0] = P.pool[pc.s[0]]; P.lane[2] = P.pool[pc.s[1]]; }
+    P.one_lane = sym && nl == 1;
   }
-  ctx->pipe_key = key;
-  ctx->pipe_cand_now = cand;
+  P.key = key;
+  P.cand_now = cand;
   // symmetric: whole buffers alternate between nl equal lanes; slot = position in the rotation
-  const int slot = (int)(ctx->pipe_seq % (unsigned long long)(sym ? nl : NS));
+  const int slot = (int)(P.seq % (unsigned long long)(sym ? nl : NS));
+  // the lanes of the two steps: equal lanes [0], [1], [3] take a whole buffer; else image lane [0], tail lane [2]
+  const int lane_img = sym ? (slot == 2 ? 3 : slot) : 0, lane_tail = sym ? lane_img : 2;
   // (workspaces first: growing one synchronises and frees what the lanes may be using)
   float *img3 = (float *)ctx->scratch(WS_IMG, NS * nb * kNpx * 4);
   unsigned long long *keys3 = (unsigned long long *)ctx->scratch(WS_KEYS, NS * nb * 2 * 8);
   if (!img3 || !keys3) return TSDR_ENOMEM;
   FrameJob j{ctx, sync, iq, fmt, S, y_t, x_t, (int)nb, do_align, alpha, img3 + (size_t)slot * nb * kNpx, keys3 + (size_t)slot * nb * 2,
-             raster_out, imageOut_state, frames_out, sync_idx, slot, NS};
+             raster_out, imageOut_state, frames_out, sync_idx, slot, NS, lane_img, lane_tail};
   SubmitGuard submitted(ctx);
   rc = job_prepare(j);
   if (rc) return rc;
-  hipStream_t tail_stream = nullptr;
+  const hipStream_t tail_stream = P.lane[lane_tail];
   if (sym) {
-    // R(k) B(k) G(k) [shift + IIR of the previous buffer done] C(k), all on lane `slot`: a lane's next buffer is stream-ordered
+    // R(k) B(k) G(k) [shift + IIR of the previous buffer done] C(k), all on one lane: a lane's next buffer is stream-ordered
     // behind its previous one, and the only cross-lane dependency is the chain of shift + IIR launches (lagged s_y, IIR state)
-    const int li = slot == 2 ? 3 : slot;
-    LaneScope lane_scope(ctx, li);
-    tail_stream = ctx->lane[li];
+    LaneScope lane_scope(ctx, lane_img);
     rc = fence_inputs(ctx, tail_stream);
     if (!rc && do_align) rc = sync_use_lane(sync, slot);
     if (!rc) rc = job_images(j);
     if (!rc) rc = job_stats(j);
     if (rc) return rc;
-    if (ctx->pipe_last_slot >= 0 && ctx->pipe_last_slot != slot && ctx->ev_tail_used[ctx->pipe_last_slot])
-      TSDR_HIP(ctx, hipStreamWaitEvent(tail_stream, ctx->ev_tail[ctx->pipe_last_slot], 0));
-    rc = job_combine(j, nl > 1 ? ctx->ev_tail[slot] : nullptr);   // (one lane: no event per buffer, see pipe_drain)
+    if (P.last_slot >= 0 && P.last_slot != slot && P.ev_tail_used[P.last_slot])
+      TSDR_HIP(ctx, hipStreamWaitEvent(tail_stream, P.ev_tail[P.last_slot], 0));
+    rc = job_combine(j, nl > 1 ? P.ev_tail[slot] : nullptr);   // (one lane: no event per buffer, see pipe_drain)
     if (rc) return rc;
   } else {
-    tail_stream = ctx->lane[2];
     {
-      LaneScope image_lane(ctx, 0);
-      rc = fence_inputs(ctx, ctx->lane[0]);
+      LaneScope image_lane(ctx, lane_img);
+      rc = fence_inputs(ctx, P.lane[lane_img]);
       if (rc) return rc;
       // this slot's previous user: submission k - NS, whose tail read its images / keys / sums
-      if (ctx->ev_tail_used[slot]) TSDR_HIP(ctx, hipStreamWaitEvent(ctx->lane[0], ctx->ev_tail[slot], 0));
+      if (P.ev_tail_used[slot]) TSDR_HIP(ctx, hipStreamWaitEvent(P.lane[lane_img], P.ev_tail[slot], 0));
       if (do_align) rc = sync_use_lane(sync, 0);   // (one beta set serves: the statistics run in stream order on the tail lane)
       if (!rc) rc = job_images(j);
       if (rc) return rc;
-      TSDR_HIP(ctx, hipEventRecord(ctx->ev_img[slot], ctx->lane[0]));
+      TSDR_HIP(ctx, hipEventRecord(P.ev_img[slot], P.lane[lane_img]));
     }
     {
-      LaneScope tail_lane(ctx, 2);
-      TSDR_HIP(ctx, hipStreamWaitEvent(ctx->lane[2], ctx->ev_img[slot], 0));
+      LaneScope tail_lane(ctx, lane_tail);
+      TSDR_HIP(ctx, hipStreamWaitEvent(tail_stream, P.ev_img[slot], 0));
       rc = job_stats(j);
       // (shift + IIR on a third stream of its own: 348 k vs 357 k frames/s raster-free, 175 k vs 181 k with rasters -- dropped)
-      if (!rc) rc = job_combine(j, ctx->ev_tail[slot]);
+      if (!rc) rc = job_combine(j, P.ev_tail[slot]);
       if (rc) return rc;
     }
   }
-  if (ctx->opt_pipe_pin < 0 && ctx->opt_pipe_mode < 0 && ctx->opt_pipe_tune && ctx->tune.state == 1 && ctx->tune.pos < tsdr_ctx::kTrial) {
-    // two timing events per trial (a timed event is a marker packet that holds up the launches behind it for a few
-    // microseconds: one per buffer made the one-stream candidate look 10 % slower than it is)
-    if (ctx->tune.pos == 2 || ctx->tune.pos == tsdr_ctx::kTrial - 1) TSDR_HIP(ctx, hipEventRecord(ctx->tune_ev[ctx->tune.pos], tail_stream));
-    ++ctx->tune.pos;
-  }
-  ctx->ev_tail_used[slot] = true;
-  ctx->pipe_last_slot = slot;
-  ++ctx->pipe_seq;
-  ++ctx->pipe_n;
+  const int timed = P.tuner.submitted(opts);   // a trial's buffers 2 and kTrial - 1 carry a timing event behind their tails
+  if (timed >= 0) TSDR_HIP(ctx, hipEventRecord(P.tune_ev[timed], tail_stream));
+  P.ev_tail_used[slot] = true;
+  P.last_slot = slot;
+  ++P.seq;
+  ++P.n;
   submitted.ok = true;
   return TSDR_OK;
 }
 
 int tsdr_frames_pipeline_info(tsdr_ctx *ctx, int *trials_left, int *chosen, float *ms_per_buffer, int cap, char *text, size_t text_cap) {
   if (!ctx || cap < 0 || (cap && !ms_per_buffer)) return TSDR_EINVAL;
-  const tsdr_ctx::PipeTune &t = ctx->tune;
-  const bool measured = ctx->opt_pipe_mode < 0 && ctx->opt_pipe_tune && ctx->opt_pipe_pin < 0;
-  constexpr int kAll = 2 * tsdr_ctx::kTuneCands + 1;   // the warm-up trial + two passes
-  if (trials_left) *trials_left = !measured ? 0 : t.state == 2 ? 0 : t.state == 1 ? kAll - (t.round == 0 ? 0 : 1 + (t.round - 1) * tsdr_ctx::kTuneCands + t.cand) : kAll;
-  if (chosen) *chosen = measured ? (t.state == 2 ? t.chosen : -1) : ctx->pipe_cand_now;
-  for (int c = 0; c < cap && c < tsdr_ctx::kTuneCands; ++c) ms_per_buffer[c] = measured && (t.state == 2 || t.round == 2 || (t.round == 1 && c < t.cand)) ? t.ms[c] : 0.f;
-  if (text && text_cap) {
-    std::string s;
-    if (ctx->opt_pipe_pin >= 0) s = std::string("pinned (\"pipe_pin\"): ") + kCands[ctx->opt_pipe_pin].name;
-    else if (!measured) s = std::string("forced: ") + (ctx->pipe_cand_now >= 0 ? kCands[ctx->pipe_cand_now].name : "nothing submitted yet");
-    else if (t.state != 2) s = "measuring";
-    else {
-      s = std::string(t.inherited ? "taken over from a neighbouring configuration's measurement: " : "measured: ") + kCands[t.chosen].name + " |";
-      char b[96];
-      for (int c = 0; c < tsdr_ctx::kTuneCands; ++c) { snprintf(b, sizeof b, " [%d] %s %.4f ms;", c, kCands[c].name, (double)t.ms[c]); s += b; }
-    }
-    s += " (measurements started on this context: " + std::to_string(ctx->tune_runs) + ")";
-    snprintf(text, text_cap, "%s", s.c_str());
-  }
+  const PipeInfo r = ctx->pipe.tuner.info(pipe_opts(ctx), ctx->pipe.cand_now);
+  if (trials_left) *trials_left = r.trials_left;
+  if (chosen) *chosen = r.chosen;
+  for (int c = 0; c < cap && c < kTuneCands; ++c) ms_per_buffer[c] = r.ms[c];
+  if (text && text_cap) snprintf(text, text_cap, "%s", r.text.c_str());
   return TSDR_OK;
 }
 

@@ -1252,7 +1252,7 @@ static int launch_step(tsdr_ctx *ctx, const ImageStep &s, const StepPtrs &p, flo
 // Launch what plan_images decided.  proj / keys: room for the projection partial sums the plan says it forms (plan.sums) and the
 // frames' argmax keys, which the same kernel clears.
 int launch_images(tsdr_ctx *ctx, const ImagePlan &pl, const float *in, float *raster, size_t raster_stride, float *down,
-                  size_t down_stride, float *proj, unsigned long long *keys) {
+                  size_t down_stride, float *proj, unsigned long long *keys, int lane) {
   if (pl.status) return set_err(ctx, pl.status, "%s", pl.err);
   assert(!pl.sums.ncp || (proj && keys));   // a plan that forms projection sums is launched with room for them
   const int whole = pl.nsteps - (pl.fallback ? 2 : 0);
@@ -1268,7 +1268,7 @@ int launch_images(tsdr_ctx *ctx, const ImagePlan &pl, const float *in, float *ra
   const size_t P = (size_t)ds.rs[0] * (size_t)ds.rs[1];
   float *ras = (float *)ctx->scratch(WS_RASTER, pl.ws_raster);
   if (!ras) return TSDR_ENOMEM;
-  ras += (size_t)(ctx->pipe_lane & 3) * P;
+  ras += (size_t)(lane & 3) * P;
   for (int f = 0; f < pl.frames; ++f) {
     const float *in_f = rs.cplx ? iq_at(in, (size_t)f * pl.in_stride, iq_bytes(rs.q.iqf)) : in + (size_t)f * pl.in_stride;
     if (int rc = launch_step(ctx, rs, StepPtrs{in_f, pl.in_stride, ras, P, nullptr, 0}, nullptr, nullptr)) return rc;
@@ -1312,7 +1312,7 @@ int tsdr_sig_to_image_d(tsdr_ctx *ctx, const float *sig, size_t S, int y_t, int 
   TSDR_PTR_ALIGNED(ctx, "sig_to_image", img, 4);
   ImageReq r;
   r.cplx = 0; r.precision = TSDR_EXACT; r.S = r.in_stride = S; r.y_t = y_t; r.x_t = x_t; r.frames = 1; r.raster = true;
-  return launch_images(ctx, plan_images(plan_opts(ctx), r), sig, img, (size_t)y_t * x_t, nullptr, 0, nullptr, nullptr);
+  return launch_images(ctx, plan_images(plan_opts(ctx), r), sig, img, (size_t)y_t * x_t, nullptr, 0, nullptr, nullptr, 0);
 }
 
 int tsdr_resize2d_d(tsdr_ctx *ctx, const float *img, int h_in, int w_in, int h_out, int w_out, float *out) {

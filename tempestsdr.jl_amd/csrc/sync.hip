@@ -844,7 +844,7 @@ __global__ __launch_bounds__(512, 2) void k_guard(GuardAllArgs a) {
 bool guard_image_plan(tsdr_ctx *ctx, IqFmt iqf, size_t S, int y_t, int x_t, int h_out, int w_out, DownParams *q, size_t *lds);
 
 int sync_guard_d(tsdr_sync *s, const float *iq, IqFmt iqf, size_t S, int y_t, int x_t, int frames, float *img, size_t img_stride,
-                 unsigned long long *keys, float *proj, const GuardArgs &g, bool *can, bool plan_only) {
+                 unsigned long long *keys, float *proj, const GuardArgs &g, bool *can, bool plan_only, int lane) {
   tsdr_ctx *ctx = s->ctx;
   if (can) *can = false;
 #ifdef TSDR_ROWSUM_CHUNK8
@@ -869,7 +869,7 @@ int sync_guard_d(tsdr_sync *s, const float *iq, IqFmt iqf, size_t S, int y_t, in
     const int nf = std::min(kGuardChunk, frames - f0);
     // queue words: zero between launches (the kernel restores that itself)
     const size_t words = 2 + 2 * (size_t)kGuardChunk + 2;   // + the per-call accumulator of multi-launch calls (GuardArgs::acc)
-    unsigned *&qwords = ctx->guard_sync[ctx->pipe_lane & 3];   // (guard launches of different pipeline lanes may run side by side)
+    unsigned *&qwords = ctx->guard_sync[lane & 3];   // (guard launches of different pipeline lanes may run side by side)
     if (!qwords) {
       TSDR_HIP(ctx, hipMalloc((void **)&qwords, words * 4));
       TSDR_HIP(ctx, hipMemsetAsync(qwords, 0, words * 4, ctx->launch_stream));

@@ -489,21 +489,23 @@ def test_submit_with_changing_raster_geometry(ctx, tsdr, synth, want_raster, pre
         ctx.set_option("sync_guard_auto", 1)
 
 
-@pytest.mark.parametrize("mode", [1, 0])
+@pytest.mark.parametrize("mode", [1, 0, "pin7"])
 def test_pipeline_on_a_geometry_without_fused_kernels(ctx, tsdr, mode):
     """A raster no image kernel tiles (30000 lines of 200 pixels in TSDR_EXACT: 3000 source lines per 64 output rows do not
     fit the staging budget, and the narrow raster rules out the in-walk downgrade) goes through the raster-in-workspace +
     2-D resize fallback, frame by frame.  Two pipelined submissions may run that loop side by side on two lanes: each lane
-    has its own workspace raster, so the result is the sequential one."""
+    has its own workspace raster, so the result is the sequential one.  "pin7": three equal lanes, whose third is lane index 3
+    and uses the fourth workspace raster."""
     S, nfr, y_t, x_t = 50_000, 2, 30_000, 200
     r = np.random.default_rng(41)
     bufs = [((r.standard_normal(S * nfr) + 1j * r.standard_normal(S * nfr)) * 1e-2).astype(np.complex64) for _ in range(4)]
     ctx.set_precision("exact")
-    ctx.set_option("pipe_mode", mode)
+    opt, value = ("pipe_pin", 7) if mode == "pin7" else ("pipe_mode", mode)
+    ctx.set_option(opt, value)
     try:
         _pipeline_vs_sequential(ctx, tsdr, bufs, [(y_t, x_t)] * 4, S)
     finally:
-        ctx.set_option("pipe_mode", -1)
+        ctx.set_option(opt, -1)
         ctx.set_precision("fast")
 
 
