@@ -537,6 +537,8 @@ int tsdr_frames_pipeline_info(tsdr_ctx *ctx, int *trials_left, int *chosen, floa
 #include "tempest_hip_register.h"
 /* display export of any of those pictures: ROI crop, range stretch (fixed / min-max / percentile) and 8-bit output on the GPU */
 #include "tempest_hip_display.h"
+/* coherent frame folding at a fractional frame period: the mean of a buffer's frames sampled at t0 + f*T, and the period scan */
+#include "tempest_hip_fold.h"
 
 /* ---- host -> device staging ring ---------------------------------------
  * The consumer side of AtomicCircularBuffer (AtomicAbstractSDRs.jl:64-190): `depth` slots of nEch samples in

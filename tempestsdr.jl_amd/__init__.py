@@ -18,3 +18,4 @@ from .api import (Context, Group, Resampler, StagingRing, SyncXY, amDemod, calcu
                   downgradeImage, fmDemod, getSpectrum, getWaterfall, getWelch, init_resampler, invert_amDemod,
                   naiveResampler, sig_to_image, vsync, zoom_autocorr)
 from .display import display_u8, display_u8_d  # noqa: F401
+from .fold import fold, fold_d, fold_plan, fold_scan, fold_scan_d, refine_period  # noqa: F401

@@ -249,6 +249,17 @@ RANGE_FIXED, RANGE_MINMAX, RANGE_PERCENTILE = 0, 1, 2  # TSDR_RANGE_*
 DISPLAY_INVERT, DISPLAY_SHARED = 1, 2  # TSDR_DISPLAY_* flags
 DISPLAY_BINS = 4096
 
+# include/tempest_hip_fold.h (included after tempest_hip_display.h): coherent frame folding at a fractional period, and its period scan
+_FOLD = [vp, vp, C.c_int, C.c_float, c_sz, C.c_double]  # ctx, iq, iq_fmt, scale, n, t0
+_GEOM = [C.c_int, C.c_int, C.c_int]  # n_frames, y_t, x_t
+_SIGS_FOLD = {
+    "tsdr_fold_iq_d": (C.c_int, _FOLD + [C.c_double] + _GEOM + [C.c_float, vp]),                    # T, ..., alpha, state
+    "tsdr_fold_iq": (C.c_int, _FOLD + [C.c_double] + _GEOM + [C.c_float, vp]),
+    "tsdr_fold_scan_iq_d": (C.c_int, _FOLD + [C.c_double, C.c_double, C.c_int] + _GEOM + [vp]),     # T0, dT, n_trials, ..., score
+    "tsdr_fold_scan_iq": (C.c_int, _FOLD + [C.c_double, C.c_double, C.c_int] + _GEOM + [vp, vp]),   # ..., score, best
+}
+FOLD_MAX_TRIALS, FOLD_STAGE_MAX = 4096, 240  # TSDR_FOLD_*
+
 
 def exported_names():
     """Every symbol include/tempest_hip.h declares (kept in sync by tests/test_abi.py)."""
@@ -280,6 +291,11 @@ def exported_names_display():
     return sorted(_SIGS_DISPLAY)
 
 
+def exported_names_fold():
+    """Every symbol include/tempest_hip_fold.h declares (kept in sync by tests/test_fold_host.py)."""
+    return sorted(_SIGS_FOLD)
+
+
 def _share_torch_hip_runtime():
     """PyTorch-ROCm wheels bundle their own libamdhip64/libhsa-runtime64.  Two HIP runtimes in one
     process cannot both own the GPU (whichever initialises second sees no device), and the dynamic
@@ -306,7 +322,7 @@ def load():
             "(there is no CPU fallback)")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(_SIGS.items()) + list(_SIGS_IQ.items()) + list(_SIGS_CPLX.items()) + list(_SIGS_HIRES.items()) + \
-            list(_SIGS_REGISTER.items()) + list(_SIGS_DISPLAY.items()):
+            list(_SIGS_REGISTER.items()) + list(_SIGS_DISPLAY.items()) + list(_SIGS_FOLD.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI is incomplete
         fn.restype = res
         fn.argtypes = args

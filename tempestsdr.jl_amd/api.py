@@ -621,6 +621,28 @@ class Context:
         """device-pointer form of display_u8: enqueues on the context's stream and returns"""
         return display.display_u8_d(self, images, n_images, h, w, out, roi, mode, lo, hi, p, invert, shared, ranges_out)
 
+    # -- coherent folding at a fractional frame period (include/tempest_hip_fold.h; fold.py) -------------------------
+    def fold(self, iq, t0, T, n_frames, y_t, x_t, alpha=0.0, state=None, fmt="cf32", scale=1.0):
+        """-> (y_t, x_t) float32: alpha * state + (1 - alpha) * the mean of n_frames frames of period T (samples, fractional)
+        starting at t0, each sampled at t0 + f*T + ...; alpha == 0: no state needed"""
+        return _fold.fold(self, iq, t0, T, n_frames, y_t, x_t, alpha, state, fmt, scale)
+
+    def fold_d(self, iq, fmt, scale, n, t0, T, n_frames, y_t, x_t, alpha, state):
+        """device-pointer form of fold: enqueues on the context's stream and returns"""
+        return _fold.fold_d(self, iq, fmt, scale, n, t0, T, n_frames, y_t, x_t, alpha, state)
+
+    def fold_scan(self, iq, t0, T0, dT, n_trials, n_frames, y_t, x_t, fmt="cf32", scale=1.0):
+        """-> (scores float64[n_trials], best): the variance times y_t * x_t of the picture folded at T0 + k * dT, and its first maximum"""
+        return _fold.fold_scan(self, iq, t0, T0, dT, n_trials, n_frames, y_t, x_t, fmt, scale)
+
+    def fold_scan_d(self, iq, fmt, scale, n, t0, T0, dT, n_trials, n_frames, y_t, x_t, score):
+        """device-pointer form of fold_scan (score: n_trials float64 on the device): enqueues and returns"""
+        return _fold.fold_scan_d(self, iq, fmt, scale, n, t0, T0, dT, n_trials, n_frames, y_t, x_t, score)
+
+    def refine_period(self, iq_d, fmt, scale, n, T_guess, n_frames, y_t, x_t, dT=0.125, half=8, levels=2, shrink=4):
+        """-> (T_hat, last_dT, scores): the frame period refined from a guess good to half a sample by folding at trial periods"""
+        return _fold.refine_period(self, iq_d, fmt, scale, n, T_guess, n_frames, y_t, x_t, dT, half, levels, shrink)
+
 
 def frames_d(ctx, sync, iq, nEch, S, y_t, x_t, alpha, do_align, state, frames_out=None, raster_out=None, sync_idx=None):
     """Device-pointer form of Context.frames: every array argument is a device buffer (torch tensor
@@ -696,6 +718,8 @@ from . import hires  # noqa: E402
 from . import register  # noqa: E402
 # the display export of any picture (the entry points of include/tempest_hip_display.h): display.py
 from . import display  # noqa: E402
+# coherent folding at a fractional frame period and its period scan (the entry points of include/tempest_hip_fold.h): fold.py
+from . import fold as _fold  # noqa: E402  (the package exports a function of that name)
 
 
 def frames_iq_d(ctx, sync, iq, fmt, scale, nEch, S, y_t, x_t, alpha, do_align, state, frames_out=None, raster_out=None, sync_idx=None,

@@ -720,5 +720,7 @@ include("TempestHIP_hires.jl")
 include("TempestHIP_register.jl")
 # display export of any of those pictures: hip_display_u8!, hip_display_u8_d! (include/tempest_hip_display.h)
 include("TempestHIP_display.jl")
+# coherent folding at a fractional frame period: hip_fold!, hip_fold_d!, hip_fold_scan, hip_fold_scan_d!, fold_plan (include/tempest_hip_fold.h)
+include("TempestHIP_fold.jl")
 
 end # module
