@@ -260,6 +260,15 @@ _SIGS_FOLD = {
 }
 FOLD_MAX_TRIALS, FOLD_STAGE_MAX = 4096, 240  # TSDR_FOLD_*
 
+# include/tempest_hip_cfold.h (included after tempest_hip_fold.h): phase-coherent folding with carrier de-rotation, and its carrier scan
+_SIGS_CFOLD = {
+    "tsdr_cfold_iq_d": (C.c_int, _FOLD + [C.c_double, C.c_double] + _GEOM + [C.c_float, vp]),                    # T, kappa, ..., alpha, state
+    "tsdr_cfold_iq": (C.c_int, _FOLD + [C.c_double, C.c_double] + _GEOM + [C.c_float, vp]),
+    "tsdr_cfold_scan_iq_d": (C.c_int, _FOLD + [C.c_double, C.c_double, C.c_double, C.c_int] + _GEOM + [vp]),     # T, kappa0, dkappa, n_trials, ..., score
+    "tsdr_cfold_scan_iq": (C.c_int, _FOLD + [C.c_double, C.c_double, C.c_double, C.c_int] + _GEOM + [vp, vp]),   # ..., score, best
+}
+CFOLD_MAX_TRIALS, CFOLD_STAGE_MAX = 4096, 120  # TSDR_CFOLD_*
+
 
 def exported_names():
     """Every symbol include/tempest_hip.h declares (kept in sync by tests/test_abi.py)."""
@@ -296,6 +305,11 @@ def exported_names_fold():
     return sorted(_SIGS_FOLD)
 
 
+def exported_names_cfold():
+    """Every symbol include/tempest_hip_cfold.h declares (kept in sync by tests/test_cfold_host.py)."""
+    return sorted(_SIGS_CFOLD)
+
+
 def _share_torch_hip_runtime():
     """PyTorch-ROCm wheels bundle their own libamdhip64/libhsa-runtime64.  Two HIP runtimes in one
     process cannot both own the GPU (whichever initialises second sees no device), and the dynamic
@@ -322,7 +336,7 @@ def load():
             "(there is no CPU fallback)")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(_SIGS.items()) + list(_SIGS_IQ.items()) + list(_SIGS_CPLX.items()) + list(_SIGS_HIRES.items()) + \
-            list(_SIGS_REGISTER.items()) + list(_SIGS_DISPLAY.items()) + list(_SIGS_FOLD.items()):
+            list(_SIGS_REGISTER.items()) + list(_SIGS_DISPLAY.items()) + list(_SIGS_FOLD.items()) + list(_SIGS_CFOLD.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI is incomplete
         fn.restype = res
         fn.argtypes = args

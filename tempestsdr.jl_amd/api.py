@@ -643,6 +643,28 @@ class Context:
         """-> (T_hat, last_dT, scores): the frame period refined from a guess good to half a sample by folding at trial periods"""
         return _fold.refine_period(self, iq_d, fmt, scale, n, T_guess, n_frames, y_t, x_t, dT, half, levels, shrink)
 
+    # -- phase-coherent folding with carrier de-rotation (include/tempest_hip_cfold.h; cfold.py) ----------------------
+    def cfold(self, iq, t0, T, kappa, n_frames, y_t, x_t, alpha=0.0, state=None, fmt="cf32", scale=1.0):
+        """-> (y_t, x_t) float32: alpha * state + (1 - alpha) * |the mean of n_frames complex frames of period T starting at t0,
+        frame f turned by -f * kappa turns|; alpha == 0: no state needed"""
+        return _cfold.cfold(self, iq, t0, T, kappa, n_frames, y_t, x_t, alpha, state, fmt, scale)
+
+    def cfold_d(self, iq, fmt, scale, n, t0, T, kappa, n_frames, y_t, x_t, alpha, state):
+        """device-pointer form of cfold: enqueues on the context's stream and returns"""
+        return _cfold.cfold_d(self, iq, fmt, scale, n, t0, T, kappa, n_frames, y_t, x_t, alpha, state)
+
+    def cfold_scan(self, iq, t0, T, kappa0, dkappa, n_trials, n_frames, y_t, x_t, fmt="cf32", scale=1.0):
+        """-> (scores float64[n_trials], best): the energy of the complex picture folded at kappa0 + k * dkappa, and its first maximum"""
+        return _cfold.cfold_scan(self, iq, t0, T, kappa0, dkappa, n_trials, n_frames, y_t, x_t, fmt, scale)
+
+    def cfold_scan_d(self, iq, fmt, scale, n, t0, T, kappa0, dkappa, n_trials, n_frames, y_t, x_t, score):
+        """device-pointer form of cfold_scan (score: n_trials float64 on the device): enqueues and returns"""
+        return _cfold.cfold_scan_d(self, iq, fmt, scale, n, t0, T, kappa0, dkappa, n_trials, n_frames, y_t, x_t, score)
+
+    def refine_carrier(self, iq_d, fmt, scale, n, t0, T, n_frames, y_t, x_t, oversample=4, half=8, levels=2, shrink=4):
+        """-> (kappa_hat mod 1, last_dkappa, scores): the carrier's advance per frame in turns, by a coarse-to-fine carrier scan"""
+        return _cfold.refine_carrier(self, iq_d, fmt, scale, n, t0, T, n_frames, y_t, x_t, oversample, half, levels, shrink)
+
 
 def frames_d(ctx, sync, iq, nEch, S, y_t, x_t, alpha, do_align, state, frames_out=None, raster_out=None, sync_idx=None):
     """Device-pointer form of Context.frames: every array argument is a device buffer (torch tensor
@@ -720,6 +742,8 @@ from . import register  # noqa: E402
 from . import display  # noqa: E402
 # coherent folding at a fractional frame period and its period scan (the entry points of include/tempest_hip_fold.h): fold.py
 from . import fold as _fold  # noqa: E402  (the package exports a function of that name)
+# phase-coherent folding with carrier de-rotation and its carrier scan (the entry points of include/tempest_hip_cfold.h): cfold.py
+from . import cfold as _cfold  # noqa: E402  (the package exports a function of that name)
 
 
 def frames_iq_d(ctx, sync, iq, fmt, scale, nEch, S, y_t, x_t, alpha, do_align, state, frames_out=None, raster_out=None, sync_idx=None,

@@ -13,7 +13,7 @@
 //                           leave the registers; a workgroup writes its f64 (sum x, sum x^2) to the workspace (fixed shuffle tree,
 //                           then wave order), and k_fold_score adds them with one lane per trial, in tile order.
 //
-// Coordinates: B = t0 + f*T is split once per frame into bi = floor(B) and bf = B - bi (exact); a pixel's position relative to bi
+// Coordinates (fold_pos.h, shared with raster_cfold.hip): B = t0 + f*T is split once per frame into bi = floor(B) and bf = B - bi (exact); a pixel's position relative to bi
 // is s = bf + ((m + 1/2)*(T/P) - 1/2), evaluated from m for the first pixel of a lane's run and as fma(i, T/P, s) for its i-th (one
 // rounding each, no sum carried along the line), so the f64 rounding happens at the magnitude of one frame, not of the buffer.
 // The buffer clamps act on s as [-bi, n-1-bi].
@@ -23,6 +23,7 @@
 
 #include "common.h"
 #include "down_fused.h"
+#include "fold_pos.h"
 
 namespace tsdr {
 namespace {
@@ -47,26 +48,7 @@ struct FoldArgs {
   double *part;         // scan: [trial][tile][2]
 };
 
-struct FramePos {   // one frame's origin: integer part, and the clamps relative to it
-  double bf, lo, hi, hik;
-  long long bi;
-};
-
-__device__ inline FramePos frame_pos(const FoldArgs &A, double T, int f) {
-  const double B = A.t0 + (double)f * T;
-  const double bi = floor(B);
-  return FramePos{B - bi, -bi, (double)(A.n - 1) - bi, (double)(A.n - 2) - bi, (long long)bi};
-}
-
-// position of pixel m of the frame at `fp`, relative to fp.bi, before the buffer clamps
-__device__ inline double fold_s(const FramePos &fp, double spp, unsigned m) { return fp.bf + (((double)m + 0.5) * spp - 0.5); }
-// ... its left tap (relative to fp.bi) and the weight of the right one
-__device__ inline int fold_tap(const FramePos &fp, double s, double &d) {
-  s = fmin(fmax(s, fp.lo), fp.hi);
-  const double k = fmin(floor(s), fp.hik);
-  d = s - k;
-  return (int)k;
-}
+// FramePos, frame_pos, fold_s, fold_tap: fold_pos.h (shared with raster_cfold.hip)
 
 template <int TP, int NW, bool STAGED, bool SCAN>
 __global__ __launch_bounds__(NW * 64) void k_fold(FoldArgs A) {

@@ -722,5 +722,7 @@ include("TempestHIP_register.jl")
 include("TempestHIP_display.jl")
 # coherent folding at a fractional frame period: hip_fold!, hip_fold_d!, hip_fold_scan, hip_fold_scan_d!, fold_plan (include/tempest_hip_fold.h)
 include("TempestHIP_fold.jl")
+# phase-coherent folding with carrier de-rotation: hip_cfold!, hip_cfold_d!, hip_cfold_scan, hip_cfold_scan_d!, refine_carrier (include/tempest_hip_cfold.h)
+include("TempestHIP_cfold.jl")
 
 end # module
