@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-from .fold import _host_iq, _iq_args, first_max
+from .fold import _host_iq, _host_state, _iq_args, first_max
 
 
 def cfold_d(ctx, iq, fmt, scale, n, t0, T, kappa, n_frames, y_t, x_t, alpha, state):
@@ -26,11 +26,7 @@ def cfold(ctx, iq, t0, T, kappa, n_frames, y_t, x_t, alpha=0.0, state=None, fmt=
     `fmt`), averaged into `state` (left untouched; required when alpha != 0) -- tsdr_cfold_iq"""
     from . import api
     a, code, n = _host_iq(iq, fmt)
-    if alpha != 0.0 and state is None:
-        raise AssertionError("cfold: alpha != 0 needs a state")
-    out = np.zeros(int(y_t) * int(x_t), np.float32) if state is None else np.asarray(state, np.float32).reshape(-1, order="F").copy()
-    if out.size != int(y_t) * int(x_t):
-        raise AssertionError(f"cfold: state has {out.size} pixels, expected {int(y_t) * int(x_t)}")
+    out = _host_state("cfold", state, alpha, y_t, x_t)
     ctx.call("tsdr_cfold_iq", api._ptr(a), code, C.c_float(scale), n, C.c_double(t0), C.c_double(T), C.c_double(kappa), int(n_frames),
              int(y_t), int(x_t), C.c_float(alpha), api._ptr(out))
     return out.reshape((int(y_t), int(x_t)), order="F")

@@ -51,16 +51,22 @@ def _host_iq(iq, fmt):
     return api._int_iq(iq, fmt, "fold")
 
 
+def _host_state(who, state, alpha, y_t, x_t):
+    """the y_t * x_t float32 vector a host fold works on: a column-major copy of `state` (required when alpha != 0), else zeros"""
+    if alpha != 0.0 and state is None:
+        raise AssertionError(f"{who}: alpha != 0 needs a state")
+    out = np.zeros(int(y_t) * int(x_t), np.float32) if state is None else np.asarray(state, np.float32).reshape(-1, order="F").copy()
+    if out.size != int(y_t) * int(x_t):
+        raise AssertionError(f"{who}: state has {out.size} pixels, expected {int(y_t) * int(x_t)}")
+    return out
+
+
 def fold(ctx, iq, t0, T, n_frames, y_t, x_t, alpha=0.0, state=None, fmt="cf32", scale=1.0):
     """host arrays -> the (y_t, x_t) Fortran-order float32 picture: the fold of `iq` (complex64, or integer IQ of format `fmt`),
     averaged into `state` (left untouched; required when alpha != 0) -- tsdr_fold_iq"""
     from . import api
     a, code, n = _host_iq(iq, fmt)
-    if alpha != 0.0 and state is None:
-        raise AssertionError("fold: alpha != 0 needs a state")
-    out = np.zeros(int(y_t) * int(x_t), np.float32) if state is None else np.asarray(state, np.float32).reshape(-1, order="F").copy()
-    if out.size != int(y_t) * int(x_t):
-        raise AssertionError(f"fold: state has {out.size} pixels, expected {int(y_t) * int(x_t)}")
+    out = _host_state("fold", state, alpha, y_t, x_t)
     ctx.call("tsdr_fold_iq", api._ptr(a), code, C.c_float(scale), n, C.c_double(t0), C.c_double(T), int(n_frames), int(y_t), int(x_t),
              C.c_float(alpha), api._ptr(out))
     return out.reshape((int(y_t), int(x_t)), order="F")

@@ -9,8 +9,8 @@ TSDR_CFOLD_STAGE_MAX = 120; asserted by profile name):
     U  70 x 150, T 1207.73   W  18  cfold_tile / cfold_scan_tile      partial second line tile, partial pixel tile
     M  66 x 160, T 9150.37   W 114  cfold_tile / cfold_scan_tile
     D  77 x 131, T 11600.61  W 151  cfold_direct / cfold_scan_direct  odd sizes; starts one period in
-    S  20 x 140, T 2550.3    W 120  cfold_tile                        the widest span the tiled kernel stages
-    R  20 x 140, T 2565.3    W 121  cfold_direct                      the narrowest span of the direct kernel
+    S  20 x 140, T 2550.3    W 120  cfold_tile / cfold_scan_tile      the widest span the tiled kernel stages
+    R  20 x 140, T 2565.3    W 121  cfold_direct / cfold_scan_direct  the narrowest span of the direct kernel
     X   8 x 16,  T 5000.5    W 5004 cfold_direct / cfold_scan_direct  39 samples per pixel
     Q  66 x 160, T 9150.37, F 16, -10 dB: the capability case
 
@@ -215,6 +215,28 @@ def test_scan_scores_and_maximum(ctx, name, n_trials):
     ctx.call("tsdr_cfold_scan_iq", C.c_void_p(iq.ctypes.data), 0, C.c_float(1.0), iq.size, C.c_double(c["t0"]), C.c_double(c["T"]),
              C.c_double(k0), C.c_double(dk), n_trials, c["F"], c["y"], c["x"], C.c_void_p(sc.ctypes.data), C.byref(b))
     assert np.array_equal(sc, got) and b.value == half
+
+
+@pytest.mark.parametrize("name", ["S", "R"])
+def test_scan_at_the_staging_boundary(ctx, name):
+    """nine trials (a batch and one more) at the boundary cases: the scan makes the fold's choice (W 120: cfold_scan_tile, W 121:
+    cfold_scan_direct), every score within the bound of the reference's.  No claim about the maximum: these cases carry no margin
+    precondition."""
+    c = CASES[name]
+    iq, amax = _capture(name)
+    P, dk = c["y"] * c["x"], _dk(c)
+    k0 = KAPPA_TRUE - 4 * dk
+    ref = _ref_scan(name, N_TRIALS)
+    bounds = np.array([R.score_bound(R.eps_z(c["F"], amax), P, r) for r in ref])
+    with D.Arenas(ctx) as A:
+        d_iq, d_sc = A.input("iq", iq, IQ_PHASE[name]), A.output("score", 8 * N_TRIALS, 8)
+        names = _profiled(ctx, lambda: _scan_d(ctx, d_iq.ptr, 0, 1.0, iq.size, c["t0"], c["T"], k0, dk, N_TRIALS, c["F"], c["y"], c["x"],
+                                               d_sc.ptr))
+        A.check()
+        got = d_sc.get(np.float64)
+    assert names == {"cfold_scan_" + KERNEL[name], "cfold_score"}, names
+    _report(f"cscan {name} at the boundary", float(np.max(np.abs(got - ref) / bounds)), 1.0)
+    assert np.all(np.abs(got - ref) <= bounds), (got, ref, bounds)
 
 
 def test_a_trial_scores_the_picture_the_fold_leaves(ctx):

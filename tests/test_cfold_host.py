@@ -1,7 +1,7 @@
 """Host-side checks of phase-coherent frame folding (no GPU): include/tempest_hip_cfold.h, its ctypes table (_lib._SIGS_CFOLD), its
 Python module (cfold.py) and its Julia shim (julia/TempestHIP_cfold.jl) agree with each other and with the library, the way
-test_fold_host.py pins tempest_hip_fold.h; the launch rules of csrc/raster_cfold.hip; the coordinate helpers shared with
-csrc/raster_fold.hip; and the numpy reference the GPU tests compare against (tests/cfold_ref.py) on answers known without it."""
+test_fold_host.py pins tempest_hip_fold.h; the launch rules of csrc/raster_cfold.hip; the engine shared with
+csrc/raster_fold.hip (csrc/fold_engine.h); and the numpy reference the GPU tests compare against (tests/cfold_ref.py) on answers known without it."""
 import ctypes as C
 import inspect
 import math
@@ -23,6 +23,7 @@ FOLD_H = os.path.join(ROOT, "include", "tempest_hip_fold.h")
 CFOLD_SHIM = os.path.join(ROOT, "tempestsdr.jl_amd", "julia", "TempestHIP_cfold.jl")
 CSRC = os.path.join(ROOT, "tempestsdr.jl_amd", "csrc")
 KERNEL = os.path.join(CSRC, "raster_cfold.hip")
+ENGINE = os.path.join(CSRC, "fold_engine.h")   # the kernels and the host path, shared with raster_fold.hip
 
 SYMS = ["tsdr_cfold_iq", "tsdr_cfold_iq_d", "tsdr_cfold_scan_iq", "tsdr_cfold_scan_iq_d"]
 HEAD = ["tsdr_ctx *ctx", "const void *iq", "int iq_fmt", "float scale", "size_t n", "double t0", "double T"]
@@ -181,25 +182,36 @@ def test_every_new_entry_point_is_called_by_the_gpu_suite():
 def test_kernel_source_keeps_its_launch_rules():
     src = open(KERNEL).read()
     code = re.sub(r"//.*", "", src)
-    assert "stream_grid(" not in code and "stream_blocks(" not in code and "ceil_div(" in code, "exact grids"
+    engine = re.sub(r"//.*", "", open(ENGINE).read())
     for name in ("cfold_tile", "cfold_direct", "cfold_scan_tile", "cfold_scan_direct", "cfold_score"):
         assert f'TSDR_LAUNCH(ctx, "{name}"' in src, name
-    assert len(re.findall(r"\bTSDR_LAUNCH\(", code)) == 5 and "hipLaunchKernelGGL" not in code, "every launch goes through TSDR_LAUNCH"
-    assert not re.search(r"\batomic\w*\(", code), "no atomics at all: partial sums are combined in a fixed order"
-    assert not re.search(r"\basm\b", code), "no inline assembly"
-    assert "blockIdx.y * KB" in code and re.search(r"constexpr int kBatch = (\d+);", code), "the trial batch rides in blockIdx.y"
+    assert len(re.findall(r"\bTSDR_LAUNCH\(", code)) == 5 and "TSDR_LAUNCH(" not in engine, "the launches stay in the flavour's file"
+    assert "ceil_div(" in code and "ceil_div(" in engine
+    for text in (code, engine):
+        assert "stream_grid(" not in text and "stream_blocks(" not in text, "exact grids"
+        assert "hipLaunchKernelGGL" not in text, "every launch goes through TSDR_LAUNCH"
+        assert not re.search(r"\batomic\w*\(", text), "no atomics at all: partial sums are combined in a fixed order"
+        assert not re.search(r"\basm\b", text), "no inline assembly"
+    assert "blockIdx.y * KB" in engine and re.search(r"constexpr int kBatch = (\d+);", code), "the trial batch rides in blockIdx.y"
     assert int(re.search(r"constexpr int kBatch = (\d+);", code).group(1)) >= 8
+    assert re.search(r'"cfold_scan_tile", \(k_fold_engine<Coherent, kScanP, kFoldTileWaves, kBatch,', code), "the scan kernels get the batch"
+    assert re.search(r'"cfold_scan_direct", \(k_fold_engine<Coherent, kFoldDirectP, kFoldDirectWaves, kBatch,', code)
 
 
 def test_coordinate_helpers_are_shared_with_the_envelope_fold():
-    shared = open(os.path.join(CSRC, "fold_pos.h")).read()
-    for name in ("struct FramePos", "frame_pos(", "fold_s(", "fold_tap("):
+    shared = open(ENGINE).read()
+    for name in ("struct FramePos", "frame_pos(", "fold_s(", "fold_tap(", "__umulhi(", "__fmul_rn(alpha, *o)", "__shfl_down(", "__syncthreads()"):
         assert name in shared, name
+    assert not os.path.exists(os.path.join(CSRC, "fold_pos.h")), "the coordinate helpers moved into the engine"
     for f in ("raster_fold.hip", "raster_cfold.hip"):
         code = re.sub(r"//.*", "", open(os.path.join(CSRC, f)).read())
-        assert '#include "fold_pos.h"' in code, f
+        assert '#include "fold_engine.h"' in code, f
         assert "struct FramePos" not in code and not re.search(r"inline \w+ (frame_pos|fold_s|fold_tap)\(", code), f
-        assert "frame_pos(" in code and "fold_s(" in code and "fold_tap(" in code, f
+        # ... nor the staging loop, the walk, the IIR epilogue, the reductions or a kernel of its own
+        for piece in (r"frame_pos\(", r"fold_s\(", r"fold_tap\(", r"__umulhi\(", r"\bld_iq\(", r"__syncthreads\(", "__shfl", "__shared__",
+                      "__global__", r"\bbeta\b", r"\*o\b", "hipMemcpyAsync", r"scratch\("):
+            assert not re.search(piece, code), (f, piece)
+        assert "k_fold_engine<" in code and "k_fold_score<" in code and code.count("fold_entry<") == 4, f
 
 
 def test_workspace_and_build_know_the_feature():

@@ -7,8 +7,8 @@ Which case reaches which kernel (W = ceil(128 * T / P) + 3 against TSDR_FOLD_STA
     U  70 x 150, T 1207.73   W  18  fold_tile / fold_scan_tile   P/T = 8.69; partial second line tile, partial pixel tile
     M  66 x 160, T 9150.37   W 114  fold_tile / fold_scan_tile   P/T = 1.15
     D  77 x 131, T 11600.61  W 151  fold_tile / fold_scan_tile   P/T = 0.87; odd sizes; starts one period in
-    S  20 x 140, T 5180.3    W 240  fold_tile                    the widest span the tiled kernel stages
-    R  20 x 140, T 5195.3    W 241  fold_direct                  the narrowest span of the direct kernel
+    S  20 x 140, T 5180.3    W 240  fold_tile / fold_scan_tile   the widest span the tiled kernel stages
+    R  20 x 140, T 5195.3    W 241  fold_direct / fold_scan_direct   the narrowest span of the direct kernel
     X   8 x 16,  T 5000.5    W 5004 fold_direct / fold_scan_direct   39 samples per pixel
 
 Captures and references are made once per case (functools caches); nothing modifies them."""
@@ -294,6 +294,26 @@ def test_scan_on_the_direct_path(ctx):
     assert names == {"fold_scan_direct", "fold_score"}, names
     assert np.all(np.abs(got - ref) <= [R.score_bound(e, P, r) for r in ref]), (got, ref)
     assert abs(got[3] - R.score_of(pic)) <= 1e-12 * got[3], "trial 3 scores the picture the fold leaves at T0 + 3 dT"
+
+
+@pytest.mark.parametrize("name", ["S", "R"])
+def test_scan_at_the_staging_boundary(ctx, name):
+    """three trials at a quarter sample whose largest is the case's T: the scan makes the fold's choice at the boundary (W 240:
+    fold_scan_tile, W 241: fold_scan_direct; 128 T / P = 236.8 and 237.5, so the rounding of T0 + 2 dT cannot move it), every score
+    within the bound of the reference's.  No claim about the maximum: these cases carry no margin precondition."""
+    c = CASES[name]
+    iq, a = _capture(name)
+    P, T0, nt = c["y"] * c["x"], c["T"] - 2 * DT, 3
+    ref = R.scan(a, c["t0"], T0, DT, nt, c["F"], c["y"], c["x"])
+    bounds = np.array([R.score_bound(R.eps(c["F"], a.max()), P, r) for r in ref])
+    with D.Arenas(ctx) as A:
+        d_iq, d_sc = A.input("iq", iq, IQ_PHASE[name]), A.output("score", 8 * nt, 8)
+        names = _profiled(ctx, lambda: _scan_d(ctx, d_iq.ptr, 0, 1.0, iq.size, c["t0"], T0, DT, nt, c["F"], c["y"], c["x"], d_sc.ptr))
+        A.check()
+        got = d_sc.get(np.float64)
+    assert names == {"fold_scan_" + KERNEL[name], "fold_score"}, names
+    _report(f"scan {name} at the boundary", float(np.max(np.abs(got - ref) / bounds)), 1.0)
+    assert np.all(np.abs(got - ref) <= bounds), (got, ref, bounds)
 
 
 # ---------------------------------------------------------------- 6. refine_period

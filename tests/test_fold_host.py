@@ -21,6 +21,7 @@ FOLD_H = os.path.join(ROOT, "include", "tempest_hip_fold.h")
 DISP_H = os.path.join(ROOT, "include", "tempest_hip_display.h")
 FOLD_SHIM = os.path.join(ROOT, "tempestsdr.jl_amd", "julia", "TempestHIP_fold.jl")
 KERNEL = os.path.join(ROOT, "tempestsdr.jl_amd", "csrc", "raster_fold.hip")
+ENGINE = os.path.join(ROOT, "tempestsdr.jl_amd", "csrc", "fold_engine.h")   # the kernels and the host path, shared with raster_cfold.hip
 
 SYMS = ["tsdr_fold_iq", "tsdr_fold_iq_d", "tsdr_fold_scan_iq", "tsdr_fold_scan_iq_d"]
 HEAD = ["tsdr_ctx *ctx", "const void *iq", "int iq_fmt", "float scale", "size_t n", "double t0"]
@@ -171,13 +172,18 @@ def test_every_new_entry_point_is_called_by_the_gpu_suite():
 def test_kernel_source_keeps_its_launch_rules():
     src = open(KERNEL).read()
     code = re.sub(r"//.*", "", src)
-    assert "stream_grid(" not in code and "stream_blocks(" not in code and "ceil_div(" in code, "exact grids"
+    engine = re.sub(r"//.*", "", open(ENGINE).read())
+    assert '#include "fold_engine.h"' in code, "the kernels are the engine's"
     for name in ("fold_tile", "fold_direct", "fold_scan_tile", "fold_scan_direct", "fold_score"):
         assert f'TSDR_LAUNCH(ctx, "{name}"' in src, name
-    assert len(re.findall(r"\bTSDR_LAUNCH\(", code)) == 5 and "hipLaunchKernelGGL" not in code, "every launch goes through TSDR_LAUNCH"
-    assert not re.search(r"\batomic\w*\(", code), "no atomics at all: partial sums are combined in a fixed order"
-    assert not re.search(r"atomic\w*\([^;]*float", code)
-    assert not re.search(r"\basm\b", code), "no inline assembly"
+    assert len(re.findall(r"\bTSDR_LAUNCH\(", code)) == 5 and "TSDR_LAUNCH(" not in engine, "the launches stay in the flavour's file"
+    assert "ceil_div(" in code and "ceil_div(" in engine
+    for text in (code, engine):
+        assert "stream_grid(" not in text and "stream_blocks(" not in text, "exact grids"
+        assert "hipLaunchKernelGGL" not in text, "every launch goes through TSDR_LAUNCH"
+        assert not re.search(r"\batomic\w*\(", text), "no atomics at all: partial sums are combined in a fixed order"
+        assert not re.search(r"atomic\w*\([^;]*float", text)
+        assert not re.search(r"\basm\b", text), "no inline assembly"
 
 
 def test_workspace_and_build_know_the_feature():

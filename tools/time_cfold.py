@@ -10,6 +10,8 @@
 #
 #     python tools/time_cfold.py [out.json = profiles/cfold.json] [workloads = C2,C5]
 #
+# Workload DIRECT (640x480 at 50 MS/s, not in the default) is the one whose spans do not fit the staged kernels.
+#
 # Prints one JSON document and writes it to out.json.  GPU box only.
 import importlib
 import json
@@ -28,7 +30,9 @@ T = load_package()
 synth = importlib.import_module("tempestsdr_jl_amd.synth")
 OUT = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "cfold.json")
 WANT = (sys.argv[2] if len(sys.argv) > 2 else "C2,C5").split(",")
-WORKLOADS = {"C2": dict(Fs=20e6, x_t=2576, y_t=1125, fv=60.14, frames=30), "C5": dict(Fs=50e6, x_t=4400, y_t=2250, fv=60.14, frames=30)}
+WORKLOADS = {"C2": dict(Fs=20e6, x_t=2576, y_t=1125, fv=60.14, frames=30), "C5": dict(Fs=50e6, x_t=4400, y_t=2250, fv=60.14, frames=30),
+             # not in the default: T / P = 2.7 samples per pixel, W = 350 -- all four calls take their direct kernel (kernels_us_per_call)
+             "DIRECT": dict(Fs=50e6, x_t=640, y_t=480, fv=60.14, frames=30)}
 MIN_SECONDS, ROUNDS = 0.3, 5
 N_TRIALS, DT = 17, 0.125          # the envelope scan of tools/time_fold.py
 OVERSAMPLE = 4                    # the coherent scan: refine_carrier's level 0
