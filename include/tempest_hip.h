@@ -142,6 +142,11 @@ int tsdr_get_precision(tsdr_ctx *ctx);
  *   "down_spp_max_pct" the raster-free TSDR_FAST route uses the tap kernel up to this many samples per raster pixel, in percent
  *                 (default 200), the raster walk with out == NULL above; "down_xcd" 1 (default): XCD-aware tile order of that kernel.
  *   "beta_waves"  wavefronts per workgroup of the vsync statistics kernel: 4 (default) or 8; identical results.
+ *   "frames_overlap" 1 (default): tsdr_frames_d / _sc16_d / _iq_d run a buffer's tail on an internal stream beside the next call's
+ *                 image launch (see tsdr_frames_d) while the context is the only one alive on its device -- two contexts on one
+ *                 GPU fill each other's gaps already, and their internal streams cost them 3-4 % -- ; 2: whatever else is alive
+ *                 on the device; 0: every call on the context's stream, one launch after the other.  Identical results.
+ *                 Setting it first orders the context's stream behind the calls in flight.  TSDR_FRAMES_OVERLAP presets it.
  *   "pipe_mode"   how tsdr_frames_submit_d arranges successive buffers on its internal streams: -1 (default) = the measured
  *                 choice (below); 0 = image launches on one stream, every buffer's tail on a second one ("pipe_priority" 1,
  *                 default: of the highest priority); 1 = whole buffers alternate between "pipe_lanes" (2 or 3) equal streams,
@@ -467,6 +472,26 @@ int tsdr_resampler_run_f64_d(tsdr_resampler *r, const double *in, size_t n_in, d
 int tsdr_frames(tsdr_ctx *ctx, tsdr_sync *sync, const float *iq, size_t nEch, size_t S, int y_t, int x_t,
                 float alpha, int do_align, float *imageOut_state, float *frames_out, float *raster_out,
                 int *sync_idx, int *n_frames);
+/* tsdr_frames_d (and _sc16_d / _iq_d) only enqueue.  In the default mode (TSDR_FAST, the context's own stream, no profiling,
+ * option "frames_overlap" 1 with no other context alive on the device, or 2) the image launch goes to one internal stream and the buffer's tail -- vsync statistics, sync guard,
+ * shift + IIR -- to a second one behind it, so that the tail of call k runs beside the image launch of call k+1; nothing is
+ * measured and no call spends buffers on trials (the arrangement is fixed: tsdr_frames_pipeline_info does not change).  Results
+ * are those of "frames_overlap" 0, bit for bit.  Ordering: the call waits for whatever the context's stream holds at the time
+ * (uploads, a producer's kernels), and what the library puts on the context's stream afterwards is ordered behind the calls
+ * before it: every kernel launch of every entry point, and these copies and event records -- tsdr_upload / tsdr_download,
+ * tsdr_timer_start / _stop, tsdr_ring_take_d, tsdr_iq_expand_d of ComplexF32, the identity cases of the f64 resizes, the FFT's
+ * first copy, tsdr_synchronize, tsdr_frames_flush.  (The library's other direct stream operations -- clearing or staging its own
+ * workspaces ahead of a launch -- touch no buffer of the caller's.)  So whatever the caller does next through the library sees
+ * completed results; no flush is needed.  A caller that reads the outputs with its OWN work (another runtime's kernels, its own streams) first calls
+ * tsdr_synchronize, or tsdr_frames_flush and then orders itself behind the context's stream -- or adopts that stream with
+ * tsdr_set_stream, where calls stay on it and stream order alone holds, as with "frames_overlap" 0.
+ * Lifetime: until such a point has been reached AND the context's stream has completed, the caller must not touch or free
+ * iq, the SyncXY state, imageOut_state, frames_out / raster_out / sync_idx of the calls before it.  Successive calls MAY share
+ * one frames_out / raster_out / sync_idx (image launches run in call order on one stream, and so do the tails).  A call whose
+ * configuration (frames per buffer, S, y_t, x_t, raster or not, SyncXY, input format) differs from the previous one's, or that
+ * follows a tsdr_frames_submit_* on the same context, waits on the HOST for the buffers in flight (bounded: "wait_ms"), as
+ * does a call that fails after it has launched.  With nothing in flight -- a tsdr_synchronize, download or other completed host
+ * wait since the last call -- such a call waits for nothing, whatever the context's stream holds. */
 int tsdr_frames_d(tsdr_ctx *ctx, tsdr_sync *sync, const float *iq, size_t nEch, size_t S, int y_t, int x_t,
                   float alpha, int do_align, float *imageOut_state, float *frames_out, float *raster_out,
                   int *sync_idx, int *n_frames);

@@ -668,7 +668,9 @@ class Context:
 
 def frames_d(ctx, sync, iq, nEch, S, y_t, x_t, alpha, do_align, state, frames_out=None, raster_out=None, sync_idx=None):
     """Device-pointer form of Context.frames: every array argument is a device buffer (torch tensor
-    or raw address); enqueues on the context's stream and returns without synchronising."""
+    or raw address); enqueues and returns without synchronising -- on the context's stream, or (option "frames_overlap", the
+    default while the context is alone on its device) with the buffer's tail on an internal stream beside the next call's image
+    launch; whatever goes through the context afterwards is ordered behind it either way (tempest_hip.h: tsdr_frames_d)."""
     n = C.c_int(0)
     ctx.call("tsdr_frames_d", C.c_void_p(sync.h if sync is not None else 0), _ptr(iq), int(nEch), int(S), int(y_t),
              int(x_t), C.c_float(alpha), int(bool(do_align)), _ptr(state), _ptr(frames_out), _ptr(raster_out),

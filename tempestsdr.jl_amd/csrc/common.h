@@ -90,7 +90,11 @@ struct Pipeline {
   PipeKey key;                      // what the slot offsets of the submissions in flight were computed from
   int last_slot = -1;               // slot of the latest submission: its tail is behind everything submitted
   int cand_now = -1;                // arrangement (index into kCands) of the submissions in flight
+  int cand_submit = -1;             // ... of the latest tsdr_frames_submit_* call: what tsdr_frames_pipeline_info reports when nothing is measured
+  bool from_run = false;            // the lanes carry tsdr_frames_d / _sc16_d / _iq_d calls (frames.hip:frames_run), not submissions: the
+                                    // caller was promised no flush point, so whatever the context's stream receives next drains first (run_fence)
   bool one_lane = false;            // ... is the one-stream arrangement (no event per buffer; pipe_drain records one when asked)
+  LaneBusy busy;                    // which pool streams may still hold work (loop_policy.h): pipe_sync_lanes waits for these only
   PipeTuner tuner;
   void release() {                  // tsdr_destroy, with every lane idle
     for (auto &l : pool) if (l) (void)hipStreamDestroy(l);
@@ -184,6 +188,9 @@ struct tsdr_ctx {
   int opt_pipe_dev_events = 1;      // the pipeline's hand-over events release to device scope (TSDR_PIPE_DEV_EVENTS=0: the default system scope; A/B)
   int opt_pipe_tune = 1;            // 0: "pipe_mode" -1 means arrangement 0 with rasters, 1 without (rounds 1-4), nothing is measured
   int opt_pipe_pin = -1;            // "pipe_pin" k >= 0: arrangement k of loop_policy.h:kCands, nothing measured; -1: not pinned
+  int opt_frames_overlap = 1;       // "frames_overlap": tsdr_frames_d / _sc16_d / _iq_d leave a buffer's tail on the pipeline's tail lane, beside the
+                                    // next call's image launch (frames.hip:frames_run); 0: every call on the context's stream, as before;
+                                    // 1: while this is the device's only context; 2: whatever else lives on the device
   // Every host-side wait of this library is bounded (round 6): a stream that does not complete within opt_wait_ms returns
   // TSDR_EHIP with the waiting stage in tsdr_last_error instead of holding the caller's thread (a GUI task inside a ccall) for
   // good.  0: unbounded (plain hipStreamSynchronize).  Option "wait_ms" / TSDR_WAIT_MS.
@@ -208,6 +215,10 @@ int lds_opt_in(tsdr_ctx *ctx, const void *fn, size_t bytes);
 // frames.hip: order the context's stream behind every buffer submitted to the pipeline (tsdr_frames_submit_d)
 int pipe_drain(tsdr_ctx *ctx);
 int pipe_sync_lanes(tsdr_ctx *ctx);    // bounded host-side wait for the pipeline's internal streams (TSDR_EHIP when one is stuck)
+// A tsdr_frames_d call that left its tail on the lanes promised its caller stream order, not a flush point: everything the
+// context's stream is about to receive -- any launch (TSDR_LAUNCH), a copy, a timing event -- comes behind those tails.
+int contexts_on_device(int device);   // ctx.hip: contexts alive on it (tsdr_create .. tsdr_destroy)
+static inline int run_fence(tsdr_ctx *c) { return c->pipe.n && c->pipe.from_run ? pipe_drain(c) : (int)TSDR_OK; }
 static inline PipeOpts pipe_opts(const tsdr_ctx *c) {
   return PipeOpts{c->opt_pipe_mode, c->opt_pipe_lanes, c->opt_pipe_priority, c->opt_pipe_tune, c->opt_pipe_pin};
 }
@@ -227,9 +238,14 @@ void prof_end(tsdr_ctx *ctx);
   } while (0)
 
 // Launch a kernel on the context's stream; when profiling is on the launch is
-// bracketed by its own hipEvent pair so bench.py can read per-kernel durations live.
+// bracketed by its own hipEvent pair so bench.py can read per-kernel durations live.  A launch that goes to the context's
+// stream itself (not to a lane: LaneScope) first orders that stream behind what tsdr_frames_d left on the lanes (run_fence).
 #define TSDR_LAUNCH(ctx, kname, kernel, grid, block, shmem, ...)                              \
   do {                                                                                        \
+    if ((ctx)->launch_stream == (ctx)->stream) {                                              \
+      int _rf = tsdr::run_fence((ctx));                                                       \
+      if (_rf) return _rf;                                                                    \
+    }                                                                                         \
     if ((ctx)->prof_on) tsdr::prof_begin((ctx), kname);                                       \
     hipLaunchKernelGGL(kernel, grid, block, shmem, (ctx)->launch_stream, __VA_ARGS__);               \
     if ((ctx)->prof_on) tsdr::prof_end((ctx));                                                \

@@ -1,4 +1,5 @@
 // ctx.hip -- context lifetime, workspace, error reporting, HIP-event measurement.
+#include <atomic>
 #include <cstdarg>
 #include <cstdlib>
 #include <chrono>
@@ -69,7 +70,11 @@ int wait_event(tsdr_ctx *ctx, hipEvent_t e, const char *what) {
 }
 
 int wait_stream(tsdr_ctx *ctx, hipStream_t s, const char *what) {
-  if (ctx->opt_wait_ms <= 0) { TSDR_HIP(ctx, hipStreamSynchronize(s)); return TSDR_OK; }
+  if (ctx->opt_wait_ms <= 0) {
+    TSDR_HIP(ctx, hipStreamSynchronize(s));
+    if (s == ctx->stream) ctx->pipe.busy.host_saw_stream();
+    return TSDR_OK;
+  }
   if (!ctx->wait_ev) {
     // (an event belongs to the device that is current when it is created: the context's, whatever the caller's is)
     int cur = -1;
@@ -80,7 +85,9 @@ int wait_stream(tsdr_ctx *ctx, hipStream_t s, const char *what) {
     if (e != hipSuccess) return hip_fail(ctx, e, "hipEventCreateWithFlags");
   }
   TSDR_HIP(ctx, hipEventRecord(ctx->wait_ev, s));
-  return wait_event(ctx, ctx->wait_ev, what);
+  const int rc = wait_event(ctx, ctx->wait_ev, what);
+  if (!rc && s == ctx->stream) ctx->pipe.busy.host_saw_stream();   // (lanes that pipe_drain ordered into this stream are idle now)
+  return rc;
 }
 
 static hipEvent_t take_event(tsdr_ctx *ctx) {
@@ -153,6 +160,12 @@ void *tsdr_ctx::scratch(int slot, size_t bytes) {
   return b.p;
 }
 
+// contexts alive per device (loop_policy.h:overlap_allowed); devices past the table count as shared
+static std::atomic<int> g_live[64];
+namespace tsdr {
+int contexts_on_device(int device) { return device >= 0 && device < 64 ? g_live[device].load(std::memory_order_relaxed) : 2; }
+}
+
 extern "C" {
 
 const char *tsdr_version(void) { return "tempest-hip 0.1 (gfx950)"; }
@@ -210,12 +223,15 @@ tsdr_ctx *tsdr_create(int device) {
   if (const char *e = getenv("TSDR_PIPE_EXT_EVENT")) ctx->opt_pipe_ext_event = atoi(e) != 0;
   if (const char *e = getenv("TSDR_PIPE_LANES")) ctx->opt_pipe_lanes = atoi(e) == 3 ? 3 : 2;
   if (const char *e = getenv("TSDR_WAIT_MS")) ctx->opt_wait_ms = atoi(e) < 0 ? 0 : atoi(e);
+  if (const char *e = getenv("TSDR_FRAMES_OVERLAP")) ctx->opt_frames_overlap = atoi(e) <= 0 ? 0 : atoi(e) >= 2 ? 2 : 1;
   if (const char *e = getenv("TSDR_BETA_WAVES")) ctx->opt_beta_waves = atoi(e) == 8 ? 8 : 4;
+  if (device < 64) g_live[device].fetch_add(1, std::memory_order_relaxed);
   return ctx;
 }
 
 void tsdr_destroy(tsdr_ctx *ctx) {
   if (!ctx) return;
+  if (ctx->device < 64) g_live[ctx->device].fetch_sub(1, std::memory_order_relaxed);   // (an abandoned context counts no longer either)
   (void)hipSetDevice(ctx->device);
   (void)tsdr::pipe_drain(ctx);
   if (tsdr::wait_stream(ctx, ctx->stream, "tsdr_destroy") || tsdr::pipe_sync_lanes(ctx)) {
@@ -319,6 +335,8 @@ int tsdr_set_option(tsdr_ctx *ctx, const char *name, int value) {
   }
   else if (!strcmp(name, "pipe_measure")) { if (int rc = tsdr::pipe_drain(ctx)) return rc; if (value) ctx->pipe.tuner.measure_now(); }
   else if (!strcmp(name, "pipe_ext_event")) ctx->opt_pipe_ext_event = value != 0;
+  // (calls already enqueued keep the lanes they are on; the next tsdr_frames_d is ordered behind them either way)
+  else if (!strcmp(name, "frames_overlap")) { if (int rc = tsdr::pipe_drain(ctx)) return rc; ctx->opt_frames_overlap = value <= 0 ? 0 : value >= 2 ? 2 : 1; }
   else if (!strcmp(name, "wait_ms")) ctx->opt_wait_ms = value < 0 ? 0 : value;
   else if (!strcmp(name, "sync_guard_ppb")) {
     if (value < 0 || value > 100000000) return tsdr::set_err(ctx, TSDR_EINVAL, "sync_guard_ppb must be in [0, 1e8]");
@@ -458,6 +476,7 @@ int tsdr_dev_free(tsdr_ctx *ctx, void *dev) {
 int tsdr_upload(tsdr_ctx *ctx, void *dst_dev, const void *src_host, size_t bytes) {
   if (!ctx || (bytes && (!dst_dev || !src_host))) return TSDR_EINVAL;
   if (bytes) {
+    if (int rc = tsdr::run_fence(ctx)) return rc;   // (dst_dev may be a buffer a tsdr_frames_d call still reads or writes on a lane)
     TSDR_HIP(ctx, hipMemcpyAsync(dst_dev, src_host, bytes, hipMemcpyHostToDevice, ctx->stream));
     { int _w = tsdr::wait_stream(ctx, ctx->stream, __func__); if (_w) return _w; }
   }
@@ -467,6 +486,7 @@ int tsdr_upload(tsdr_ctx *ctx, void *dst_dev, const void *src_host, size_t bytes
 int tsdr_download(tsdr_ctx *ctx, void *dst_host, const void *src_dev, size_t bytes) {
   if (!ctx || (bytes && (!dst_host || !src_dev))) return TSDR_EINVAL;
   if (bytes) {
+    if (int rc = tsdr::run_fence(ctx)) return rc;   // (src_dev may be what a tsdr_frames_d call's tail is still writing on a lane)
     TSDR_HIP(ctx, hipMemcpyAsync(dst_host, src_dev, bytes, hipMemcpyDeviceToHost, ctx->stream));
     { int _w = tsdr::wait_stream(ctx, ctx->stream, __func__); if (_w) return _w; }
   }
@@ -475,12 +495,15 @@ int tsdr_download(tsdr_ctx *ctx, void *dst_host, const void *src_dev, size_t byt
 
 int tsdr_timer_start(tsdr_ctx *ctx) {
   if (!ctx) return TSDR_EINVAL;
+  // (the pair brackets what the caller enqueues between the two calls: buffers whose tails are still on the lanes come first)
+  if (int rc = tsdr::pipe_drain(ctx)) return rc;
   TSDR_HIP(ctx, hipEventRecord(ctx->t0, ctx->stream));
   return TSDR_OK;
 }
 
 int tsdr_timer_stop(tsdr_ctx *ctx, double *ms) {
   if (!ctx || !ms) return TSDR_EINVAL;
+  if (int rc = tsdr::pipe_drain(ctx)) return rc;
   TSDR_HIP(ctx, hipEventRecord(ctx->t1, ctx->stream));
   { int _w = tsdr::wait_event(ctx, ctx->t1, __func__); if (_w) return _w; }
   float f = 0.f;

@@ -1230,6 +1230,7 @@ static int fft_launch(tsdr_ctx *ctx, const float2 *in, float2 *out, float2 *mid,
   pl.user = &L;
   plan(pl);
   if (pl.status) return pl.err[0] ? set_err(ctx, pl.status, "%s", pl.err) : pl.status;
+  if (int rf = run_fence(ctx)) return rf;   // (the copy below precedes the first launch)
   if (pl.copy_bytes && in != out) TSDR_HIP(ctx, hipMemcpyAsync(out, in, pl.copy_bytes, hipMemcpyDeviceToDevice, ctx->stream));
   return TSDR_OK;
 }

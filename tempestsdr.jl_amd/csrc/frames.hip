@@ -8,7 +8,10 @@
 //
 // The two sequential couplings of the reference loop -- s_y lags one vsync call, and the IIR
 // recurrence -- are resolved inside shift_iir/sync_publish, so everything upstream is parallel
-// over frames.  No host synchronisation happens in the _d entry point.
+// over frames.  The _d entry points only enqueue -- on the context's stream, or (tsdr_frames_d / _sc16_d / _iq_d in the default
+// mode: frames_run) the tail of a buffer on an internal stream beside the next call's image launch.  The host waits, within the
+// bound of wait_stream, only where a workspace grows, the configuration changes while buffers are in flight, or a call fails
+// after launching on an internal stream.
 #include <algorithm>
 #include <chrono>
 #include <string>
@@ -58,6 +61,15 @@ static int frames_check(tsdr_ctx *ctx, tsdr_sync *sync, int do_align) {
   if (b[1] != TSDR_RENDER_H / 4 || b[3] != TSDR_RENDER_W / 4) return set_err(ctx, TSDR_EINVAL, "SyncXY state must be 600x800");
   return TSDR_OK;
 }
+
+// Which arrangement of the lanes a buffer is submitted in (frames_submit): the measured choice of tsdr_frames_submit_*, or
+// the fixed image lane + tail lane of tsdr_frames_d (frames_run) -- kCands[kRunCand].  Only an arrangement with ONE image lane
+// is legal there: a caller may hand every call the same raster_out, and image launches on one lane write it in call order.
+// Two streams of normal priority, not the high-priority tail lane of kCands[1]: in a process whose first streams are the
+// context's own and these (the benchmark's), the priority lane measured 0.95-0.99 of one stream per call and this pair
+// 1.03-1.05 (NOTEBOOK "tsdr_frames_d on the lanes").
+enum class LanePolicy { Measured, ImageAndTail };
+constexpr int kRunCand = 2;
 
 // ---- sync guard (guard.h) ---------------------------------------------------------------------------------------
 // FAST-mode calls with do_align: k_beta reports every workgroup's top-2 column maxima, and ONE more launch (k_guard,
@@ -277,9 +289,14 @@ int tsdr_frames_combine_d(tsdr_ctx *ctx, tsdr_sync *sync, const float *img, cons
                      do_align ? sync_idx : nullptr, nullptr);
 }
 
-// run one buffer: both parts, through workspace images and keys
+static int frames_submit(tsdr_ctx *ctx, tsdr_sync *sync, const float *iq, IqFmt fmt, size_t nEch, size_t S, int y_t, int x_t, float alpha,
+                         int do_align, float *imageOut_state, float *frames_out, float *raster_out, int *sync_idx, int *n_frames, LanePolicy policy);
+
+// run one buffer: both parts, through workspace images and keys -- or, where the call may overlap (`may_overlap`: not the
+// host-pointer form, whose copies follow on the context's stream at once), as one submission on the image lane + tail lane
 static int frames_run(tsdr_ctx *ctx, tsdr_sync *sync, const float *iq, IqFmt fmt, size_t nEch, size_t S, int y_t, int x_t, float alpha,
-                      int do_align, float *imageOut_state, float *frames_out, float *raster_out, int *sync_idx, int *n_frames) {
+                      int do_align, float *imageOut_state, float *frames_out, float *raster_out, int *sync_idx, int *n_frames,
+                      bool may_overlap = true) {
   if (!ctx || !imageOut_state || S == 0 || y_t <= 0 || x_t <= 0) return TSDR_EINVAL;
   if (int rc = sync_f32_check(ctx, sync)) return rc;
   TSDR_PTR_ALIGNED(ctx, "frames", iq, iq_bytes(fmt));
@@ -289,6 +306,15 @@ static int frames_run(tsdr_ctx *ctx, tsdr_sync *sync, const float *iq, IqFmt fmt
   TSDR_PTR_ALIGNED(ctx, "frames", sync_idx, 4);
   const size_t nb = nEch / S;
   if (nb > (size_t)1 << 20) return set_err(ctx, TSDR_EINVAL, "too many frames in one buffer");
+  // The tail of buffer k (statistics, guard, shift + IIR: 50 of C2's 165 us, the memory system idle for half of them) beside
+  // the image launch of buffer k + 1: arrangement A below, fixed -- nothing is measured, no call spends buffers on trials.
+  // Not where the caller reads launches one by one (profiling), not in TSDR_EXACT (the bit-for-bit leg stays on one stream),
+  // and not on an adopted stream, whose owner orders their own work against this call by stream order alone.  Not beside another
+  // context on the device either, unless asked for ("frames_overlap" 2): two contexts fill each other's gaps already, and four
+  // lanes beside two context streams on four hardware queues measured 0.96-0.97 of two plain streams (bench: two_streams).
+  if (may_overlap && overlap_allowed(ctx->opt_frames_overlap, contexts_on_device(ctx->device)) && !ctx->prof_on && ctx->precision == TSDR_FAST && ctx->own_stream && nb > 0)
+    return frames_submit(ctx, sync, iq, fmt, nEch, S, y_t, x_t, alpha, do_align, imageOut_state, frames_out, raster_out, sync_idx, n_frames,
+                         LanePolicy::ImageAndTail);
   if (ctx->pipe.n) {  // buffers submitted through the pipeline come first (SyncXY and imageOut state are sequential)
     int rcd = pipe_drain(ctx);
     if (rcd) return rcd;
@@ -296,7 +322,7 @@ static int frames_run(tsdr_ctx *ctx, tsdr_sync *sync, const float *iq, IqFmt fmt
   float *img = (float *)ctx->scratch(WS_IMG, (nb ? nb : 1) * kNpx * 4);
   unsigned long long *keys = (unsigned long long *)ctx->scratch(WS_KEYS, (nb ? nb : 1) * 2 * 8);
   if (!img || !keys) return TSDR_ENOMEM;
-  // (Measured and closed: cutting ONE buffer into frame chunks whose tails run beside the next chunk's image launch -- round 1:
+  // (The sequential arrangement.  Measured and closed: cutting ONE buffer into frame chunks whose tails run beside the next chunk's image launch -- round 1:
   // 0.245 -> 0.271 ms with 2 chunks; round 5 on the pipeline's lanes: 0.162 -> 0.247 ms (2), 0.266 (3); raster-free 0.086 ->
   // 0.130 / 0.164.  Half-size image launches fill the machine worse and the chain of tails is exposed at the call's end.
   // The overlap lives ACROSS buffers: frames_submit.)
@@ -379,12 +405,22 @@ int pipe_drain(tsdr_ctx *ctx) {
     TSDR_HIP(ctx, hipStreamWaitEvent(ctx->stream, P.ev_tail[P.last_slot], 0));
   }
   P.n = 0;
+  P.busy.drain();
   return TSDR_OK;
 }
 
-// host-side wait for the lanes (workspace reallocation, destruction, a change of arrangement)
+// host-side wait for the lanes (workspace reallocation, destruction, a change of arrangement): for those that may hold work
+// (Pipeline::busy).  A lane the host already saw complete is not touched: it may share a hardware queue with a stream that
+// is held -- the context's own, behind a caller's unfinished work -- and a marker on it would wait for that stream, so a
+// tsdr_frames_d call with a new SyncXY or geometry would wait where it only ever enqueued.
 int pipe_sync_lanes(tsdr_ctx *ctx) {
-  for (auto l : ctx->pipe.pool) if (l) { int rc = wait_stream(ctx, l, "pipeline lane"); if (rc) return rc; }
+  Pipeline &P = ctx->pipe;
+  for (int i = 0; i < kPoolN + kPoolH; ++i) {
+    if (!P.pool[i] || !P.busy.busy(i)) continue;
+    int rc = wait_stream(ctx, P.pool[i], "pipeline lane");
+    if (rc) return rc;
+    P.busy.lane_idle(i);
+  }
   return TSDR_OK;
 }
 
@@ -399,7 +435,7 @@ static int pipe_quiesce(tsdr_ctx *ctx) {
 struct SubmitGuard {
   tsdr_ctx *ctx; bool ok = false;
   explicit SubmitGuard(tsdr_ctx *c) : ctx(c) {}
-  ~SubmitGuard() { if (!ok) pipe_sync_lanes(ctx); }
+  ~SubmitGuard() { if (!ok) { ctx->pipe.busy.failed(); pipe_sync_lanes(ctx); } }
 };
 
 struct LaneScope {  // launches of this scope go to a lane: the one piece of ambient state the steps read (TSDR_LAUNCH)
@@ -421,18 +457,23 @@ static int fence_inputs(tsdr_ctx *ctx, hipStream_t lane) {
 
 extern "C" {
 
-// submit one buffer to the pipeline
+// submit one buffer to the pipeline.  policy: who chooses the arrangement.  Measured -- the tuner (tsdr_frames_submit_*);
+// ImageAndTail -- nobody: kRunCand, the tuner neither consulted nor advanced (frames_run).  A change of policy between two
+// calls on one context is a change of arrangement: the lanes run empty first.
 static int frames_submit(tsdr_ctx *ctx, tsdr_sync *sync, const float *iq, IqFmt fmt, size_t nEch, size_t S, int y_t, int x_t, float alpha,
-                         int do_align, float *imageOut_state, float *frames_out, float *raster_out, int *sync_idx, int *n_frames) {
+                         int do_align, float *imageOut_state, float *frames_out, float *raster_out, int *sync_idx, int *n_frames,
+                         LanePolicy policy) {
+  const bool run = policy == LanePolicy::ImageAndTail;
+  const char *const fn = run ? "frames" : "frames_submit";
   if (!ctx || !imageOut_state || S == 0 || y_t <= 0 || x_t <= 0) return TSDR_EINVAL;
   if (nEch && !iq) return TSDR_EINVAL;
   int rc = frames_check(ctx, sync, do_align);
   if (rc) return rc;
-  TSDR_PTR_ALIGNED(ctx, "frames_submit", iq, iq_bytes(fmt));
-  TSDR_PTR_ALIGNED(ctx, "frames_submit", imageOut_state, 4);
-  TSDR_PTR_ALIGNED(ctx, "frames_submit", frames_out, 4);
-  TSDR_PTR_ALIGNED(ctx, "frames_submit", raster_out, 4);
-  TSDR_PTR_ALIGNED(ctx, "frames_submit", sync_idx, 4);
+  TSDR_PTR_ALIGNED(ctx, fn, iq, iq_bytes(fmt));
+  TSDR_PTR_ALIGNED(ctx, fn, imageOut_state, 4);
+  TSDR_PTR_ALIGNED(ctx, fn, frames_out, 4);
+  TSDR_PTR_ALIGNED(ctx, fn, raster_out, 4);
+  TSDR_PTR_ALIGNED(ctx, fn, sync_idx, 4);
   const size_t nb = nEch / S;
   if (nb > (size_t)1 << 20) return set_err(ctx, TSDR_EINVAL, "too many frames in one buffer");
   if (n_frames) *n_frames = (int)nb;
@@ -445,16 +486,20 @@ static int frames_submit(tsdr_ctx *ctx, tsdr_sync *sync, const float *iq, IqFmt 
   PipeKey key;
   key.nb = nb; key.S = S; key.y_t = y_t; key.x_t = x_t; key.raster = raster_out ? 1 : 0; key.prec = ctx->precision;
   key.align = do_align ? 1 : 0; key.sync = (const void *)sync; key.iq_kind = fmt.kind;
-  P.tuner.select(key, opts);
-  if (P.tuner.trial_complete()) {   // (a wait that fails leaves the trial complete: the next submission tries again)
+  if (!run) P.tuner.select(key, opts);
+  if (!run && P.tuner.trial_complete()) {   // (a wait that fails leaves the trial complete: the next submission tries again)
     rc = pipe_quiesce(ctx);
+    if (rc) return rc;
+    // (the trial's last timing event is a marker BEHIND its last tail: a lane the host saw complete through the context's
+    // stream is not waited for above, and may still be a marker short)
+    rc = wait_event(ctx, P.tune_ev[kTrial - 1], "pipeline trial");
     if (rc) return rc;
     float ms = 0.f;
     const bool okev = hipEventElapsedTime(&ms, P.tune_ev[2], P.tune_ev[kTrial - 1]) == hipSuccess;
     (void)hipGetLastError();
     P.tuner.record_trial(okev, ms);
   }
-  const int cand = P.tuner.candidate();
+  const int cand = run ? kRunCand : P.tuner.candidate();
   const PipeCand &pc = kCands[cand];
   const bool sym = pc.sym != 0;
   const int nl = pc.nl;
@@ -463,7 +508,7 @@ static int frames_submit(tsdr_ctx *ctx, tsdr_sync *sync, const float *iq, IqFmt 
   // these (GUI.jl's FLAG_CONFIG_UPDATE, its y_t / x_t corrections, a trial boundary of the measurement) would compute slot
   // offsets that overlap what an in-flight tail on another lane still reads -- the pipeline runs empty first (a
   // configuration change, not a steady-state event).
-  if (!(P.key == key) || P.cand_now != cand) {
+  if (!(P.key == key) || P.cand_now != cand || P.from_run != run) {
     rc = pipe_quiesce(ctx);
     if (rc) return rc;
     for (bool &u : P.ev_tail_used) u = false;
@@ -475,6 +520,8 @@ static int frames_submit(tsdr_ctx *ctx, tsdr_sync *sync, const float *iq, IqFmt 
   }
   P.key = key;
   P.cand_now = cand;
+  P.from_run = run;
+  if (!run) P.cand_submit = cand;
   // symmetric: whole buffers alternate between nl equal lanes; slot = position in the rotation
   const int slot = (int)(P.seq % (unsigned long long)(sym ? nl : NS));
   // the lanes of the two steps: equal lanes [0], [1], [3] take a whole buffer; else image lane [0], tail lane [2]
@@ -486,6 +533,9 @@ static int frames_submit(tsdr_ctx *ctx, tsdr_sync *sync, const float *iq, IqFmt 
   FrameJob j{ctx, sync, iq, fmt, S, y_t, x_t, (int)nb, do_align, alpha, img3 + (size_t)slot * nb * kNpx, keys3 + (size_t)slot * nb * 2,
              raster_out, imageOut_state, frames_out, sync_idx, slot, NS, lane_img, lane_tail};
   SubmitGuard submitted(ctx);
+  unsigned lanes_used = 0;
+  for (int i = 0; i < (sym ? nl : 2); ++i) lanes_used |= 1u << pc.s[i];
+  P.busy.submit(lanes_used);   // (from here on the arrangement's streams may hold work)
   rc = job_prepare(j);
   if (rc) return rc;
   const hipStream_t tail_stream = P.lane[lane_tail];
@@ -523,7 +573,7 @@ static int frames_submit(tsdr_ctx *ctx, tsdr_sync *sync, const float *iq, IqFmt 
       if (rc) return rc;
     }
   }
-  const int timed = P.tuner.submitted(opts);   // a trial's buffers 2 and kTrial - 1 carry a timing event behind their tails
+  const int timed = run ? -1 : P.tuner.submitted(opts);   // a trial's buffers 2 and kTrial - 1 carry a timing event behind their tails
   if (timed >= 0) TSDR_HIP(ctx, hipEventRecord(P.tune_ev[timed], tail_stream));
   P.ev_tail_used[slot] = true;
   P.last_slot = slot;
@@ -535,7 +585,7 @@ static int frames_submit(tsdr_ctx *ctx, tsdr_sync *sync, const float *iq, IqFmt 
 
 int tsdr_frames_pipeline_info(tsdr_ctx *ctx, int *trials_left, int *chosen, float *ms_per_buffer, int cap, char *text, size_t text_cap) {
   if (!ctx || cap < 0 || (cap && !ms_per_buffer)) return TSDR_EINVAL;
-  const PipeInfo r = ctx->pipe.tuner.info(pipe_opts(ctx), ctx->pipe.cand_now);
+  const PipeInfo r = ctx->pipe.tuner.info(pipe_opts(ctx), ctx->pipe.cand_submit);
   if (trials_left) *trials_left = r.trials_left;
   if (chosen) *chosen = r.chosen;
   for (int c = 0; c < cap && c < kTuneCands; ++c) ms_per_buffer[c] = r.ms[c];
@@ -546,7 +596,7 @@ int tsdr_frames_pipeline_info(tsdr_ctx *ctx, int *trials_left, int *chosen, floa
 int tsdr_frames_submit_d(tsdr_ctx *ctx, tsdr_sync *sync, const float *iq, size_t nEch, size_t S, int y_t, int x_t,
                          float alpha, int do_align, float *imageOut_state, float *frames_out, float *raster_out,
                          int *sync_idx, int *n_frames) {
-  return frames_submit(ctx, sync, iq, IqFmt{}, nEch, S, y_t, x_t, alpha, do_align, imageOut_state, frames_out, raster_out, sync_idx, n_frames);
+  return frames_submit(ctx, sync, iq, IqFmt{}, nEch, S, y_t, x_t, alpha, do_align, imageOut_state, frames_out, raster_out, sync_idx, n_frames, LanePolicy::Measured);
 }
 
 // ---- int16 I/Q input (what SDR hardware delivers, AtomicAbstractSDRs.jl:284-306 before its conversion): the same loop with
@@ -562,7 +612,7 @@ int tsdr_frames_submit_sc16_d(tsdr_ctx *ctx, tsdr_sync *sync, const int16_t *iq,
                               int x_t, float alpha, int do_align, float *imageOut_state, float *frames_out, float *raster_out,
                               int *sync_idx, int *n_frames) {
   return frames_submit(ctx, sync, reinterpret_cast<const float *>(iq), IqFmt{IQK_SC16, scale}, nEch, S, y_t, x_t, alpha, do_align,
-                       imageOut_state, frames_out, raster_out, sync_idx, n_frames);
+                       imageOut_state, frames_out, raster_out, sync_idx, n_frames, LanePolicy::Measured);
 }
 
 // ---- any input format (TSDR_IQ_*): ComplexF32, int16 pairs, or the 8-bit pairs of HackRF / UHD sc8 (int8) and RTL-SDR
@@ -593,7 +643,7 @@ int tsdr_frames_submit_iq_d(tsdr_ctx *ctx, tsdr_sync *sync, const void *iq, int 
   IqFmt f;
   if (int rc = iq_fmt_arg(ctx, iq, iq_fmt, scale, &f)) return rc;
   return frames_submit(ctx, sync, reinterpret_cast<const float *>(iq), f, nEch, S, y_t, x_t, alpha, do_align, imageOut_state, frames_out,
-                       raster_out, sync_idx, n_frames);
+                       raster_out, sync_idx, n_frames, LanePolicy::Measured);
 }
 
 int tsdr_frames_flush(tsdr_ctx *ctx) {
@@ -615,7 +665,7 @@ int tsdr_frames(tsdr_ctx *ctx, tsdr_sync *sync, const float *iq, size_t nEch, si
     return TSDR_ENOMEM;
   if (nEch) TSDR_HIP(ctx, hipMemcpyAsync(d_iq, iq, nEch * 8, hipMemcpyHostToDevice, ctx->stream));
   TSDR_HIP(ctx, hipMemcpyAsync(d_state, imageOut_state, npx * 4, hipMemcpyHostToDevice, ctx->stream));
-  int rc = tsdr_frames_d(ctx, sync, d_iq, nEch, S, y_t, x_t, alpha, do_align, d_state, d_frames, d_raster, d_idx, n_frames);
+  int rc = frames_run(ctx, sync, d_iq, IqFmt{}, nEch, S, y_t, x_t, alpha, do_align, d_state, d_frames, d_raster, d_idx, n_frames, false);
   if (rc) return rc;
   TSDR_HIP(ctx, hipMemcpyAsync(imageOut_state, d_state, npx * 4, hipMemcpyDeviceToHost, ctx->stream));
   if (d_frames && nb) TSDR_HIP(ctx, hipMemcpyAsync(frames_out, d_frames, nb * npx * 4, hipMemcpyDeviceToHost, ctx->stream));

@@ -213,4 +213,29 @@ struct GuardRoute {
   void set_auto(bool on) { if (!on) exact_now = false; }   // "sync_guard_auto"
 };
 
+// Which of the pipeline's pool streams may still hold work, as far as the host knows (bit i: pool[i]).  A host wait for the
+// lanes (frames.hip:pipe_sync_lanes) touches only these: an idle stream can share a hardware queue with a stream that is held,
+// and a marker on it would wait for that one.  Transitions, in the order frames.hip makes them:
+//   submit(mask)       a submission is about to launch on the streams of its arrangement
+//   failed()           ... and returned half-way: its launches are behind no event that a later drain would order
+//   drain()            pipe_drain ordered the context's stream behind the latest complete submission's tail
+//   host_saw_stream()  a host wait for the context's stream completed: after a drain with nothing submitted since, and no
+//                      failed submission outstanding, every lane is idle
+//   lane_idle(i)       a host wait for pool[i] completed; with the last one a failed submission's launches are done as well
+struct LaneBusy {
+  unsigned mask = 0;
+  bool drained = false, unordered = false;
+  void submit(unsigned m) { mask |= m; drained = false; }
+  void failed() { unordered = true; }
+  void drain() { drained = true; }
+  void host_saw_stream() { if (drained && !unordered) mask = 0; }
+  bool busy(int i) const { return (mask >> i & 1u) != 0; }
+  void lane_idle(int i) { mask &= ~(1u << i); if (!mask) unordered = false; }
+};
+
+// Contexts alive per device: tsdr_frames_d takes the lanes only while its context is the device's only one (two contexts on one
+// GPU fill each other's gaps already, and their lanes get in each other's way: NOTEBOOK "tsdr_frames_d on the lanes"), unless
+// option "frames_overlap" is 2.  overlap_allowed: opt 0 never, 1 alone on the device, 2 always.
+inline bool overlap_allowed(int opt, int contexts_on_device) { return opt >= 2 || (opt == 1 && contexts_on_device <= 1); }
+
 }  // namespace tsdr

@@ -97,6 +97,7 @@ int tsdr_resize1d_f64_d(tsdr_ctx *ctx, const double *sig, size_t n_in, size_t n_
   if (!ctx || (n_out && (!sig || !out))) return TSDR_EINVAL;
   if (n_out == 0) return TSDR_OK;
   if (n_in == n_out) {
+    if (int rf = run_fence(ctx)) return rf;   // (a copy, not a launch)
     TSDR_HIP(ctx, hipMemcpyAsync(out, sig, n_in * 8, hipMemcpyDeviceToDevice, ctx->stream));
     return TSDR_OK;
   }
@@ -120,6 +121,7 @@ int tsdr_resize2d_f64_d(tsdr_ctx *ctx, const double *img, int h_in, int w_in, in
   if (!ctx || !img || !out) return TSDR_EINVAL;
   if (h_in <= 0 || w_in <= 0 || h_out <= 0 || w_out <= 0) return set_err(ctx, TSDR_EINVAL, "resize2d: sizes must be positive");
   if (h_in == h_out && w_in == w_out) {
+    if (int rf = run_fence(ctx)) return rf;   // (a copy, not a launch)
     TSDR_HIP(ctx, hipMemcpyAsync(out, img, (size_t)h_in * w_in * 8, hipMemcpyDeviceToDevice, ctx->stream));
     return TSDR_OK;
   }

@@ -150,6 +150,7 @@ int tsdr_iq_expand_d(tsdr_ctx *ctx, const void *iq, int iq_fmt, float scale, siz
   TSDR_PTR_ALIGNED(ctx, "iq_expand", cf32_out, 8);
   if (n == 0) return TSDR_OK;
   if (iq_fmt == TSDR_IQ_CF32) {   // the samples themselves
+    if (int rc = run_fence(ctx)) return rc;   // (a copy, not a launch: ordered behind tsdr_frames_d calls like one)
     if ((const void *)cf32_out != iq) TSDR_HIP(ctx, hipMemcpyAsync(cf32_out, iq, n * 8, hipMemcpyDeviceToDevice, ctx->stream));
     return TSDR_OK;
   }
@@ -283,7 +284,9 @@ int tsdr_ring_take_d(tsdr_ring *r, int timeout_ms, float **dev_iq) {
     if (!staged) { r->dma_slot[d] = slot; r->staging[d] = true; }
   }
   // the device buffer about to be refilled further down (the other one) was handed out two takes ago: the
-  // caller's stream has to be past its consumers before the DMA may overwrite it
+  // caller's stream has to be past its consumers before the DMA may overwrite it (a tsdr_frames_d call that consumes one on
+  // the lanes is ordered into the caller's stream first)
+  if (int rc = run_fence(ctx)) return rc;
   TSDR_HIP(ctx, hipEventRecord(r->freed, ctx->stream));
   TSDR_HIP(ctx, hipStreamWaitEvent(r->copy, r->freed, 0));
   if (!staged) {

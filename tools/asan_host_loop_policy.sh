@@ -12,4 +12,7 @@ trap 'rm -rf "$T"' EXIT
 "$T/loop_policy" > "$T/out.txt"
 "$T/loop_policy" eviction > /dev/null
 cmp "$T/out.txt" "$R/tests/golden/loop_policy_v1.txt"
+/opt/rocm/bin/hipcc -x c++ -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+  -fno-omit-frame-pointer "$R/tools/host_plan/lane_busy_main.cpp" -o "$T/lane_busy"
+"$T/lane_busy" > /dev/null   # (the pipeline's lane bookkeeping: LaneBusy, overlap_allowed)
 echo "loop policy: $(wc -l < "$T/out.txt") steps, equal to tests/golden/loop_policy_v1.txt, no sanitizer report"
