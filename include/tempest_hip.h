@@ -566,6 +566,8 @@ int tsdr_frames_pipeline_info(tsdr_ctx *ctx, int *trials_left, int *chosen, floa
 #include "tempest_hip_fold.h"
 /* phase-coherent frame folding: frames de-rotated by the carrier's advance per frame and summed as complex samples, and the carrier scan */
 #include "tempest_hip_cfold.h"
+/* coherent stacking across buffers: the fold's picture kept complex, turned onto a complex state (given phase, or phase lock) and blended */
+#include "tempest_hip_cstack.h"
 
 /* ---- host -> device staging ring ---------------------------------------
  * The consumer side of AtomicCircularBuffer (AtomicAbstractSDRs.jl:64-190): `depth` slots of nEch samples in

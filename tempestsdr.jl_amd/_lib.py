@@ -269,6 +269,14 @@ _SIGS_CFOLD = {
 }
 CFOLD_MAX_TRIALS, CFOLD_STAGE_MAX = 4096, 120  # TSDR_CFOLD_*
 
+# include/tempest_hip_cstack.h (included after tempest_hip_cfold.h): coherent stacking across buffers -- a complex fold state, phase lock
+_CSTACK = _FOLD + [C.c_double, C.c_double, C.c_double] + _GEOM + [C.c_float, C.c_int, vp, vp, vp]  # T, kappa, phi, ..., alpha, mode, zstate, mag, info
+_SIGS_CSTACK = {
+    "tsdr_cstack_iq_d": (C.c_int, list(_CSTACK)),
+    "tsdr_cstack_iq": (C.c_int, list(_CSTACK)),
+}
+CSTACK_GIVEN, CSTACK_LOCK, CSTACK_INFO = 0, 1, 8  # TSDR_CSTACK_*
+
 
 def exported_names():
     """Every symbol include/tempest_hip.h declares (kept in sync by tests/test_abi.py)."""
@@ -310,6 +318,11 @@ def exported_names_cfold():
     return sorted(_SIGS_CFOLD)
 
 
+def exported_names_cstack():
+    """Every symbol include/tempest_hip_cstack.h declares (kept in sync by tests/test_cstack_host.py)."""
+    return sorted(_SIGS_CSTACK)
+
+
 def _share_torch_hip_runtime():
     """PyTorch-ROCm wheels bundle their own libamdhip64/libhsa-runtime64.  Two HIP runtimes in one
     process cannot both own the GPU (whichever initialises second sees no device), and the dynamic
@@ -336,7 +349,8 @@ def load():
             "(there is no CPU fallback)")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(_SIGS.items()) + list(_SIGS_IQ.items()) + list(_SIGS_CPLX.items()) + list(_SIGS_HIRES.items()) + \
-            list(_SIGS_REGISTER.items()) + list(_SIGS_DISPLAY.items()) + list(_SIGS_FOLD.items()) + list(_SIGS_CFOLD.items()):
+            list(_SIGS_REGISTER.items()) + list(_SIGS_DISPLAY.items()) + list(_SIGS_FOLD.items()) + list(_SIGS_CFOLD.items()) + \
+            list(_SIGS_CSTACK.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI is incomplete
         fn.restype = res
         fn.argtypes = args

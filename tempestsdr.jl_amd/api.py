@@ -665,6 +665,21 @@ class Context:
         """-> (kappa_hat mod 1, last_dkappa, scores): the carrier's advance per frame in turns, by a coarse-to-fine carrier scan"""
         return _cfold.refine_carrier(self, iq_d, fmt, scale, n, t0, T, n_frames, y_t, x_t, oversample, half, levels, shrink)
 
+    # -- coherent stacking across buffers: a complex fold state, phase lock (include/tempest_hip_cstack.h; cstack.py) ----------------
+    def cstack(self, iq, t0, T, kappa, phi, n_frames, y_t, x_t, alpha=0.0, mode="given", zstate=None, fmt="cf32", scale=1.0):
+        """-> (zstate complex64 (y_t, x_t), mag float32 (y_t, x_t), info float64[8]): alpha * zstate + (1 - alpha) * conj(q) * Z, Z the
+        complex mean of n_frames frames turned by -(phi + f * kappa) turns; q = 1 ("given") or the measured turn ("lock")"""
+        return _cstack.cstack(self, iq, t0, T, kappa, phi, n_frames, y_t, x_t, alpha, mode, zstate, fmt, scale)
+
+    def cstack_d(self, iq, fmt, scale, n, t0, T, kappa, phi, n_frames, y_t, x_t, alpha, mode, zstate, mag=None, info=None):
+        """device-pointer form of cstack (mag, info: optional device pointers): enqueues on the context's stream and returns"""
+        return _cstack.cstack_d(self, iq, fmt, scale, n, t0, T, kappa, phi, n_frames, y_t, x_t, alpha, mode, zstate, mag, info)
+
+    @staticmethod
+    def cstack_plan(n, t0, T, kappa, phi, theta=0.0):
+        """-> (F, next_t0, next_phi): fold_plan, and the carrier phase carried over the F frames and the straddling one"""
+        return _cstack.cstack_plan(n, t0, T, kappa, phi, theta)
+
 
 def frames_d(ctx, sync, iq, nEch, S, y_t, x_t, alpha, do_align, state, frames_out=None, raster_out=None, sync_idx=None):
     """Device-pointer form of Context.frames: every array argument is a device buffer (torch tensor
@@ -746,6 +761,8 @@ from . import display  # noqa: E402
 from . import fold as _fold  # noqa: E402  (the package exports a function of that name)
 # phase-coherent folding with carrier de-rotation and its carrier scan (the entry points of include/tempest_hip_cfold.h): cfold.py
 from . import cfold as _cfold  # noqa: E402  (the package exports a function of that name)
+# coherent stacking across buffers (the entry points of include/tempest_hip_cstack.h): cstack.py
+from . import cstack as _cstack  # noqa: E402  (the package exports a function of that name)
 
 
 def frames_iq_d(ctx, sync, iq, fmt, scale, nEch, S, y_t, x_t, alpha, do_align, state, frames_out=None, raster_out=None, sync_idx=None,

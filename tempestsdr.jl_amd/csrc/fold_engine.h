@@ -13,10 +13,15 @@
 //                           score-only epilogue -- the pictures never leave the registers; a workgroup writes Fl::NS f64 statistics per
 //                           trial to the workspace (fixed shuffle tree, then wave order), and k_fold_score adds them with one lane per
 //                           trial, in tile order.
+//   k_fold_engine<Fl with stacks, ., ., 1, ., false>   the fold of a flavour that keeps its picture complex: the scan's epilogue
+//                           with one trial, in which Fl::stack also stores the pixel (raster_cstack.hip).
 //
 // A Flavour is a struct of constants and static functions:
 //   Sample, Trial              the staged sample, the trial parameters a launch carries (FoldArgs::tr)
 //   has_weights, NS            whether frame f of trial k has a weight; f64 statistics per trial of the scan
+//   stacks                     the fold keeps its picture complex (raster_cstack.hip): its epilogue is the scan's with one trial, and
+//                              stack(A, s, acc, Ff, at) per pixel -- the pixel's share of the NS statistics and its stores at state
+//                              index `at` -- in place of stat; the tile's NS sums land at part[tile][NS]
 //   kMaxTrials, kStageMax      the header's limits;  kSlot: the scan's workspace;  name: the prefix of its launch's message
 //   tile_p(scan), batch(scan)  host: pixels per tile of the call's staged kernel, and its trials per workgroup
 //   stage(float2) -> Sample    __device__: what is kept of an IQ sample
@@ -191,7 +196,7 @@ __global__ __launch_bounds__(NW * 64) void k_fold_engine(FoldArgs<typename Fl::T
   }
 
   const float Ff = (float)A.F;
-  if constexpr (!SCAN) {
+  if constexpr (!SCAN && !Fl::stacks) {
     if (lane_on) {
       const float alpha = A.alpha, beta = __fsub_rn(1.f, alpha);
 #pragma unroll
@@ -214,8 +219,12 @@ __global__ __launch_bounds__(NW * 64) void k_fold_engine(FoldArgs<typename Fl::T
 #pragma unroll
       for (int i = 0; i < PW; ++i) {
         if (pbeg + i < A.x_t) {
+          if constexpr (SCAN) {
 #pragma unroll
-          for (int j = 0; j < KB; ++j) Fl::stat(st[j], make_float2(accr[i][j], acci[i][j]), Ff);
+            for (int j = 0; j < KB; ++j) Fl::stat(st[j], make_float2(accr[i][j], acci[i][j]), Ff);
+          } else {
+            Fl::stack(A, st[0], make_float2(accr[i][0], acci[i][0]), Ff, (size_t)(pbeg + i) * (size_t)A.y_t + (size_t)l);
+          }
         }
       }
     }
@@ -282,9 +291,13 @@ struct FoldCall {
   double kappa0, dkappa;    // the coherent fold: trial k turns frame f by -f * (kappa0 + k * dkappa) turns
   int n_trials, F, y_t, x_t;
   float alpha;
-  float *state;    // fold (else null)
+  float *state;    // fold (else null); a stacking flavour: the complex state, P (re, im) pairs
   double *score;   // scan (else null)
   bool scan;
+  double phi = 0.0;        // a stacking flavour: the call's start phase in turns, its mode, and its optional outputs
+  int mode = 0;
+  float *mag = nullptr;
+  double *info = nullptr;
   double t_max() const { return T + (double)(n_trials - 1) * dT; }   // the largest trial period
 };
 

@@ -7,6 +7,8 @@
 // a pixel has two f32 sums per trial, and a trial of the scan changes only the weights, so a scan workgroup samples z_f(m) ONCE per
 // frame and accumulates w_{f,k} * z into the sums of a batch of kBatch = 8 trials (blockIdx.y): with the scan's 32-pixel tile that is
 // 4 pixels per lane x 8 trials x 2 = 64 accumulator registers.  A trial's score is the energy sum |Z|^2 of its picture.
+// The device arithmetic (weight, blend, sum, mean) is coherent_ops.h's, shared with raster_cstack.hip.
+#include "coherent_ops.h"
 #include "fold_engine.h"
 
 namespace tsdr {
@@ -24,7 +26,7 @@ struct Coherent {
     double kappa0, dkappa;   // trial k = blockIdx.y * KB + j turns frame f by -f * (kappa0 + k * dkappa) turns
     int n_trials;
   };
-  static constexpr bool has_weights = true;
+  static constexpr bool has_weights = true, stacks = false;
   static constexpr int NS = 1, kMaxTrials = TSDR_CFOLD_MAX_TRIALS, kStageMax = TSDR_CFOLD_STAGE_MAX, kSlot = WS_CFOLD;
   static constexpr const char *name = "cfold";
   static int tile_p(bool scan) { return scan ? kScanP : kFoldTileP; }
@@ -36,20 +38,17 @@ struct Coherent {
   // w_f of tempest_hip_cfold.h (WEIGHT): x = fl64(f * kappa), r = x - floor(x), (f32(cospi(2r)), f32(-sinpi(2r)))
   __device__ static float2 weight(const Trial &t, int f, int k) {
     const double kappa = t.kappa0 + (double)k * t.dkappa;
-    const double x = (double)f * kappa;
-    const double r = x - floor(x);
-    double s, c;
-    sincospi(2.0 * r, &s, &c);
-    return make_float2((float)c, (float)(-s));
+    return coh_weight((double)f * kappa);
   }
-  __device__ static float2 blend(float2 a, float2 b, double d) { return make_float2(fast_blend(a.x, b.x, d), fast_blend(a.y, b.y, d)); }
-  __device__ static void add(float2 &a, float2 z, float2 w) {
-    a.x = __fadd_rn(a.x, __fsub_rn(__fmul_rn(w.x, z.x), __fmul_rn(w.y, z.y)));
-    a.y = __fadd_rn(a.y, __fadd_rn(__fmul_rn(w.x, z.y), __fmul_rn(w.y, z.x)));
+  __device__ static float2 blend(float2 a, float2 b, double d) { return coh_blend(a, b, d); }
+  __device__ static void add(float2 &a, float2 z, float2 w) { coh_add(a, z, w); }
+  __device__ static float pixel(float2 a, float Ff) {
+    const float2 z = coh_mean(a, Ff);
+    return abs_iq_rn(z.x, z.y);
   }
-  __device__ static float pixel(float2 a, float Ff) { return abs_iq_rn(__fdiv_rn(a.x, Ff), __fdiv_rn(a.y, Ff)); }
   __device__ static void stat(double *s, float2 a, float Ff) {
-    const double zr = (double)__fdiv_rn(a.x, Ff), zi = (double)__fdiv_rn(a.y, Ff);
+    const float2 z = coh_mean(a, Ff);
+    const double zr = (double)z.x, zi = (double)z.y;
     s[0] += zr * zr + zi * zi;
   }
   __device__ static double finish(const double *s, double) { return s[0]; }

@@ -724,5 +724,7 @@ include("TempestHIP_display.jl")
 include("TempestHIP_fold.jl")
 # phase-coherent folding with carrier de-rotation: hip_cfold!, hip_cfold_d!, hip_cfold_scan, hip_cfold_scan_d!, refine_carrier (include/tempest_hip_cfold.h)
 include("TempestHIP_cfold.jl")
+# coherent stacking across buffers, a complex fold state and a phase lock: hip_cstack!, hip_cstack_d!, cstack_plan (include/tempest_hip_cstack.h)
+include("TempestHIP_cstack.jl")
 
 end # module

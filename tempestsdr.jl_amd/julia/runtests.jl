@@ -84,4 +84,16 @@ ref = load_all(refdir)
         @test Int.(permutedims(sidx)) == Int.(ref["fr$(tag)_idx"])
         @test relmax(vec(state)[1:499:end], ref["fr$(tag)_state_sub"]) < 6e-7
     end
+    # coherent stacking across buffers: a constant sample folds to itself; the lock turns a buffer that arrives a quarter turn off
+    # back onto the state, the given phase does not
+    let z0 = ComplexF32(0.3, -0.4), T = 40.5, F = 12, iq = fill(ComplexF32(0.3, -0.4), 600)
+        zs = zeros(ComplexF32, 4, 4); mag = zeros(Float32, 4, 4)
+        info = TempestHIP.hip_cstack!(zs, iq, 0.0, T, 0.0, 0.0, F; mag = mag)
+        @test all(abs.(zs .- z0) .<= 1f-6) && all(abs.(mag .- 0.5f0) .<= 1f-6) && info[1] == 0.0 && info[7] == 1.0
+        info = TempestHIP.hip_cstack!(zs, iq, 0.0, T, 0.0, 0.25, F; α = 0.5f0, mode = :lock, mag = mag)
+        @test abs(info[5] + 0.25) <= 1e-6 && abs(info[6] - 1.0) <= 1e-6 && all(abs.(zs .- z0) .<= 1f-6)
+        TempestHIP.hip_cstack!(zs, iq, 0.0, T, 0.0, 0.5, F; α = 0.5f0, mag = mag)
+        @test all(mag .<= 1f-6)
+        @test TempestHIP.cstack_plan(600, 0.0, T, 0.125, 0.5) == (14, 15 * T - 600, 0.375)
+    end
 end
