@@ -147,6 +147,7 @@ int tsdr_get_precision(tsdr_ctx *ctx);
  *                 GPU fill each other's gaps already, and their internal streams cost them 3-4 % -- ; 2: whatever else is alive
  *                 on the device; 0: every call on the context's stream, one launch after the other.  Identical results.
  *                 Setting it first orders the context's stream behind the calls in flight.  TSDR_FRAMES_OVERLAP presets it.
+ *                 tsdr_frames_overlap_stats tells which route the calls took.
  *   "pipe_mode"   how tsdr_frames_submit_d arranges successive buffers on its internal streams: -1 (default) = the measured
  *                 choice (below); 0 = image launches on one stream, every buffer's tail on a second one ("pipe_priority" 1,
  *                 default: of the highest priority); 1 = whole buffers alternate between "pipe_lanes" (2 or 3) equal streams,
@@ -200,6 +201,21 @@ int tsdr_wait_stats(tsdr_ctx *ctx, unsigned long long *timeouts, unsigned long l
  * something that does not complete looks like to the library.  tests/test_bounded_waits_gpu.py uses it to show that the
  * frame-loop entry points and tsdr_synchronize return within their bounds while it lasts. */
 int tsdr_debug_hold_stream(tsdr_ctx *ctx, int ms);
+/* Which route the tsdr_frames_d / _sc16_d / _iq_d calls of this context took (option "frames_overlap"): host-side counters,
+ * nothing is enqueued and nothing synchronised.  *on_lanes = calls (of at least one frame) whose image launch and tail went to
+ * the internal streams; *sequential = those that ran on the context's stream; *why = why the LATEST sequential call did, as
+ * bits: 1 = the option, or another context alive on the device; 2 = profiling is on; 4 = TSDR_EXACT; 8 = an adopted stream
+ * (tsdr_set_stream) -- 0 while no call was sequential.  Any output pointer may be NULL; reset != 0 zeroes all three after
+ * reading.  The chunk calls of tsdr_frames_hires_iq_d count one each; the host-pointer tsdr_frames and the submit, scan,
+ * combine and group routes count in neither. */
+int tsdr_frames_overlap_stats(tsdr_ctx *ctx, unsigned long long *on_lanes, unsigned long long *sequential, unsigned *why, int reset);
+/* Diagnostic: arm a one-shot host-side delay of `ms` milliseconds (0 .. 1000; 0 disarms) for the internal stream that carries a
+ * buffer's tail.  The next tsdr_frames_d / _sc16_d / _iq_d call that takes the internal streams enqueues it behind its image
+ * launch and in front of its vsync statistics: the image launch runs, and everything the tail produces or reads again -- frames,
+ * sync indices, the IIR state, the guard's second look at the IQ and its rewrite of images and rasters -- is `ms` late.  A call
+ * that runs on the context's stream leaves it armed.  Results do not change: whatever follows through the library is ordered
+ * behind the tail as always (tests/test_frames_overlap_callers_gpu.py holds the tail to show exactly that). */
+int tsdr_debug_hold_tail(tsdr_ctx *ctx, int ms);
 
 /* resident buffers for callers without their own device allocator */
 void *tsdr_dev_alloc(tsdr_ctx *ctx, size_t bytes);

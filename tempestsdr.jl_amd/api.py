@@ -127,6 +127,19 @@ class Context:
         self.call("tsdr_wait_stats", C.byref(a), C.byref(b))
         return int(a.value), int(b.value)
 
+    def frames_overlap_stats(self, reset=False):
+        """which route the frames_d / frames_sc16_d / frames_iq_d calls of this context took: (calls on the internal streams,
+        calls on the context's stream, why the latest of those was sequential: bits 1 option or another context on the device,
+        2 profiling, 4 'exact', 8 adopted stream).  Host-side counters -- tsdr_frames_overlap_stats"""
+        a, b, w = C.c_ulonglong(0), C.c_ulonglong(0), C.c_uint(0)
+        self.call("tsdr_frames_overlap_stats", C.byref(a), C.byref(b), C.byref(w), int(bool(reset)))
+        return int(a.value), int(b.value), int(w.value)
+
+    def debug_hold_tail(self, ms):
+        """diagnostic: the tail of the next call that takes the internal streams starts `ms` milliseconds late (0 .. 1000, 0
+        disarms) -- tsdr_debug_hold_tail"""
+        self.call("tsdr_debug_hold_tail", int(ms))
+
     def pipeline_info(self):
         """what tsdr_frames_submit_d measured on this context: dict(trials_left, chosen, ms_per_buffer[8], text)"""
         left, chosen, ms, text = C.c_int(0), C.c_int(-1), (C.c_float * 8)(), C.create_string_buffer(1024)

@@ -200,6 +200,11 @@ struct tsdr_ctx {
   unsigned long long wait_timeouts = 0;   // bounded waits that gave up (tsdr_wait_stats)
   unsigned long long guard_uncounted = 0; // guard ring entries that never arrived within their bound / were overwritten unread
   bool guard_late = false;          // the last awaited guard entry timed out: later ones get a short bound until one arrives
+  // tsdr_frames_overlap_stats: which route the tsdr_frames_d / _sc16_d / _iq_d calls of this context took (frames.hip:frames_run).
+  // Host-side counters; nothing reads them but that entry point.
+  unsigned long long run_on_lanes = 0, run_sequential = 0;
+  unsigned run_why = 0;             // why the latest sequential call was one: 1 option / contexts on the device, 2 profiling, 4 TSDR_EXACT, 8 adopted stream
+  int hold_tail_ms = 0;             // tsdr_debug_hold_tail: one-shot host-side delay on the tail lane of the next call that takes the lanes (0: none)
   int opt_beta_waves = 4;           // wavefronts per k_beta workgroup (4 or 8): alone the two tie; beside the pipeline's image kernel a 256-thread
                                     // workgroup fits the holes its retiring workgroups leave (raster-free 357 k vs 309 k frames/s)
 
@@ -219,6 +224,7 @@ int pipe_sync_lanes(tsdr_ctx *ctx);    // bounded host-side wait for the pipelin
 // A tsdr_frames_d call that left its tail on the lanes promised its caller stream order, not a flush point: everything the
 // context's stream is about to receive -- any launch (TSDR_LAUNCH), a copy, a timing event -- comes behind those tails.
 int contexts_on_device(int device);   // ctx.hip: contexts alive on it (tsdr_create .. tsdr_destroy)
+void hold_cb(void *ms);               // ctx.hip: the host function of tsdr_debug_hold_stream / tsdr_debug_hold_tail (sleeps (intptr_t)ms milliseconds)
 static inline int run_fence(tsdr_ctx *c) { return c->pipe.n && c->pipe.from_run ? pipe_drain(c) : (int)TSDR_OK; }
 static inline PipeOpts pipe_opts(const tsdr_ctx *c) {
   return PipeOpts{c->opt_pipe_mode, c->opt_pipe_lanes, c->opt_pipe_priority, c->opt_pipe_tune, c->opt_pipe_pin};

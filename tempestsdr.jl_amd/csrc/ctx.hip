@@ -164,6 +164,8 @@ void *tsdr_ctx::scratch(int slot, size_t bytes) {
 static std::atomic<int> g_live[64];
 namespace tsdr {
 int contexts_on_device(int device) { return device >= 0 && device < 64 ? g_live[device].load(std::memory_order_relaxed) : 2; }
+// the host function of tsdr_debug_hold_stream / tsdr_debug_hold_tail
+void hold_cb(void *p) { std::this_thread::sleep_for(std::chrono::milliseconds((long)(intptr_t)p)); }
 }
 
 extern "C" {
@@ -368,11 +370,25 @@ int tsdr_wait_stats(tsdr_ctx *ctx, unsigned long long *timeouts, unsigned long l
   return TSDR_OK;
 }
 
-static void hold_cb(void *p) { std::this_thread::sleep_for(std::chrono::milliseconds((long)(intptr_t)p)); }
-
 int tsdr_debug_hold_stream(tsdr_ctx *ctx, int ms) {
   if (!ctx || ms < 0 || ms > 10000) return TSDR_EINVAL;
-  TSDR_HIP(ctx, hipLaunchHostFunc(ctx->stream, hold_cb, (void *)(intptr_t)ms));
+  TSDR_HIP(ctx, hipLaunchHostFunc(ctx->stream, tsdr::hold_cb, (void *)(intptr_t)ms));
+  return TSDR_OK;
+}
+
+// armed here, spent by the next call that takes the lanes (frames.hip:frames_submit)
+int tsdr_debug_hold_tail(tsdr_ctx *ctx, int ms) {
+  if (!ctx || ms < 0 || ms > 1000) return TSDR_EINVAL;
+  ctx->hold_tail_ms = ms;
+  return TSDR_OK;
+}
+
+int tsdr_frames_overlap_stats(tsdr_ctx *ctx, unsigned long long *on_lanes, unsigned long long *sequential, unsigned *why, int reset) {
+  if (!ctx) return TSDR_EINVAL;
+  if (on_lanes) *on_lanes = ctx->run_on_lanes;
+  if (sequential) *sequential = ctx->run_sequential;
+  if (why) *why = ctx->run_why;
+  if (reset) { ctx->run_on_lanes = ctx->run_sequential = 0; ctx->run_why = 0; }
   return TSDR_OK;
 }
 

@@ -312,9 +312,15 @@ static int frames_run(tsdr_ctx *ctx, tsdr_sync *sync, const float *iq, IqFmt fmt
   // and not on an adopted stream, whose owner orders their own work against this call by stream order alone.  Not beside another
   // context on the device either, unless asked for ("frames_overlap" 2): two contexts fill each other's gaps already, and four
   // lanes beside two context streams on four hardware queues measured 0.96-0.97 of two plain streams (bench: two_streams).
-  if (may_overlap && overlap_allowed(ctx->opt_frames_overlap, contexts_on_device(ctx->device)) && !ctx->prof_on && ctx->precision == TSDR_FAST && ctx->own_stream && nb > 0)
+  // (why not, for tsdr_frames_overlap_stats: every condition that fails, as bits)
+  const unsigned why = (overlap_allowed(ctx->opt_frames_overlap, contexts_on_device(ctx->device)) ? 0u : 1u) | (ctx->prof_on ? 2u : 0u) |
+                       (ctx->precision == TSDR_FAST ? 0u : 4u) | (ctx->own_stream ? 0u : 8u);
+  if (may_overlap && !why && nb > 0) {
+    ++ctx->run_on_lanes;
     return frames_submit(ctx, sync, iq, fmt, nEch, S, y_t, x_t, alpha, do_align, imageOut_state, frames_out, raster_out, sync_idx, n_frames,
                          LanePolicy::ImageAndTail);
+  }
+  if (may_overlap && nb > 0) { ++ctx->run_sequential; ctx->run_why = why; }
   if (ctx->pipe.n) {  // buffers submitted through the pipeline come first (SyncXY and imageOut state are sequential)
     int rcd = pipe_drain(ctx);
     if (rcd) return rcd;
@@ -567,6 +573,11 @@ static int frames_submit(tsdr_ctx *ctx, tsdr_sync *sync, const float *iq, IqFmt 
     {
       LaneScope tail_lane(ctx, lane_tail);
       TSDR_HIP(ctx, hipStreamWaitEvent(tail_stream, P.ev_img[slot], 0));
+      if (run && ctx->hold_tail_ms) {   // tsdr_debug_hold_tail: the whole tail of this call is that late, once
+        const int ms = ctx->hold_tail_ms;
+        ctx->hold_tail_ms = 0;
+        TSDR_HIP(ctx, hipLaunchHostFunc(tail_stream, hold_cb, (void *)(intptr_t)ms));
+      }
       rc = job_stats(j);
       // (shift + IIR on a third stream of its own: 348 k vs 357 k frames/s raster-free, 175 k vs 181 k with rasters -- dropped)
       if (!rc) rc = job_combine(j, P.ev_tail[slot]);

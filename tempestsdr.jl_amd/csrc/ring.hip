@@ -45,7 +45,13 @@ struct tsdr_ring {
   std::vector<unsigned long long> slot_gen;
   unsigned long long staged_gen[2] = {0, 0};
   int next_dev = 0;
-  int dma_slot[2] = {-1, -1};   // host slot the last DMA into dev[i] reads (guards against a lapping producer)
+  // Every DMA out of a host slot gets a ticket, in issue order, which is the copy stream's order.  slot_dma[s]: the latest one that
+  // reads slot s; dma_ticket[i]: the one ready[i] stands for (the latest into dev[i]); dma_done: the highest one the producer has
+  // seen complete.  The producer touches a slot only when the slot's ticket is done.  (Remembering only which slot the LAST
+  // transfer into each device buffer reads is not enough: the copy stream waits for the consumer's stream (`freed`), and on a
+  // stream that lags two takes behind the host an older transfer has not started when its device buffer is handed the next.)
+  std::vector<unsigned long long> slot_dma;
+  unsigned long long dma_ticket[2] = {0, 0}, dma_issued = 0, dma_done = 0;
   int writing_slot = -1;         // slot the producer is filling right now
   bool staging[2] = {false, false};  // a DMA into dev[i] is being enqueued (its `ready` event is not recorded yet)
   long long seq_written = 0, seq_read = 0;  // counts of put / take
@@ -164,6 +170,7 @@ int tsdr_ring_create(tsdr_ctx *ctx, size_t nEch, int depth, int fmt, float scale
   r->ctx = ctx; r->nEch = nEch; r->depth = depth; r->fmt = fmt; r->scale = scale;
   r->slot_bytes = nEch * ring_fmt_bytes(fmt);
   r->slot_gen.assign((size_t)depth, 0ull);
+  r->slot_dma.assign((size_t)depth, 0ull);
   bool ok = hipHostMalloc((void **)&r->host, r->slot_bytes * depth, hipHostMallocDefault) == hipSuccess;
   for (int i = 0; i < 2 && ok; ++i) {
     ok = hipMalloc((void **)&r->dev[i], nEch * 8) == hipSuccess;
@@ -199,15 +206,29 @@ void tsdr_ring_free(tsdr_ring *r) {
 // A slot must not change under a DMA that is still reading it (the reference takes a per-slot lock around its
 // copyto!, :183-185).  Called by the producer before it touches slot `pos`.
 static void ring_wait_slot_idle(tsdr_ring *r, int pos) {
-  for (int i = 0; i < 2; ++i) {
-    bool pending;
+  for (;;) {
+    int i;
+    unsigned long long upto;
     {
       std::unique_lock<std::mutex> lk(r->m);
-      r->cv.wait(lk, [&] { return !(r->staging[i] && r->dma_slot[i] == pos); });  // until its event is recorded
-      pending = r->dma_slot[i] == pos;
+      const unsigned long long t = r->slot_dma[(size_t)pos];
+      if (t <= r->dma_done) return;
+      // the event of that transfer -- or, the copy stream running in order, of the one issued behind it into the other buffer
+      i = r->dma_ticket[0] >= t && (r->dma_ticket[1] < t || r->dma_ticket[0] < r->dma_ticket[1]) ? 0 : 1;
+      r->cv.wait(lk, [&] { return !r->staging[i]; });  // until it is recorded
+      upto = r->dma_ticket[i];
     }
-    if (pending) (void)tsdr::wait_event(r->ctx, r->ready[i], "ring: DMA out of the slot about to be rewritten");
+    // (bounded like every host-side wait; a transfer that never completes does not hold the producer for good, as before)
+    if (tsdr::wait_event(r->ctx, r->ready[i], "ring: DMA out of the slot about to be rewritten")) return;
+    std::lock_guard<std::mutex> g(r->m);
+    if (upto > r->dma_done) r->dma_done = upto;
   }
+}
+
+// a DMA out of host slot `slot` into dev[d] is about to be enqueued (caller holds the lock; ring_stage records its event)
+static void ring_dma_begin(tsdr_ring *r, int d, int slot) {
+  r->staging[d] = true;
+  r->dma_ticket[d] = r->slot_dma[(size_t)slot] = ++r->dma_issued;
 }
 
 static void ring_publish(tsdr_ring *r) {
@@ -281,7 +302,7 @@ int tsdr_ring_take_d(tsdr_ring *r, int timeout_ms, float **dev_iq) {
     staged = r->staged_seq[d] == r->seq_read && r->staged_gen[d] == r->slot_gen[(size_t)slot];
     ++r->seq_read;
     if (staged) ++r->prefetch_hits; else ++r->prefetch_misses;
-    if (!staged) { r->dma_slot[d] = slot; r->staging[d] = true; }
+    if (!staged) ring_dma_begin(r, d, slot);
   }
   // the device buffer about to be refilled further down (the other one) was handed out two takes ago: the
   // caller's stream has to be past its consumers before the DMA may overwrite it (a tsdr_frames_d call that consumes one on
@@ -303,13 +324,11 @@ int tsdr_ring_take_d(tsdr_ring *r, int timeout_ms, float **dev_iq) {
     std::lock_guard<std::mutex> g(r->m);
     r->next_dev = d ^ 1;
     r->staged_seq[d ^ 1] = -1;
-    r->dma_slot[d ^ 1] = -1;
     if (r->t_new > 0 && r->writing_slot != r->ptr_read) {
       nslot = r->ptr_read;
       r->staged_seq[d ^ 1] = r->seq_read;
       r->staged_gen[d ^ 1] = r->slot_gen[(size_t)nslot];
-      r->dma_slot[d ^ 1] = nslot;
-      r->staging[d ^ 1] = true;
+      ring_dma_begin(r, d ^ 1, nslot);
     }
   }
   if (nslot >= 0) {

@@ -21,7 +21,7 @@ export getSpectrum, getWelch, getWaterfall
 export hip_welch_d, hip_waterfall_d                                   # getWelch / getWaterfall of a device buffer in any IQ format (a raw ring slot)
 export SyncXY, vsync
 export hip_frames!, hip_frames_submit!, hip_frames_submit_sc16!, hip_frames_submit_iq!, hip_frames_flush, hip_synchronize   # fused GUI.jl:163-178 loop body (optional fast path; pipelined form)
-export hip_extract_configuration, sync_guard_stats, sync_guard_auto, wait_stats   # fused GUI.jl:67-81 search; counters of the FAST loop's sync guard
+export hip_extract_configuration, sync_guard_stats, sync_guard_auto, wait_stats, frames_overlap_stats, debug_hold_tail  # fused GUI.jl:67-81 search; counters of the FAST loop's sync guard
 export hip_set_precision, hip_set_option                              # TSDR_EXACT / TSDR_FAST and the library's options, per task context
 export arg_area_blank!                                                # FrameSynchronisation.jl:53's binding: findmax (bright blanking) or findmin
 export HipGroup, hip_group                                            # one process, several GPUs (RCCL inside the library): `devices = ...`
@@ -555,6 +555,20 @@ function wait_stats()
     a = Ref{Culonglong}(0); b = Ref{Culonglong}(0); c = ctx()
     check(c, ccall((:tsdr_wait_stats, LIB), Cint, (Ptr{Cvoid}, Ptr{Culonglong}, Ptr{Culonglong}), c.h, a, b), "wait_stats")
     return (Int(a[]), Int(b[]))
+end
+
+"(calls on the internal streams, calls on the context's stream, why the latest of those was sequential: bits 1 option or another context on the device, 2 profiling, 4 TSDR_EXACT, 8 adopted stream) of `hip_frames!` on device buffers: option \"frames_overlap\""
+function frames_overlap_stats(; reset = false)
+    a = Ref{Culonglong}(0); b = Ref{Culonglong}(0); w = Ref{Cuint}(0); c = ctx()
+    check(c, ccall((:tsdr_frames_overlap_stats, LIB), Cint, (Ptr{Cvoid}, Ptr{Culonglong}, Ptr{Culonglong}, Ptr{Cuint}, Cint), c.h, a, b, w, reset ? 1 : 0), "frames_overlap_stats")
+    return (Int(a[]), Int(b[]), Int(w[]))
+end
+
+"diagnostic: the tail of the next frame-loop call on the internal streams starts `ms` milliseconds late (0 disarms)"
+function debug_hold_tail(ms::Integer)
+    c = ctx()
+    check(c, ccall((:tsdr_debug_hold_tail, LIB), Cint, (Ptr{Cvoid}, Cint), c.h, ms), "debug_hold_tail")
+    return nothing
 end
 
 # ---- one process, several GPUs (tsdr_group_*: one context + one RCCL communicator per device) ----------------------

@@ -51,10 +51,20 @@ def _call(api, ctx, sync, iq, fmt, scale, nEch, S, g, do_align, state, out, subm
     assert n == NFR
 
 
+def _expected_route(overlap, calls, between=None):
+    """(on_lanes, sequential, why) of tsdr_frames_overlap_stats after `calls` calls with "frames_overlap" 2 * overlap: the one
+    call through tsdr_frames_submit_d counts in neither, the one TSDR_EXACT call is sequential whatever the option says"""
+    n = calls - 1 if between == "submit_flush" else calls
+    if not overlap:
+        return 0, n, 1   # (the latest sequential call is a plain one: the option alone)
+    return (n - 1, 1, 4) if between == "exact" else (n, 0, 0)
+
+
 def _run(ctx, tsdr, synth, overlap, geo="small", fmt="cf32", raster=True, do_align=True, current_sy=0, reuse=False, card="box",
-         between=None, ppb=None, calls=NBUF):
+         between=None, ppb=None, calls=NBUF, ext_event=None):
     """Six calls on one SyncXY / IIR state; `between`: what the caller does around the fourth call.  Returns everything a caller
-    can observe afterwards, as a dict of tensors / tuples."""
+    can observe afterwards, as a dict of tensors / tuples.  The route the calls took is asserted (tsdr_frames_overlap_stats): a run
+    with the option on that stayed on the context's stream fails here."""
     from tempestsdr_jl_amd import api
     g = GEO[geo]
     iqs, scale, nEch, S = _bufs(synth, geo, fmt, card)
@@ -78,6 +88,9 @@ def _run(ctx, tsdr, synth, overlap, geo="small", fmt="cf32", raster=True, do_ali
     ctx.set_option("sync_guard_ppb", 20000 if ppb is None else ppb)
     ctx.sync_guard_stats(reset=True)
     route0 = ctx.sync_guard_auto()
+    if ext_event is not None:   # (how the tail's event is recorded: with the shift + IIR dispatch, or as a marker of its own)
+        ctx.set_option("pipe_ext_event", ext_event)
+    ctx.frames_overlap_stats(reset=True)
     try:
         for b in range(calls):
             out = outs[b % nout]
@@ -107,6 +120,7 @@ def _run(ctx, tsdr, synth, overlap, geo="small", fmt="cf32", raster=True, do_ali
             elif act == "timer":
                 extra["timer_ms"] = ctx.timer_stop()
         ctx.synchronize()
+        assert ctx.frames_overlap_stats() == _expected_route(overlap, calls, between), (overlap, between, ctx.frames_overlap_stats())
         res = {"state": state.clone(), "guard": ctx.sync_guard_stats(), "s_yx": s_yx.clone()}
         route1 = ctx.sync_guard_auto()   # the adaptive route: (whole buffers exactly right now, calls that ran so, route changes)
         res["route"] = (route1[0], route1[1] - route0[1], route1[2] - route0[2])
@@ -127,6 +141,8 @@ def _run(ctx, tsdr, synth, overlap, geo="small", fmt="cf32", raster=True, do_ali
     finally:
         ctx.set_option("frames_overlap", 1)
         ctx.set_option("vsync_current_sy", 0)
+        if ext_event is not None:
+            ctx.set_option("pipe_ext_event", 1)
         if ppb is not None:
             ctx.set_option("sync_guard_ppb", 20000)
         if sync is not None:
@@ -160,6 +176,78 @@ def test_overlap_equals_sequential(ctx, tsdr, synth, geo, fmt, reuse):
             continue   # (the option is read by the aligned path only)
         cfg = dict(geo=geo, fmt=fmt, raster=raster, do_align=do_align, current_sy=current_sy, reuse=reuse)
         _same(_sequential(ctx, tsdr, synth, **cfg), _run(ctx, tsdr, synth, 1, **cfg), cfg)
+
+
+@pytest.mark.parametrize("ext_event", [1, 0])
+def test_overlap_equals_sequential_with_either_tail_event(ctx, tsdr, synth, ext_event):
+    """"pipe_ext_event" 1 (default): the tail's event -- what every later fence waits for -- rides on the shift + IIR dispatch;
+    0: it is a marker of its own behind it.  Two implementations of the same fence, the same results."""
+    cfg = dict(geo="small", fmt="cf32", raster=True, do_align=True, current_sy=0, reuse=False)
+    _same(_sequential(ctx, tsdr, synth, **cfg), _run(ctx, tsdr, synth, 1, ext_event=ext_event, **cfg), ext_event)
+
+
+def test_overlap_is_off_on_an_adopted_stream(ctx, tsdr, synth):
+    """tsdr_set_stream to a stream of the caller's: calls stay on it (stream order alone holds there), tsdr_frames_overlap_stats
+    says why (8); back on a stream of its own the context takes the lanes again.  Results equal the sequential run's."""
+    from tempestsdr_jl_amd import api
+    cfg = dict(geo="small", fmt="cf32", raster=True, do_align=True, current_sy=0, reuse=False)
+    want = _sequential(ctx, tsdr, synth, **cfg)
+    g = GEO["small"]
+    iqs, scale, nEch, S = _bufs(synth, "small", "cf32")
+    outs = [(torch.zeros(NFR * NPX, dtype=torch.float32, device="cuda:0"), torch.zeros(NFR * g["x_t"] * g["y_t"], dtype=torch.float32, device="cuda:0"),
+             torch.zeros(2 * NFR, dtype=torch.int32, device="cuda:0")) for _ in range(NBUF)]
+    state = torch.zeros(NPX, dtype=torch.float32, device="cuda:0")
+    mine = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    sync = tsdr.SyncXY(ctx, 600, 800)
+    ctx.set_option("frames_overlap", 2)
+    ctx.sync_guard_stats(reset=True)
+    ctx.frames_overlap_stats(reset=True)
+    try:
+        for b in (0, 1):
+            _call(api, ctx, sync, iqs[b], "cf32", scale, nEch, S, g, True, state, outs[b])
+        assert ctx.frames_overlap_stats() == (2, 0, 0)
+        ctx.set_stream(mine.cuda_stream)   # (with two tails in flight: ordered through the old stream first)
+        try:
+            for b in (2, 3):
+                _call(api, ctx, sync, iqs[b], "cf32", scale, nEch, S, g, True, state, outs[b])
+            assert ctx.frames_overlap_stats() == (2, 2, 8)
+        finally:
+            ctx.set_stream(None)
+        for b in (4, 5):
+            _call(api, ctx, sync, iqs[b], "cf32", scale, nEch, S, g, True, state, outs[b])
+        assert ctx.frames_overlap_stats() == (4, 2, 8)
+        ctx.synchronize()
+        assert torch.equal(state, want["state"]) and ctx.sync_guard_stats() == want["guard"]
+        for k, (fo, ro, si) in enumerate(outs):
+            assert torch.equal(fo, want[f"frames{k}"]) and torch.equal(ro, want[f"raster{k}"]) and torch.equal(si, want[f"idx{k}"]), k
+        # (the SyncXY state as _run reads it: the pending s_y through one more vsync of the same image, then beta)
+        img = np.random.default_rng(5).random(NPX).astype(np.float32)
+        assert tuple(int(v) for v in sync.vsync(img.reshape(800, 600).T)) == want["pending"]
+        assert torch.equal(torch.from_numpy(sync.beta("x").copy()), want["beta_x"]) and torch.equal(torch.from_numpy(sync.beta("y").copy()), want["beta_y"])
+    finally:
+        ctx.set_option("frames_overlap", 1)
+        sync.close()
+
+
+def test_default_option_in_a_process_of_its_own():
+    """The real default -- one context alone on its device, "frames_overlap" left at 1 -- in a fresh process (tests/overlap_child.py):
+    six calls on the lanes, a second context turns them off for the next call (why: 1), closing it turns them on again, and all
+    eight calls give what the same eight give with the option 0."""
+    import json
+    import os
+    import subprocess
+    import sys
+    child = os.path.join(os.path.dirname(os.path.abspath(__file__)), "overlap_child.py")
+    r = subprocess.run([sys.executable, child], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    print(line)
+    assert line["alone"] == [6, 0, 0], line
+    assert line["second_context"] == [6, 1, 1], line
+    assert line["alone_again"] == [7, 1, 1], line
+    assert line["option_0"] == [0, 8, 1], line
+    assert line["equal"] is True and line["guard"][0] == 8 * NFR, line
 
 
 @pytest.mark.parametrize("between", ["synchronize", "timer", "download", "vsync_d", "submit_flush", "exact", "geometry"])
@@ -211,13 +299,17 @@ def test_overlap_is_off_while_profiling(ctx, tsdr, synth):
         state = torch.zeros(NPX, dtype=torch.float32, device="cuda:0")
         torch.cuda.synchronize()
         ctx.set_option("frames_overlap", 2 * overlap)
+        ctx.frames_overlap_stats(reset=True)
         try:
             _call(api, ctx, sync, iqs[0], "cf32", scale, nEch, S, g, True, state, out)   # (one overlapped call in flight first)
+            assert ctx.frames_overlap_stats(reset=True) == ((1, 0, 0) if overlap else (0, 1, 1))
             ctx.profile_reset()
             ctx.profile(True)
             for b in (1, 2):
                 _call(api, ctx, sync, iqs[b], "cf32", scale, nEch, S, g, True, state, out)
             ctx.profile(False)
+            # (both profiled calls ran on the context's stream, and profiling is why: bit 2, beside bit 1 where the option is off too)
+            assert ctx.frames_overlap_stats() == (0, 2, 2 if overlap else 3)
             got[overlap] = {k: v["launches"] for k, v in ctx.profile_results().items()}
         finally:
             ctx.set_option("frames_overlap", 1)

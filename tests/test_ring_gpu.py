@@ -78,6 +78,37 @@ def test_ring_prefetch_survives_overflow(ctx, tsdr):
     ring.close()
 
 
+def test_ring_producer_waits_for_a_transfer_the_consumers_stream_holds_back(ctx, tsdr):
+    """The copy stream waits for the consumer's stream before it refills a device buffer, so on a stream that lags behind the
+    host (here: held for 100 ms, tsdr_debug_hold_stream) the DMA out of a host slot has not started when the consumer has already
+    taken the next buffer.  The producer, wrapping round a ring of depth 3, must still find that slot busy: the consumer's copy of
+    buffer 0, enqueued behind the take, holds buffer 0 and not the buffer 3 that was put into its slot meanwhile."""
+    import ctypes as C
+    n, depth = 4096, 3
+    ring = tsdr.StagingRing(ctx, n, depth)
+    bufs = [_buf(n, k) for k in range(4)]
+    keep = [ctx.dev_alloc(n * 8) for _ in range(2)]
+    try:
+        for b in bufs[:3]:
+            ring.put(b)
+        ctx.call("tsdr_debug_hold_stream", 100)
+        for k in range(2):   # take, and consume on the context's stream (a copy, as a frame loop's kernels would): no host wait
+            d = ring.take_d(1000)
+            ctx.call("tsdr_iq_expand_d", C.c_void_p(d), 0, C.c_float(1.0), n, C.c_void_p(keep[k]))
+        ring.put(bufs[3])    # slot 0 again: two of three buffers are consumed, nothing is dropped
+        assert ring.stats()["overflow"] == 0
+        for k in range(2):
+            got = ctx.download(keep[k], (n,), np.complex64)
+            assert np.array_equal(got.view(np.uint32), bufs[k].view(np.uint32)), k
+        for k in (2, 3):
+            got = ctx.download(ring.take_d(1000), (n,), np.complex64)
+            assert np.array_equal(got.view(np.uint32), bufs[k].view(np.uint32)), k
+    finally:
+        ring.close()
+        for p in keep:
+            ctx.dev_free(p)
+
+
 def test_ring_sc16_expansion(ctx, tsdr):
     n = 50_000
     scale = 1.0 / 2048.0
