@@ -188,12 +188,21 @@ int tsdr_sync_guard_margins(tsdr_ctx *ctx, int max_frames, float *margins, int *
  * host / GPU timing (tests/test_fast_mode_gpu.py:test_adaptive_route_is_reproducible_run_to_run); the price is that a
  * frame-loop call may return only when the call three before it has reached its guard launch. */
 int tsdr_sync_guard_auto(tsdr_ctx *ctx, int *exact_now, unsigned long long *buffers_exact, unsigned long long *switches);
-/* EVERY HOST-SIDE WAIT OF THE LIBRARY IS BOUNDED (round 6; replaces nothing in the reference -- GUI.jl:197-200 swallows a
- * consumer task's exceptions, it cannot swallow a ccall that never returns).  Waits for a stream (results of the host-pointer
- * entry points, tsdr_synchronize, workspace growth, a change of pipeline arrangement, destruction) poll a marker event for at
- * most "wait_ms" milliseconds (tsdr_set_option / TSDR_WAIT_MS; default 30000; 0 = plain hipStreamSynchronize) and then return
- * TSDR_EHIP with the waiting stage in tsdr_last_error; an object whose stream never completed is abandoned by its
- * destructor (memory not released) instead of waiting for the device.  The adaptive route's wait for a guard ring entry is
+/* EVERY HOST-SIDE WAIT OF THE LIBRARY FOR A STREAM IS BOUNDED (round 6; replaces nothing in the reference -- GUI.jl:197-200
+ * swallows a consumer task's exceptions, it cannot swallow a ccall that never returns).  Waits for a stream (results of the
+ * host-pointer entry points, tsdr_synchronize, workspace growth, a change of pipeline arrangement, destruction) poll a marker
+ * event for at most "wait_ms" milliseconds (tsdr_set_option / TSDR_WAIT_MS; default 30000; 0 = plain hipStreamSynchronize) and
+ * then return TSDR_EHIP with the waiting stage in tsdr_last_error; an object whose stream never completed is abandoned by its
+ * destructor (memory not released) instead of waiting for the device.
+ *   What the bound does NOT cover: a host-pointer entry point hands the caller's arrays to hipMemcpyAsync, and a copy from or to
+ * pageable memory may be staged by the calling thread inside that call, behind whatever the stream still holds -- before the
+ * bounded wait is reached.  (Pinned arrays -- hipHostMalloc, hipHostRegister -- are only enqueued.)
+ *   What a wait that gave up leaves behind: the call's copies stay enqueued.  After TSDR_EHIP from a timed-out wait the arrays the
+ * call was to fill may STILL BE WRITTEN, and the arrays it was to read may still be read: keep them alive and leave them alone
+ * until a later tsdr_synchronize on that context succeeds, or the context is destroyed.  The library's own host temporaries of
+ * such a call (the index pair of tsdr_vsync, the guard's counters and margin records, table images) are kept alive by the
+ * library: small results land in a pinned block of the context, larger ones move to a list tsdr_destroy releases once the
+ * stream has completed (csrc/host_stage.h).  The adaptive route's wait for a guard ring entry is
  * bounded at 50 ms per entry (2 ms once an entry has timed out, until one arrives again); an entry that did not arrive goes
  * uncounted.  *timeouts = stream waits given up so far on this context, *guard_uncounted = guard entries that went uncounted. */
 int tsdr_wait_stats(tsdr_ctx *ctx, unsigned long long *timeouts, unsigned long long *guard_uncounted);

@@ -205,6 +205,9 @@ struct tsdr_ctx {
   unsigned long long run_on_lanes = 0, run_sequential = 0;
   unsigned run_why = 0;             // why the latest sequential call was one: 1 option / contexts on the device, 2 profiling, 4 TSDR_EXACT, 8 adopted stream
   int hold_tail_ms = 0;             // tsdr_debug_hold_tail: one-shot host-side delay on the tail lane of the next call that takes the lanes (0: none)
+  void *stage_small = nullptr;      // host_stage.h: the pinned block small results of the host forms land in (allocated on first use)
+  std::vector<void *> stage_kept;   // ... and the temporaries of calls whose wait gave up: a copy may still touch them, so nothing frees them
+                                    // before tsdr_destroy has seen the stream complete
   int opt_beta_waves = 4;           // wavefronts per k_beta workgroup (4 or 8): alone the two tie; beside the pipeline's image kernel a 256-thread
                                     // workgroup fits the holes its retiring workgroups leave (raster-free 357 k vs 309 k frames/s)
 
@@ -297,21 +300,6 @@ static inline int stream_blocks(int cu_count, size_t work_items) {
 }
 static inline int stream_grid(tsdr_ctx *ctx, size_t work_items) { return stream_blocks(ctx->cu_count, work_items); }
 
-// Host-pointer wrapper: stage `in` to the device, run the device-pointer core on the
-// context's stream, copy `out` back, synchronise.  run(din, dout) returns a tsdr_status.
-template <typename F>
-static inline int host_map(tsdr_ctx *ctx, const void *in, size_t in_bytes, void *out, size_t out_bytes, F run) {
-  if (!ctx) return TSDR_EINVAL;
-  if ((in_bytes && !in) || (out_bytes && !out)) return TSDR_EINVAL;
-  void *din = ctx->scratch(WS_IN, in_bytes);
-  void *dout = ctx->scratch(WS_OUT, out_bytes);
-  if (!din || !dout) return TSDR_ENOMEM;
-  if (in_bytes) TSDR_HIP(ctx, hipMemcpyAsync(din, in, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-  int rc = run(din, dout);
-  if (rc) return rc;
-  if (out_bytes) TSDR_HIP(ctx, hipMemcpyAsync(out, dout, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-  return wait_stream(ctx, ctx->stream, "host wrapper: results");
-}
 static inline int ilog2(size_t v) { int l = 0; while ((size_t(1) << l) < v) ++l; return l; }
 static inline bool is_pow2(size_t v) { return v && !(v & (v - 1)); }
 
@@ -430,3 +418,7 @@ __device__ inline float abs2_c(float re, float im) { return __fadd_rn(__fmul_rn(
 #endif
 
 }  // namespace tsdr
+
+// the staging path of the host-pointer entry points (HostStage, host_map, read_back), over the context declared above
+#define TSDR_HOST_STAGE_WITH_CTX
+#include "host_stage.h"

@@ -254,6 +254,8 @@ void tsdr_destroy(tsdr_ctx *ctx) {
   for (auto &q : ctx->guard_sync) if (q) (void)hipFree(q);
   if (ctx->guard_ring) (void)hipHostFree(ctx->guard_ring);
   if (ctx->amax_host) (void)hipHostFree(ctx->amax_host);
+  if (ctx->stage_small) (void)hipHostFree(ctx->stage_small);
+  for (void *p : ctx->stage_kept) free(p);   // (the stream completed: no copy of a timed-out call is pending any more)
   if (ctx->tw_small) (void)hipFree(ctx->tw_small);
   for (auto &kv : ctx->tw) { (void)hipFree(kv.second.lo); (void)hipFree(kv.second.hi); }
   for (auto &kv : ctx->twg) (void)hipFree(kv.second);
@@ -394,13 +396,16 @@ int tsdr_frames_overlap_stats(tsdr_ctx *ctx, unsigned long long *on_lanes, unsig
 
 int tsdr_sync_guard_stats(tsdr_ctx *ctx, unsigned long long *frames_checked, unsigned long long *frames_reevaluated, int reset) {
   if (!ctx) return TSDR_EINVAL;
-  unsigned long long h[2] = {0ull, 0ull};
   int rc = tsdr::pipe_drain(ctx);
   if (rc) return rc;
+  const unsigned long long none[2] = {0ull, 0ull}, *h = none;
   if (ctx->guard_stats) {
-    TSDR_HIP(ctx, hipMemcpyAsync(h, ctx->guard_stats, 16, hipMemcpyDeviceToHost, ctx->stream));
-    if (reset) TSDR_HIP(ctx, hipMemsetAsync(ctx->guard_stats, 0, 16, ctx->stream));
-    { int _w = tsdr::wait_stream(ctx, ctx->stream, __func__); if (_w) return _w; }
+    tsdr::HostStage st(ctx);
+    void *small = st.small(16);
+    st.out_from(ctx->guard_stats, small, 16);
+    if ((rc = st.run(__func__))) return rc;
+    h = (const unsigned long long *)small;
+    if (reset) TSDR_HIP(ctx, hipMemsetAsync(ctx->guard_stats, 0, 16, ctx->stream));   // (behind the copy, in stream order)
   }
   if (frames_checked) *frames_checked = h[0];
   if (frames_reevaluated) *frames_reevaluated = h[1];
@@ -420,13 +425,14 @@ int tsdr_sync_guard_margins(tsdr_ctx *ctx, int max_frames, float *margins, int *
   if (n_frames) *n_frames = F;
   const int nf = F < max_frames ? F : max_frames;
   if (nf == 0) return TSDR_OK;
-  std::vector<uint2> h((size_t)nf * nbb);
-  TSDR_HIP(ctx, hipMemcpyAsync(h.data(), (const char *)gb_ws.p + ctx->guard_last_off, h.size() * sizeof(uint2), hipMemcpyDeviceToHost,
-                               ctx->stream));
-  { int _w = tsdr::wait_stream(ctx, ctx->stream, __func__); if (_w) return _w; }
+  tsdr::HostStage st(ctx);
+  const size_t hbytes = (size_t)nf * nbb * sizeof(uint2);
+  const uint2 *h = (const uint2 *)st.temp(hbytes);
+  st.out_from((const char *)gb_ws.p + ctx->guard_last_off, (void *)h, hbytes);
+  if ((rc = st.run(__func__))) return rc;
   for (int f = 0; f < nf; ++f)
     for (int axis = 0; axis < 2; ++axis) {  // the same top-2 merge as guard_eval (guard.h)
-      const uint2 *e = h.data() + (size_t)f * nbb + (axis ? nbx : 0);
+      const uint2 *e = h + (size_t)f * nbb + (axis ? nbx : 0);
       const int nb = axis ? nby : nbx;
       unsigned gb = 0, gs = 0;
       int holders = 0;
@@ -491,22 +497,17 @@ int tsdr_dev_free(tsdr_ctx *ctx, void *dev) {
 
 int tsdr_upload(tsdr_ctx *ctx, void *dst_dev, const void *src_host, size_t bytes) {
   if (!ctx || (bytes && (!dst_dev || !src_host))) return TSDR_EINVAL;
-  if (bytes) {
-    if (int rc = tsdr::run_fence(ctx)) return rc;   // (dst_dev may be a buffer a tsdr_frames_d call still reads or writes on a lane)
-    TSDR_HIP(ctx, hipMemcpyAsync(dst_dev, src_host, bytes, hipMemcpyHostToDevice, ctx->stream));
-    { int _w = tsdr::wait_stream(ctx, ctx->stream, __func__); if (_w) return _w; }
-  }
-  return TSDR_OK;
+  if (!bytes) return TSDR_OK;
+  tsdr::HostStage st(ctx);
+  st.in_to(dst_dev, src_host, bytes);
+  return st.run(__func__);   // (its run_fence: dst_dev may be a buffer a tsdr_frames_d call still reads or writes on a lane)
 }
 
 int tsdr_download(tsdr_ctx *ctx, void *dst_host, const void *src_dev, size_t bytes) {
   if (!ctx || (bytes && (!dst_host || !src_dev))) return TSDR_EINVAL;
-  if (bytes) {
-    if (int rc = tsdr::run_fence(ctx)) return rc;   // (src_dev may be what a tsdr_frames_d call's tail is still writing on a lane)
-    TSDR_HIP(ctx, hipMemcpyAsync(dst_host, src_dev, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    { int _w = tsdr::wait_stream(ctx, ctx->stream, __func__); if (_w) return _w; }
-  }
-  return TSDR_OK;
+  if (!bytes) return TSDR_OK;
+  // (the fence: src_dev may be what a tsdr_frames_d call's tail is still writing on a lane)
+  return tsdr::read_back(ctx, false, dst_host, src_dev, bytes, __func__);
 }
 
 int tsdr_timer_start(tsdr_ctx *ctx) {

@@ -472,18 +472,11 @@ int tsdr_display_u8(tsdr_ctx *ctx, const float *images, int n_images, int h, int
   if (int rc = display_check(ctx, "display_u8", c)) return rc;
   if (n_images == 0) return TSDR_OK;
   const size_t n = (size_t)n_images, in_bytes = n * (size_t)h * (size_t)w * 4, R = (size_t)rh * (size_t)rw;
-  float *d_in = (float *)ctx->scratch(WS_IN, in_bytes);
-  uint8_t *d_out = out ? (uint8_t *)ctx->scratch(WS_OUT, n * R) : nullptr;
-  float *d_rng = ranges_out ? (float *)ctx->scratch(WS_AUX, n * 8) : nullptr;
-  if (!d_in || (out && !d_out) || (ranges_out && !d_rng)) return TSDR_ENOMEM;
-  TSDR_HIP(ctx, hipMemcpyAsync(d_in, images, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-  c.images = d_in;
-  c.out = d_out;
-  c.ranges_out = d_rng;
-  if (int rc = display_launch(ctx, c)) return rc;
-  if (out) TSDR_HIP(ctx, hipMemcpyAsync(out, d_out, n * R, hipMemcpyDeviceToHost, ctx->stream));
-  if (ranges_out) TSDR_HIP(ctx, hipMemcpyAsync(ranges_out, d_rng, n * 8, hipMemcpyDeviceToHost, ctx->stream));
-  return wait_stream(ctx, ctx->stream, __func__);
+  HostStage st(ctx);
+  c.images = (const float *)st.in(WS_IN, images, in_bytes);
+  c.out = (uint8_t *)st.out(WS_OUT, out, n * R);
+  c.ranges_out = (float *)st.out(WS_AUX, ranges_out, n * 8);
+  return st.run(__func__, [&] { return display_launch(ctx, c); });
 }
 
 }  // extern "C"

@@ -378,17 +378,12 @@ int fold_entry(tsdr_ctx *ctx, const char *fn, const char *what, FoldCall c, bool
   if (device) return fold_launch<Fl>(ctx, c, f);
   const size_t in_bytes = c.n * iq_bytes(f), out_bytes = c.scan ? (size_t)c.n_trials * 8 : (size_t)c.y_t * (size_t)c.x_t * 4;
   void *out = c.scan ? (void *)c.score : (void *)c.state;
-  void *d_iq = ctx->scratch(WS_IN, in_bytes);
-  void *d_out = ctx->scratch(WS_OUT, out_bytes);
-  if (!d_iq || !d_out) return TSDR_ENOMEM;
-  TSDR_HIP(ctx, hipMemcpyAsync(d_iq, c.iq, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-  if (!c.scan && c.alpha != 0.f) TSDR_HIP(ctx, hipMemcpyAsync(d_out, out, out_bytes, hipMemcpyHostToDevice, ctx->stream));
-  c.iq = d_iq;
+  HostStage st(ctx);
+  c.iq = st.in(WS_IN, c.iq, in_bytes);
+  void *d_out = st.inout(WS_OUT, out, out_bytes, !c.scan && c.alpha != 0.f);
   if (c.scan) c.score = (double *)d_out;
   else c.state = (float *)d_out;
-  if (int rc = fold_launch<Fl>(ctx, c, f)) return rc;
-  TSDR_HIP(ctx, hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-  if (int rc = wait_stream(ctx, ctx->stream, what)) return rc;
+  if (int rc = st.run(what, [&] { return fold_launch<Fl>(ctx, c, f); })) return rc;
   if (c.scan && best) {
     const double *score = (const double *)out;
     *best = -1;

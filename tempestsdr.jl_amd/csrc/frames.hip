@@ -667,23 +667,15 @@ int tsdr_frames(tsdr_ctx *ctx, tsdr_sync *sync, const float *iq, size_t nEch, si
   if (!ctx || !imageOut_state || S == 0 || y_t <= 0 || x_t <= 0 || (nEch && !iq)) return TSDR_EINVAL;
   if (int rc = sync_f32_check(ctx, sync)) return rc;
   const size_t nb = nEch / S, npx = (size_t)TSDR_RENDER_H * TSDR_RENDER_W, P = (size_t)y_t * x_t;
-  float *d_iq = (float *)ctx->scratch(WS_IN, nEch * 8);
-  float *d_state = (float *)ctx->scratch(WS_AUX, npx * 4);
-  float *d_frames = frames_out ? (float *)ctx->scratch(WS_OUT, nb * npx * 4) : nullptr;
-  float *d_raster = raster_out ? (float *)ctx->scratch(WS_FFT_A, nb * P * 4) : nullptr;  // WS_RASTER is the fallback path's
-  int *d_idx = (sync_idx && do_align) ? (int *)ctx->scratch(WS_MISC, nb * 8 + 16) : nullptr;
-  if (!d_iq || !d_state || (frames_out && !d_frames) || (raster_out && !d_raster) || (sync_idx && do_align && !d_idx))
-    return TSDR_ENOMEM;
-  if (nEch) TSDR_HIP(ctx, hipMemcpyAsync(d_iq, iq, nEch * 8, hipMemcpyHostToDevice, ctx->stream));
-  TSDR_HIP(ctx, hipMemcpyAsync(d_state, imageOut_state, npx * 4, hipMemcpyHostToDevice, ctx->stream));
-  int rc = frames_run(ctx, sync, d_iq, IqFmt{}, nEch, S, y_t, x_t, alpha, do_align, d_state, d_frames, d_raster, d_idx, n_frames, false);
-  if (rc) return rc;
-  TSDR_HIP(ctx, hipMemcpyAsync(imageOut_state, d_state, npx * 4, hipMemcpyDeviceToHost, ctx->stream));
-  if (d_frames && nb) TSDR_HIP(ctx, hipMemcpyAsync(frames_out, d_frames, nb * npx * 4, hipMemcpyDeviceToHost, ctx->stream));
-  if (d_raster && nb) TSDR_HIP(ctx, hipMemcpyAsync(raster_out, d_raster, nb * P * 4, hipMemcpyDeviceToHost, ctx->stream));
-  if (d_idx && nb) TSDR_HIP(ctx, hipMemcpyAsync(sync_idx, d_idx, nb * 8, hipMemcpyDeviceToHost, ctx->stream));
-  { int _w = tsdr::wait_stream(ctx, ctx->stream, __func__); if (_w) return _w; }
-  return TSDR_OK;
+  HostStage st(ctx);   // (with nb == 0 the outputs have no bytes: nothing comes back but the state)
+  float *d_iq = (float *)(iq ? st.in(WS_IN, iq, nEch * 8) : st.reserve(WS_IN, 0));
+  float *d_state = (float *)st.inout(WS_AUX, imageOut_state, npx * 4, true);
+  float *d_frames = (float *)st.out(WS_OUT, frames_out, nb * npx * 4);
+  float *d_raster = (float *)st.out(WS_FFT_A, raster_out, nb * P * 4);  // WS_RASTER is the fallback path's
+  int *d_idx = (int *)st.out(WS_MISC, do_align ? sync_idx : nullptr, nb * 8);
+  return st.run(__func__, [&] {
+    return frames_run(ctx, sync, d_iq, IqFmt{}, nEch, S, y_t, x_t, alpha, do_align, d_state, d_frames, d_raster, d_idx, n_frames, false);
+  });
 }
 
 }  // extern "C"

@@ -139,16 +139,11 @@ int tsdr_raster_accum(tsdr_ctx *ctx, const float *rasters, int n_frames, int y_t
   if (int rc = accum_check(ctx, "raster_accum", rasters, n_frames, y_t, x_t, shifts, shift_units, img_h, img_w, state)) return rc;
   if (n_frames == 0) return TSDR_OK;
   const size_t P = (size_t)y_t * (size_t)x_t, n = (size_t)n_frames;
-  float *d_r = (float *)ctx->scratch(WS_IN, n * P * 4);
-  float *d_state = (float *)ctx->scratch(WS_AUX, P * 4);
-  int *d_shifts = shifts ? (int *)ctx->scratch(WS_MISC, n * 8) : nullptr;
-  if (!d_r || !d_state || (shifts && !d_shifts)) return TSDR_ENOMEM;
-  TSDR_HIP(ctx, hipMemcpyAsync(d_r, rasters, n * P * 4, hipMemcpyHostToDevice, ctx->stream));
-  TSDR_HIP(ctx, hipMemcpyAsync(d_state, state, P * 4, hipMemcpyHostToDevice, ctx->stream));
-  if (shifts) TSDR_HIP(ctx, hipMemcpyAsync(d_shifts, shifts, n * 8, hipMemcpyHostToDevice, ctx->stream));
-  if (int rc = accum_launch(ctx, d_r, n_frames, y_t, x_t, d_shifts, shift_units, img_h, img_w, alpha, d_state)) return rc;
-  TSDR_HIP(ctx, hipMemcpyAsync(state, d_state, P * 4, hipMemcpyDeviceToHost, ctx->stream));
-  return wait_stream(ctx, ctx->stream, __func__);
+  HostStage st(ctx);
+  const float *d_r = (const float *)st.in(WS_IN, rasters, n * P * 4);
+  float *d_state = (float *)st.inout(WS_AUX, state, P * 4, true);
+  const int *d_shifts = (const int *)st.in(WS_MISC, shifts, n * 8);
+  return st.run(__func__, [&] { return accum_launch(ctx, d_r, n_frames, y_t, x_t, d_shifts, shift_units, img_h, img_w, alpha, d_state); });
 }
 
 int tsdr_frames_hires_iq_d(tsdr_ctx *ctx, tsdr_sync *sync, const void *iq, int iq_fmt, float scale, size_t nEch, size_t S, int y_t,

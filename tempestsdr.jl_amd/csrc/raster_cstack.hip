@@ -204,23 +204,13 @@ int stack_entry(tsdr_ctx *ctx, const char *fn, const char *what, FoldCall c, boo
   if (device) return fold_launch<Stacked>(ctx, c, f);
   const size_t P = (size_t)c.y_t * (size_t)c.x_t;
   const size_t in_bytes = c.n * iq_bytes(f), z_bytes = 8 * P, mag_bytes = (4 * P + 7) & ~(size_t)7;
-  float *h_z = c.state, *h_mag = c.mag;
-  double *h_info = c.info;
-  void *d_iq = ctx->scratch(WS_IN, in_bytes);
-  void *d_z = ctx->scratch(WS_OUT, z_bytes);
-  char *d_aux = (char *)ctx->scratch(WS_AUX, mag_bytes + 8 * TSDR_CSTACK_INFO);
-  if (!d_iq || !d_z || !d_aux) return TSDR_ENOMEM;
-  TSDR_HIP(ctx, hipMemcpyAsync(d_iq, c.iq, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-  if (c.alpha != 0.f) TSDR_HIP(ctx, hipMemcpyAsync(d_z, h_z, z_bytes, hipMemcpyHostToDevice, ctx->stream));
-  c.iq = d_iq;
-  c.state = (float *)d_z;
-  c.mag = h_mag ? (float *)d_aux : nullptr;
-  c.info = h_info ? (double *)(d_aux + mag_bytes) : nullptr;
-  if (int rc = fold_launch<Stacked>(ctx, c, f)) return rc;
-  TSDR_HIP(ctx, hipMemcpyAsync(h_z, d_z, z_bytes, hipMemcpyDeviceToHost, ctx->stream));
-  if (h_mag) TSDR_HIP(ctx, hipMemcpyAsync(h_mag, c.mag, 4 * P, hipMemcpyDeviceToHost, ctx->stream));
-  if (h_info) TSDR_HIP(ctx, hipMemcpyAsync(h_info, c.info, 8 * TSDR_CSTACK_INFO, hipMemcpyDeviceToHost, ctx->stream));
-  return wait_stream(ctx, ctx->stream, what);
+  HostStage st(ctx);
+  c.iq = st.in(WS_IN, c.iq, in_bytes);
+  c.state = (float *)st.inout(WS_OUT, c.state, z_bytes, c.alpha != 0.f);
+  (void)st.reserve(WS_AUX, mag_bytes + 8 * TSDR_CSTACK_INFO);   // mag, then info (8-byte aligned), either absent or present
+  c.mag = (float *)st.out(WS_AUX, c.mag, 4 * P);
+  c.info = (double *)st.out(WS_AUX, c.info, 8 * TSDR_CSTACK_INFO);
+  return st.run(what, [&] { return fold_launch<Stacked>(ctx, c, f); });
 }
 
 FoldCall stack_call(const void *iq, int iq_fmt, float scale, size_t n, double t0, double T, double kappa, double phi, int n_frames, int y_t,

@@ -341,32 +341,25 @@ int tsdr_raster_register(tsdr_ctx *ctx, const float *rasters, int n_frames, int 
   if (n_frames == 0) return TSDR_OK;
   if (n_frames > 0x3fffffff) return set_err(ctx, TSDR_EINVAL, "raster_register: n_frames must be below 2^30");
   const size_t P = (size_t)y_t * (size_t)x_t, n = (size_t)n_frames, sbytes = n * scores_per_frame(d_y, d_x) * sizeof(double);
-  float *d_r = (float *)ctx->scratch(WS_IN, n * P * 4);
-  float *d_ref = ref ? (float *)ctx->scratch(WS_AUX, P * 4) : nullptr;
-  int *d_shifts = shifts ? (int *)ctx->scratch(WS_MISC, n * 8) : nullptr;
-  char *d_out = (char *)ctx->scratch(WS_OUT, n * 8 + sbytes);   // shifts_out (n * 8 bytes), then the scores
-  if (!d_r || (ref && !d_ref) || (shifts && !d_shifts) || !d_out) return TSDR_ENOMEM;
-  TSDR_HIP(ctx, hipMemcpyAsync(d_r, rasters, n * P * 4, hipMemcpyHostToDevice, ctx->stream));
-  if (ref) TSDR_HIP(ctx, hipMemcpyAsync(d_ref, ref, P * 4, hipMemcpyHostToDevice, ctx->stream));
-  if (shifts) TSDR_HIP(ctx, hipMemcpyAsync(d_shifts, shifts, n * 8, hipMemcpyHostToDevice, ctx->stream));
-  if (int rc = register_launch(ctx, d_r, n_frames, y_t, x_t, d_ref, d_shifts, shift_units, img_h, img_w, d_y, d_x, (int *)d_out,
-                               (double *)(d_out + n * 8)))
-    return rc;
-  TSDR_HIP(ctx, hipMemcpyAsync(shifts_out, d_out, n * 8, hipMemcpyDeviceToHost, ctx->stream));
-  if (scores) TSDR_HIP(ctx, hipMemcpyAsync(scores, d_out + n * 8, sbytes, hipMemcpyDeviceToHost, ctx->stream));
-  return wait_stream(ctx, ctx->stream, __func__);
+  HostStage st(ctx);
+  const float *d_r = (const float *)st.in(WS_IN, rasters, n * P * 4);
+  const float *d_ref = (const float *)st.in(WS_AUX, ref, P * 4);
+  const int *d_shifts = (const int *)st.in(WS_MISC, shifts, n * 8);
+  char *d_out = (char *)st.reserve(WS_OUT, n * 8 + sbytes);   // shifts_out (n * 8 bytes), then the scores: the device form
+  (void)st.out(WS_OUT, shifts_out, n * 8);                    // always writes both
+  (void)st.out(WS_OUT, scores, sbytes);
+  return st.run(__func__, [&] {
+    return register_launch(ctx, d_r, n_frames, y_t, x_t, d_ref, d_shifts, shift_units, img_h, img_w, d_y, d_x, (int *)d_out, (double *)(d_out + n * 8));
+  });
 }
 
 int tsdr_frames_hires_shifts(tsdr_ctx *ctx, int max_frames, int *shifts, int *n_frames) {
   if (!ctx || max_frames < 0 || (max_frames && !shifts)) return TSDR_EINVAL;
-  if (int rc = pipe_drain(ctx)) return rc;
   const tsdr_ctx::Buf &b = ctx->ws[WS_HIRES_SHIFTS];
   const int F = b.p && (size_t)ctx->hires_shifts_n * 8 <= b.cap ? ctx->hires_shifts_n : 0;
   if (n_frames) *n_frames = F;
   const int nf = F < max_frames ? F : max_frames;
-  if (nf == 0) return wait_stream(ctx, ctx->stream, __func__);
-  TSDR_HIP(ctx, hipMemcpyAsync(shifts, b.p, (size_t)nf * 8, hipMemcpyDeviceToHost, ctx->stream));
-  return wait_stream(ctx, ctx->stream, __func__);
+  return read_back(ctx, true, shifts, b.p, (size_t)nf * 8, __func__);   // (no frames: the drain and the wait alone)
 }
 
 }  // extern "C"

@@ -380,19 +380,21 @@ static const double2 *tw64_table(tsdr_ctx *ctx, size_t n) {
   auto it = ctx->tw64.find(n);
   if (it != ctx->tw64.end()) return it->second;
   const long double w0 = 6.283185307179586476925286766559005768L / (long double)n;
-  std::vector<double2> t;
-  auto put = [&](size_t e) { t.push_back(make_double2((double)cosl(w0 * (long double)e), -(double)sinl(w0 * (long double)e))); };
+  const size_t count = n <= kTwSplit ? n : kTwSplit + ceil_div(n, kTwSplit), bytes = count * sizeof(double2);
+  HostStage st(ctx);   // (owns the table's host image: a wait that gives up leaves the copy reading it)
+  double2 *t = (double2 *)st.temp(bytes), *d = nullptr;
+  if (!t || hipMalloc((void **)&d, bytes) != hipSuccess) { set_err(ctx, TSDR_ENOMEM, "f64 twiddle table"); return nullptr; }
+  size_t m = 0;
+  auto put = [&](size_t e) { t[m++] = make_double2((double)cosl(w0 * (long double)e), -(double)sinl(w0 * (long double)e)); };
   if (n <= kTwSplit) {
     for (size_t e = 0; e < n; ++e) put(e);
   } else {
     for (size_t e = 0; e < kTwSplit; ++e) put(e);
     for (size_t h = 0; h * kTwSplit < n; ++h) put(h * kTwSplit);
   }
-  double2 *d = nullptr;
-  if (hipMalloc((void **)&d, t.size() * sizeof(double2)) != hipSuccess) { set_err(ctx, TSDR_ENOMEM, "f64 twiddle table"); return nullptr; }
-  if (hipMemcpyAsync(d, t.data(), t.size() * sizeof(double2), hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-      wait_stream(ctx, ctx->stream, "f64 twiddle table")) {
-    (void)hipFree(d);
+  st.in_to(d, t, bytes);
+  if (st.run("f64 twiddle table")) {
+    if (!st.pending()) (void)hipFree(d);   // (a copy that may still run keeps its target: hipFree would wait for it without a bound)
     set_err(ctx, TSDR_EHIP, "f64 twiddle table upload");
     return nullptr;
   }
@@ -490,7 +492,10 @@ static int fft64_rows(tsdr_ctx *ctx, double2 *X, double2 *T, size_t n, size_t B,
 static const double2 *blu64_tables(tsdr_ctx *ctx, size_t n, size_t L, double2 *X, double2 *T) {
   auto it = ctx->blu64.find(n);
   if (it != ctx->blu64.end()) return it->second;
-  std::vector<double2> h(n + L, make_double2(0.0, 0.0));
+  HostStage st(ctx);   // (owns the tables' host image, as in tw64_table)
+  double2 *h = (double2 *)st.temp((n + L) * sizeof(double2));
+  if (!h) { set_err(ctx, TSDR_ENOMEM, "f64 Bluestein tables"); return nullptr; }
+  for (size_t k = 0; k < n + L; ++k) h[k] = make_double2(0.0, 0.0);
   const long double pi = 3.141592653589793238462643383279502884L;
   for (size_t k = 0; k < n; ++k) {
     const unsigned long long e = (unsigned long long)(((unsigned __int128)k * k) % (2 * (unsigned __int128)n));
@@ -502,12 +507,17 @@ static const double2 *blu64_tables(tsdr_ctx *ctx, size_t n, size_t L, double2 *X
   }
   double2 *d = nullptr;
   if (hipMalloc((void **)&d, (n + L) * sizeof(double2)) != hipSuccess) { set_err(ctx, TSDR_ENOMEM, "f64 Bluestein tables"); return nullptr; }
-  int rc = hipMemcpyAsync(X, h.data() + n, L * sizeof(double2), hipMemcpyHostToDevice, ctx->stream) == hipSuccess ? 0 : TSDR_EHIP;
+  st.in_to(X, h + n, L * sizeof(double2));   // the wrapped conj chirp, transformed in place below
+  st.in_to(d, h, n * sizeof(double2));       // (goes up with it now, not behind the transform: the two touch different memory)
+  int rc = st.begin();
   if (!rc) rc = fft64_rows(ctx, X, T, L, 1, -1.0);
-  if (!rc && hipMemcpyAsync(d, h.data(), n * sizeof(double2), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = TSDR_EHIP;
   if (!rc && hipMemcpyAsync(d + n, X, L * sizeof(double2), hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) rc = TSDR_EHIP;
-  if (!rc) rc = wait_stream(ctx, ctx->stream, "f64 Bluestein tables");
-  if (rc) { (void)hipFree(d); set_err(ctx, TSDR_EHIP, "f64 Bluestein tables"); return nullptr; }
+  if (!rc) rc = st.finish("f64 Bluestein tables");
+  if (rc) {
+    if (!st.pending()) (void)hipFree(d);   // (as in tw64_table)
+    set_err(ctx, TSDR_EHIP, "f64 Bluestein tables");
+    return nullptr;
+  }
   ctx->blu64[n] = d;
   return d;
 }

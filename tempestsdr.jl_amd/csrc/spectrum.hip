@@ -655,17 +655,22 @@ int resampler_init_kind(tsdr_ctx *ctx, size_t bufferSize, int upCoeff, bool f64,
   }
   // H0 = round.(H .* exp(im*groupDelay*pulsation)) with H[1:bound]=1  (:85-91): entries are
   // integers in {-1,0,1}; evaluated on the host in f64 like the reference's broadcast.
-  std::vector<double2> H0(N, make_double2(0.0, 0.0));
-  const double bound_d = nearbyint((double)N / (double)upCoeff / 2.0);
-  const size_t bound = bound_d < (double)N ? (size_t)bound_d : N;
-  const LpfPhase st = lpf_phase_step(N);
-  for (size_t k = 0; k < bound; ++k) {
-    const double th = lpf_phase(k, st);
-    H0[k] = make_double2(nearbyint(cos(th)), nearbyint(sin(th)));
+  {
+    HostStage up(ctx);   // (owns H0: a wait that gives up leaves the copy reading it)
+    double2 *H0 = (double2 *)up.temp(N * sizeof(double2));
+    const double bound_d = nearbyint((double)N / (double)upCoeff / 2.0);
+    const size_t bound = bound_d < (double)N ? (size_t)bound_d : N;
+    const LpfPhase st = lpf_phase_step(N);
+    for (size_t k = 0; H0 && k < N; ++k) H0[k] = make_double2(0.0, 0.0);
+    for (size_t k = 0; H0 && k < bound; ++k) {
+      const double th = lpf_phase(k, st);
+      H0[k] = make_double2(nearbyint(cos(th)), nearbyint(sin(th)));
+    }
+    up.in_to(r->H, H0, N * sizeof(double2));
+    const int rc = up.run("init_resampler upload");
+    if (rc && up.pending()) return rc;   // (a stuck stream keeps the tables)
+    if (rc) { (void)hipFree(scratch); tsdr_resampler_free(r); return rc; }
   }
-  hipError_t e = hipMemcpyAsync(r->H, H0.data(), N * sizeof(double2), hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess) { if (int w = tsdr::wait_stream(ctx, ctx->stream, "init_resampler upload")) return w; }   // (a stuck stream keeps the tables)
-  if (e != hipSuccess) { (void)hipFree(scratch); tsdr_resampler_free(r); return hip_fail(ctx, e, "init_resampler upload"); }
   // h = ifft(H0) .* blackman  (ifft on ComplexF32 data in the reference, the window and everything after it in f64);
   // H = fft(h) .* (-1)^k -- on the device in f64 (fft64.hip)
   // (every launch is checked where it is made: a failure here must not surface as the sticky error of a later, unrelated
@@ -693,7 +698,7 @@ int resampler_init_kind(tsdr_ctx *ctx, size_t bufferSize, int upCoeff, bool f64,
     for (size_t e = 0; e < 1024; ++e) tw[e] = make_double2((double)cosl(w0 * (long double)e), (double)sinl(w0 * (long double)e));
     for (size_t h = 0; h < nhi; ++h) tw[1024 + h] = make_double2((double)cosl(w0 * (long double)(1024 * h)), (double)sinl(w0 * (long double)(1024 * h)));
     if (hipMalloc((void **)&r->tw, tw.size() * sizeof(double2)) != hipSuccess) { tsdr_resampler_free(r); return set_err(ctx, TSDR_ENOMEM, "init_resampler: allocation failed"); }
-    e = hipMemcpy(r->tw, tw.data(), tw.size() * sizeof(double2), hipMemcpyHostToDevice);
+    const hipError_t e = hipMemcpy(r->tw, tw.data(), tw.size() * sizeof(double2), hipMemcpyHostToDevice);
     if (e != hipSuccess) { tsdr_resampler_free(r); return hip_fail(ctx, e, "init_resampler upload"); }
   }
   *out = r;
@@ -868,20 +873,20 @@ int tsdr_resampler_lpf(tsdr_resampler *r, float *H_host) {
   if (!r || !H_host) return TSDR_EINVAL;
   tsdr_ctx *ctx = r->ctx;
   // (a Float64 resampler narrows in its own buffer: no f64 object moves a workspace of the f32 paths)
-  float2 *tmp = r->f64 ? (float2 *)r->A64 : (float2 *)ctx->scratch(WS_FFT_A, r->sizeFFT * sizeof(float2));
-  if (!tmp) return TSDR_ENOMEM;
-  TSDR_LAUNCH(ctx, "lpf_c32", k_c64_to_c32, dim3(stream_grid(ctx, r->sizeFFT)), dim3(256), 0, (const double2 *)r->H, r->sizeFFT, tmp);
-  TSDR_HIP(ctx, hipMemcpyAsync(H_host, tmp, r->sizeFFT * sizeof(float2), hipMemcpyDeviceToHost, ctx->stream));
-  { int _w = tsdr::wait_stream(ctx, ctx->stream, __func__); if (_w) return _w; }
-  return TSDR_OK;
+  HostStage st(ctx);
+  const size_t bytes = r->sizeFFT * sizeof(float2);
+  float2 *tmp = (float2 *)r->A64;
+  if (r->f64) st.out_from(tmp, H_host, bytes);
+  else tmp = (float2 *)st.out(WS_FFT_A, H_host, bytes);
+  return st.run(__func__, [&]() -> int {
+    TSDR_LAUNCH(ctx, "lpf_c32", k_c64_to_c32, dim3(stream_grid(ctx, r->sizeFFT)), dim3(256), 0, (const double2 *)r->H, r->sizeFFT, tmp);
+    return TSDR_OK;
+  });
 }
 
 int tsdr_resampler_lpf64(tsdr_resampler *r, double *H_host) {
   if (!r || !H_host) return TSDR_EINVAL;
-  tsdr_ctx *ctx = r->ctx;
-  TSDR_HIP(ctx, hipMemcpyAsync(H_host, r->H, r->sizeFFT * sizeof(double2), hipMemcpyDeviceToHost, ctx->stream));
-  { int _w = tsdr::wait_stream(ctx, ctx->stream, __func__); if (_w) return _w; }
-  return TSDR_OK;
+  return read_back(r->ctx, false, H_host, r->H, r->sizeFFT * sizeof(double2), __func__);
 }
 
 int tsdr_fft_z2z(tsdr_ctx *ctx, const double *in, double *out, size_t n, int dir) {
@@ -893,13 +898,14 @@ int tsdr_fft_z2z(tsdr_ctx *ctx, const double *in, double *out, size_t n, int dir
     (void)hipFree(d); (void)hipFree(sc);
     return set_err(ctx, TSDR_ENOMEM, "fft_z2z: allocation failed");
   }
-  int rc = TSDR_OK;
-  hipError_t e = hipMemcpyAsync(d, in, n * sizeof(double2), hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess) rc = fft64_d(ctx, d, sc, n, dir);
-  if (e == hipSuccess && !rc) e = hipMemcpyAsync(out, d, n * sizeof(double2), hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess) { if (int w = tsdr::wait_stream(ctx, ctx->stream, "fft_z2z")) return rc ? rc : w; }   // (a stuck stream keeps its scratch)
+  HostStage st(ctx);
+  st.in_to(d, in, n * sizeof(double2));
+  st.out_from(d, out, n * sizeof(double2));
+  int rc = st.begin();
+  if (!rc) rc = fft64_d(ctx, d, sc, n, dir);
+  // (a failed call's launches drain before its scratch goes as well)
+  if (int w = rc ? tsdr::wait_stream(ctx, ctx->stream, "fft_z2z") : st.finish("fft_z2z")) return rc ? rc : w;   // (a stuck stream keeps its scratch)
   (void)hipFree(d); (void)hipFree(sc);
-  if (!rc && e != hipSuccess) rc = hip_fail(ctx, e, "fft_z2z");
   return rc;
 }
 

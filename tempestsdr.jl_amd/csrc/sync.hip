@@ -1027,11 +1027,11 @@ int tsdr_sync_reset(tsdr_sync *s) {
     TSDR_HIP(ctx, hipMemsetAsync(s->beta_x, 0, nbx * 4, ctx->stream));
     TSDR_HIP(ctx, hipMemsetAsync(s->beta_y, 0, nby * 4, ctx->stream));
   }
-  const int one[4] = {1, 1, 0, 0};  // findmax -- and findmin -- of an all-zero beta_y is index (1,1)
+  static const int one[4] = {1, 1, 0, 0};  // findmax -- and findmin -- of an all-zero beta_y is index (1,1)
   s->cur = 0;
-  TSDR_HIP(ctx, hipMemcpyAsync(s->pending, one, 16, hipMemcpyHostToDevice, ctx->stream));
-  { int _w = tsdr::wait_stream(ctx, ctx->stream, __func__); if (_w) return _w; }
-  return TSDR_OK;
+  HostStage st(ctx);
+  st.in_to(s->pending, one, 16);
+  return st.run(__func__);
 }
 
 void tsdr_sync_free(tsdr_sync *s) {
@@ -1079,15 +1079,11 @@ int tsdr_vsync(tsdr_sync *s, const float *img, int *s_y, int *s_x) {
   tsdr_ctx *ctx = s->ctx;
   if (s->f64) return set_err(ctx, TSDR_EINVAL, "tsdr_vsync: SyncXY{Float64} state (use tsdr_vsync_f64)");
   const size_t bytes = (size_t)s->y_t * s->x_t * 4;
-  float *d = (float *)ctx->scratch(WS_IN, bytes);
-  int *didx = (int *)ctx->scratch(WS_OUT, 16);
-  if (!d || !didx) return TSDR_ENOMEM;
-  TSDR_HIP(ctx, hipMemcpyAsync(d, img, bytes, hipMemcpyHostToDevice, ctx->stream));
-  int rc = tsdr_vsync_d(s, d, didx);
-  if (rc) return rc;
-  int hidx[2];
-  TSDR_HIP(ctx, hipMemcpyAsync(hidx, didx, 8, hipMemcpyDeviceToHost, ctx->stream));
-  { int _w = tsdr::wait_stream(ctx, ctx->stream, __func__); if (_w) return _w; }
+  HostStage st(ctx);
+  const int *hidx = (const int *)st.small(8);
+  const float *d = (const float *)st.in(WS_IN, img, bytes);
+  int *didx = (int *)st.out(WS_OUT, (void *)hidx, 8);
+  if (int rc = st.run(__func__, [&] { return tsdr_vsync_d(s, d, didx); })) return rc;
   *s_y = hidx[0]; *s_x = hidx[1];
   return TSDR_OK;
 }
@@ -1097,13 +1093,8 @@ int tsdr_sync_beta(tsdr_sync *s, int which, float *beta_host) {
   tsdr_ctx *ctx = s->ctx;
   if (s->f64) return set_err(ctx, TSDR_EINVAL, "tsdr_sync_beta: SyncXY{Float64} state (use tsdr_sync_beta_f64)");
   const size_t n = which == 0 ? (size_t)(1 + s->wmax_x - s->wmin_x) * s->x_t : (size_t)(1 + s->wmax_y - s->wmin_y) * s->y_t;
-  {  // submitted buffers fill the beta sets on the pipeline's internal streams: they come first
-    int rc = pipe_drain(ctx);
-    if (rc) return rc;
-  }
-  TSDR_HIP(ctx, hipMemcpyAsync(beta_host, which == 0 ? s->beta_x : s->beta_y, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-  { int _w = tsdr::wait_stream(ctx, ctx->stream, __func__); if (_w) return _w; }
-  return TSDR_OK;
+  // (drained: submitted buffers fill the beta sets on the pipeline's internal streams, they come first)
+  return read_back(ctx, true, beta_host, which == 0 ? s->beta_x : s->beta_y, n * 4, __func__);
 }
 
 int tsdr_fill_beta(tsdr_ctx *ctx, const float *cv, int n, int w_min, int w_max, float *beta) {

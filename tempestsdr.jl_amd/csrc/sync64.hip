@@ -235,15 +235,11 @@ int tsdr_vsync_f64(tsdr_sync *s, const double *img, int *s_y, int *s_x) {
   tsdr_ctx *ctx = s->ctx;
   if (int rc = sync64_argmax_check(ctx, s, "tsdr_vsync_f64")) return rc;
   const size_t bytes = (size_t)s->y_t * s->x_t * 8;
-  double *d = (double *)ctx->scratch(WS_F64_A, bytes);
-  int *didx = (int *)ctx->scratch(WS_F64_B, 16);
-  if (!d || !didx) return TSDR_ENOMEM;
-  TSDR_HIP(ctx, hipMemcpyAsync(d, img, bytes, hipMemcpyHostToDevice, ctx->stream));
-  int rc = tsdr_vsync_f64_d(s, d, didx);
-  if (rc) return rc;
-  int hidx[2];
-  TSDR_HIP(ctx, hipMemcpyAsync(hidx, didx, 8, hipMemcpyDeviceToHost, ctx->stream));
-  { int _w = tsdr::wait_stream(ctx, ctx->stream, __func__); if (_w) return _w; }
+  HostStage st(ctx);
+  const int *hidx = (const int *)st.small(8);
+  const double *d = (const double *)st.in(WS_F64_A, img, bytes);
+  int *didx = (int *)st.out(WS_F64_B, (void *)hidx, 8);
+  if (int rc = st.run(__func__, [&] { return tsdr_vsync_f64_d(s, d, didx); })) return rc;
   *s_y = hidx[0]; *s_x = hidx[1];
   return TSDR_OK;
 }
@@ -253,9 +249,7 @@ int tsdr_sync_beta_f64(tsdr_sync *s, int which, double *beta_host) {
   tsdr_ctx *ctx = s->ctx;
   if (int rc = sync64_argmax_check(ctx, s, "tsdr_sync_beta_f64")) return rc;
   const size_t n = which == 0 ? (size_t)(1 + s->wmax_x - s->wmin_x) * s->x_t : (size_t)(1 + s->wmax_y - s->wmin_y) * s->y_t;
-  TSDR_HIP(ctx, hipMemcpyAsync(beta_host, which == 0 ? s->beta64_x : s->beta64_y, n * 8, hipMemcpyDeviceToHost, ctx->stream));
-  { int _w = tsdr::wait_stream(ctx, ctx->stream, __func__); if (_w) return _w; }
-  return TSDR_OK;
+  return read_back(ctx, false, beta_host, which == 0 ? s->beta64_x : s->beta64_y, n * 8, __func__);
 }
 
 int tsdr_fill_beta_f64(tsdr_ctx *ctx, const double *cv, int n, int w_min, int w_max, double *beta) {

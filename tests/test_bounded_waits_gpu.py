@@ -100,6 +100,79 @@ def test_synchronize_gives_up_after_wait_ms_and_says_where(tsdr):
         ctx.close()
 
 
+def test_host_forms_give_up_or_finish_while_the_stream_is_held(tsdr):
+    """The host-pointer forms behind a held stream (csrc/host_stage.h): vsync (its index pair lands in the context's pinned
+    block), download of 4 KiB, circshift_neg on 8 x 20 (host_map).  Each either raises after "wait_ms" -- its copies stay enqueued:
+    the caller's arrays are kept alive here until a later synchronize succeeds, as tempest_hip.h asks -- or returns the right data
+    once the hold has passed.  Afterwards the context works, and the same calls on fresh objects give the un-held values."""
+    import ctypes as C
+
+    import sync_cases as SC
+    from tempestsdr_jl_amd import api
+    HOLD, BOUND = 0.6, 0.1
+    img = SC.image("noise", 8, 20).ravel(order="F").copy()
+    payload = np.arange(1024, dtype=np.float32)
+    keep = []   # every array a call was handed, until the stream has completed
+
+    def three(ctx, sync, d_payload):
+        """-> [(value or None when the call gave up, seconds)] of the three calls"""
+        def vsync():
+            sy, sx = C.c_int(0), C.c_int(0)
+            api.check(ctx.h, ctx.lib.tsdr_vsync(sync.h, api._ptr(img), C.byref(sy), C.byref(sx)), "tsdr_vsync")
+            return sy.value, sx.value
+
+        def download():
+            out = np.zeros_like(payload)
+            keep.append(out)
+            ctx.call("tsdr_download", api._ptr(out), C.c_void_p(d_payload), out.nbytes)
+            return out.tobytes()
+
+        def circshift():
+            out = np.zeros_like(img)
+            keep.append(out)
+            ctx.call("tsdr_circshift_neg", api._ptr(img), 8, 20, 3, 7, api._ptr(out))
+            return out.tobytes()
+
+        res = []
+        for fn in (vsync, download, circshift):
+            t0 = time.perf_counter()
+            try:
+                val = fn()
+            except tsdr.TempestHIPError as e:
+                assert "bounded host wait" in str(e), str(e)
+                val = None
+            res.append((val, time.perf_counter() - t0))
+        return res
+
+    ctx = tsdr.Context(0)
+    syncs = [tsdr.SyncXY(ctx, 8, 20) for _ in range(4)]
+    d_payload = ctx.upload(payload)
+    try:
+        three(ctx, syncs[0], d_payload)                              # warm: workspaces, the pinned block, kernels
+        want = [v for v, _ in three(ctx, syncs[1], d_payload)]
+        assert None not in want and want[1] == payload.tobytes()
+        ctx.synchronize()
+        ctx.set_option("wait_ms", int(BOUND * 1000))
+        ctx.call("tsdr_debug_hold_stream", int(HOLD * 1000))
+        held = three(ctx, syncs[2], d_payload)
+        gave_up = sum(v is None for v, _ in held)
+        for (v, dt), w in zip(held, want):
+            assert v is None or v == w
+            assert dt < HOLD + BOUND + 0.5, held
+        assert ctx.wait_stats()[0] == gave_up
+        time.sleep(HOLD + 0.1)
+        ctx.set_option("wait_ms", 30000)
+        ctx.synchronize()                                            # the hold is over: every copy left enqueued has landed
+        assert [v for v, _ in three(ctx, syncs[3], d_payload)] == want
+        assert ctx.wait_stats()[0] == gave_up
+    finally:
+        for s in syncs:
+            s.close()
+        ctx.synchronize()
+        ctx.dev_free(d_payload)
+        ctx.close()
+
+
 def test_destroy_abandons_a_context_whose_stream_is_stuck(tsdr):
     """tsdr_destroy on a context whose stream does not complete within "wait_ms" returns (the context is abandoned: hipFree
     would wait for the device without a bound) instead of holding the caller."""
