@@ -257,6 +257,27 @@ static inline DownPlan plan_down_tiles(size_t S, int y_t, int x_t, int h_out, in
 }
 
 // ---- route 3: the tile walk ----------------------------------------------------------------------------------
+// The instantiations of k_raster_fast<true, f32w, down, pw, out, vw, rec4, iqf> that plan_raster can name, for any request it
+// accepts -- stated once: plan_raster refuses a step outside it, resample.hip:launch_fast builds exactly these kernels and
+// refuses every other value, plan_dump --table prints them.  Each rule follows from a condition of plan_raster's FAST branch
+// (quoted; NOTEBOOK.md, "kernel instantiations", says how to extend the set when a planner change needs a new kernel):
+constexpr bool fast_instance(bool f32w, bool down, int pw, bool out, int vw, bool rec4, int iqf) {
+  (void)f32w;   // either position advance at any tile: `w32 = 2 * P < 2^24 && q.tiles_l <= 128 && q.tiles_p <= 128`
+  const bool pw_any = pw == 1 || pw == 2 || pw == 4 || pw == 8 || pw == 16 || pw == 32;   // `s.pw = max(q.TP / 4, 1)`, TP = 4 .. 128
+  // `dn = want_down && q.TP >= 32 && ...`: the in-walk downgrade runs on tiles of 32 pixels and more
+  if (down && pw < 8) return false;
+  // `if (!dn && !out) return TSDR_OK`: a step that neither downgrades nor writes the raster is never made
+  if (!down && !out) return false;
+  // `want_down = ... && y_t >= 2 * 64 && ...` and `VW = v4 ? 1 : y_t >= 2 * 64 ? 2 : 1` (v4 is IK_FAST4's): the downgrade
+  // runs two wavefronts high; a raster shorter than 128 lines gets one, and no downgrade
+  if (down ? vw != 2 : (vw != 1 && vw != 2)) return false;
+  // `s.rec4 = rec4 && dn`, and the format is a template argument exactly then: `if (s.rec4) s.iqf = ...`, else IQF_RT
+  if (rec4 && !down) return false;
+  const bool iqf_ok = rec4 ? (iqf == IQF_CF32 || iqf == IQF_SC16 || iqf == IQF_SC8 || iqf == IQF_UC8) : iqf == IQF_RT;
+  return pw_any && iqf_ok;
+}
+constexpr const char *kNoFastInstance = "raster: the tile plan names a kernel that is not built";
+
 // sig_to_image for `frames` consecutive frames (`out`: the raster is written) and, with `down`, the (h_out, w_out) image of each
 // frame from the same launch where the tiling allows: did_down says so.  Appends at most one step.
 static inline int plan_raster(const PlanOpts &o, const ImageReq &r, int frames, bool out, bool down, int h_out, int w_out, bool sums,
@@ -318,7 +339,7 @@ static inline int plan_raster(const PlanOpts &o, const ImageReq &r, int frames, 
     // wavefronts stacked vertically per workgroup (see k_raster_fast).  Measured on C2: 1 -> 0.121 ms, 2 -> 0.118 ms,
     // 4 (1024 threads, 77 KiB LDS) -> 0.131 ms; again with f32 samples (REC4, 12 KiB): 130 / 124 / 138 us for the launch
     // round 6: four lines per lane (k_raster_fast4) wherever the f32-sample walk with the in-walk image writes rasters from
-    // 128-pixel tiles -- C2's route: a quarter fewer write requests for the same bytes (option "raster_v4", default on)
+    // 128-pixel tiles -- C2's route: a quarter fewer write requests for the same bytes (option "raster_v4", default off)
     const bool v4 = o.raster_v4 > 0 && rec4_ok && dn && q.TP == 128 && out && 2 * P < (size_t(1) << 24) && y_t >= 512 &&
                     x_t <= 127 * 128 && o.raster_split == 0 &&
                     (q.iqf.kind == IQK_CF32 || q.iqf.kind == IQK_SC16);   // (k_raster_fast4 exists for those two formats only)
@@ -375,6 +396,7 @@ static inline int plan_raster(const PlanOpts &o, const ImageReq &r, int frames, 
       // the f32-sample instantiations (the hot ones) exist once per input format, the others read it from the parameters
       s.rec4 = (rec4 && dn) ? 1 : 0;
       if (s.rec4) s.iqf = q.iqf.kind == IQK_SC16 ? IQF_SC16 : q.iqf.kind == IQK_SC8 ? IQF_SC8 : q.iqf.kind == IQK_UC8 ? IQF_UC8 : IQF_CF32;
+      if (!fast_instance(s.f32w, s.down, s.pw, s.out, s.vw, s.rec4, s.iqf)) return plan_fail(pl, kNoFastInstance);  // (no input gets here)
     }
     ++pl.nsteps;
     did_down = dn;

@@ -1105,7 +1105,8 @@ __global__ __launch_bounds__(256) void k_naive(const float *__restrict__ in, siz
 
 // ------------------------------------------------------------------------------------------------------------
 // launch_images: the walk over an ImagePlan (image_plan.h).  The planner decided everything; here each step's template
-// arguments select the instantiation, the pointers are filled in and the kernel is launched.  One helper per kernel family.
+// arguments select the instantiation, the pointers are filled in and the kernel is launched.  One helper per kernel family;
+// arguments that name no instantiation are refused (no_kernel), never mapped onto some kernel.
 // ------------------------------------------------------------------------------------------------------------
 struct StepPtrs {   // what a step reads and writes: one frame's worth in the per-frame fallback, else the whole buffer's
   const float *in; size_t in_stride;
@@ -1117,68 +1118,50 @@ struct StepPtrs {   // what a step reads and writes: one frame's worth in the pe
 #define DOWN_ARGS p.in, p.in_stride, q, p.down, p.down_stride, s.lds_main
 #define STEP_GRID dim3(s.grid[0], s.grid[1], s.grid[2])
 
-template <bool W32, bool D, int PW, bool OUT, int VW>
-static int fast_k(tsdr_ctx *ctx, const ImageStep &s, const TileParams &q, const StepPtrs &p) {
-  const dim3 grid = STEP_GRID, block(s.block);
-  if (!s.rec4) {
-    TSDR_LAUNCH(ctx, s.name, (k_raster_fast<true, W32, D, PW, OUT, VW>), grid, block, s.lds, FAST_ARGS);
-  } else if (s.iqf == IQF_SC16) {
-    TSDR_LAUNCH(ctx, s.name, (k_raster_fast<true, W32, true, PW, OUT, VW, true, IQF_SC16>), grid, block, s.lds, FAST_ARGS);
-  } else if (s.iqf == IQF_SC8) {
-    TSDR_LAUNCH(ctx, s.name, (k_raster_fast<true, W32, true, PW, OUT, VW, true, IQF_SC8>), grid, block, s.lds, FAST_ARGS);
-  } else if (s.iqf == IQF_UC8) {
-    TSDR_LAUNCH(ctx, s.name, (k_raster_fast<true, W32, true, PW, OUT, VW, true, IQF_UC8>), grid, block, s.lds, FAST_ARGS);
-  } else {
-    TSDR_LAUNCH(ctx, s.name, (k_raster_fast<true, W32, true, PW, OUT, VW, true, IQF_CF32>), grid, block, s.lds, FAST_ARGS);
-  }
-  return TSDR_OK;
+// A run-time value and the compile-time values it may take.  with_consts(fn, Among<..>{a}, Among<..>{b}, ...) calls
+// fn(std::integral_constant<.., A>{}, std::integral_constant<.., B>{}, ...) for the listed values that a, b, ... equal, and
+// nothing when one of them equals none of its list.
+template <auto... Vs> struct Among { int v; };
+template <class F> static void with_consts(F &&fn) { fn(); }
+template <class F, auto... Vs, class... Rest>
+static void with_consts(F &&fn, Among<Vs...> a, Rest... rest) {
+  (void)((a.v == (int)Vs && (with_consts([&](auto... cs) { fn(std::integral_constant<decltype(Vs), Vs>{}, cs...); }, rest...), true)) || ...);
 }
-template <bool W32, bool D, int PW>
-static int fast_pw(tsdr_ctx *ctx, const ImageStep &s, const TileParams &q, const StepPtrs &p) {
-  if (s.out) return s.vw == 2 ? fast_k<W32, D, PW, true, 2>(ctx, s, q, p) : fast_k<W32, D, PW, true, 1>(ctx, s, q, p);
-  return s.vw == 2 ? fast_k<W32, D, PW, false, 2>(ctx, s, q, p) : fast_k<W32, D, PW, false, 1>(ctx, s, q, p);
+using AmongBool = Among<false, true>;
+// a step whose template arguments name no kernel built here: a planner bug (image_plan.h holds its steps to the same sets)
+static int no_kernel(tsdr_ctx *ctx, const ImageStep &s) {
+  assert(!"a plan step names a kernel instantiation");
+  return set_err(ctx, TSDR_EINVAL, "%s: no kernel %d<cplx=%d f32w=%d down=%d pw=%d out=%d vw=%d rec4=%d iqf=%d mode=%d sums=%d ld=%d>", s.name, s.kernel,
+                 s.cplx, s.f32w, s.down, s.pw, s.out, s.vw, s.rec4, s.iqf, s.mode, s.sums, s.ld);
 }
-template <bool W32, bool D>
-static int fast_wd(tsdr_ctx *ctx, const ImageStep &s, const TileParams &q, const StepPtrs &p) {
-  switch (s.pw) {
-    case 32: return fast_pw<W32, D, 32>(ctx, s, q, p);
-    case 16: return fast_pw<W32, D, 16>(ctx, s, q, p);
-    case 8: return fast_pw<W32, D, 8>(ctx, s, q, p);
-    case 4: return fast_pw<W32, D, 4>(ctx, s, q, p);
-    case 2: return fast_pw<W32, D, 2>(ctx, s, q, p);
-    default: return fast_pw<W32, D, 1>(ctx, s, q, p);
-  }
-}
+// "no instantiation matched" is kept apart from the launch's status (TSDR_OK or a negative TSDR_E*, passed on unchanged)
+constexpr int kNoMatch = 1;
+static_assert(TSDR_OK == 0 && TSDR_EINVAL < 0 && TSDR_EHIP < 0, "kNoMatch must be no status");
+#define LAUNCHED(...) [&]() -> int { TSDR_LAUNCH(ctx, s.name, __VA_ARGS__); return TSDR_OK; }()
+
+// k_raster_fast exists exactly where image_plan.h:fast_instance says the planner can name it
 static int launch_fast(tsdr_ctx *ctx, const ImageStep &s, const TileParams &q, const StepPtrs &p) {
-  if (s.f32w) return s.down ? fast_wd<true, true>(ctx, s, q, p) : fast_wd<true, false>(ctx, s, q, p);
-  return s.down ? fast_wd<false, true>(ctx, s, q, p) : fast_wd<false, false>(ctx, s, q, p);
+  int rc = kNoMatch;
+  with_consts([&](auto W32, auto D, auto PW, auto OUT, auto VW, auto R4, auto F) {
+    if constexpr (fast_instance(W32, D, PW, OUT, VW, R4, F))
+      rc = LAUNCHED((k_raster_fast<true, W32, D, PW, OUT, VW, R4, F>), STEP_GRID, dim3(s.block), s.lds, FAST_ARGS);
+  }, AmongBool{s.f32w}, AmongBool{s.down}, Among<1, 2, 4, 8, 16, 32>{s.pw}, AmongBool{s.out}, Among<1, 2>{s.vw}, AmongBool{s.rec4},
+     Among<IQF_CF32, IQF_SC16, IQF_RT, IQF_SC8, IQF_UC8>{s.iqf});
+  return rc == kNoMatch ? no_kernel(ctx, s) : rc;
 }
 
 // (k_raster_fast4 exists for ComplexF32 and sc16 only: the planner chooses it for no other format)
 static int launch_fast4(tsdr_ctx *ctx, const ImageStep &s, const TileParams &q, const StepPtrs &p) {
-  const dim3 grid = STEP_GRID, block(s.block);
-  if (s.pw == 32) {
-    if (s.iqf == IQF_SC16) { TSDR_LAUNCH(ctx, s.name, (k_raster_fast4<IQF_SC16, 32>), grid, block, s.lds, FAST_ARGS); }
-    else { TSDR_LAUNCH(ctx, s.name, (k_raster_fast4<IQF_CF32, 32>), grid, block, s.lds, FAST_ARGS); }
-  } else if (s.iqf == IQF_SC16) {
-    TSDR_LAUNCH(ctx, s.name, (k_raster_fast4<IQF_SC16, 16>), grid, block, s.lds, FAST_ARGS);
-  } else {
-    TSDR_LAUNCH(ctx, s.name, (k_raster_fast4<IQF_CF32, 16>), grid, block, s.lds, FAST_ARGS);
-  }
-  return TSDR_OK;
+  int rc = kNoMatch;
+  with_consts([&](auto F, auto PW) { rc = LAUNCHED((k_raster_fast4<F, PW>), STEP_GRID, dim3(s.block), s.lds, FAST_ARGS); },
+              Among<IQF_CF32, IQF_SC16>{s.iqf}, Among<16, 32>{s.pw});
+  return rc == kNoMatch ? no_kernel(ctx, s) : rc;
 }
 
 static int launch_tile(tsdr_ctx *ctx, const ImageStep &s, const TileParams &q, const StepPtrs &p) {
-  const dim3 grid = STEP_GRID, block(s.block);
-  if (s.cplx) {
-    if (s.down) { TSDR_LAUNCH(ctx, s.name, (k_raster_tile<true, true>), grid, block, s.lds, TILE_ARGS); }
-    else { TSDR_LAUNCH(ctx, s.name, (k_raster_tile<true, false>), grid, block, s.lds, TILE_ARGS); }
-  } else if (s.down) {
-    TSDR_LAUNCH(ctx, s.name, (k_raster_tile<false, true>), grid, block, s.lds, TILE_ARGS);
-  } else {
-    TSDR_LAUNCH(ctx, s.name, (k_raster_tile<false, false>), grid, block, s.lds, TILE_ARGS);
-  }
-  return TSDR_OK;
+  int rc = kNoMatch;
+  with_consts([&](auto C, auto D) { rc = LAUNCHED((k_raster_tile<C, D>), STEP_GRID, dim3(s.block), s.lds, TILE_ARGS); }, AmongBool{s.cplx}, AmongBool{s.down});
+  return rc == kNoMatch ? no_kernel(ctx, s) : rc;
 }
 
 static int launch_direct(tsdr_ctx *ctx, const ImageStep &s, const StepPtrs &p) {
@@ -1191,29 +1174,19 @@ static int launch_direct(tsdr_ctx *ctx, const ImageStep &s, const StepPtrs &p) {
   return TSDR_OK;
 }
 
-// the FAST modes of k_down_fused (IQ input), once per input format
-template <int M, int SUMS, int LD>
-static int down_k(tsdr_ctx *ctx, const ImageStep &s, const DownParams &q, const StepPtrs &p) {
-  const dim3 grid = STEP_GRID, block(s.block);
-  if (s.iqf == IQF_SC16) { TSDR_LAUNCH(ctx, s.name, (k_down_fused<true, M, SUMS, LD, IQF_SC16>), grid, block, s.lds, DOWN_ARGS); }
-  else if (s.iqf == IQF_SC8) { TSDR_LAUNCH(ctx, s.name, (k_down_fused<true, M, SUMS, LD, IQF_SC8>), grid, block, s.lds, DOWN_ARGS); }
-  else if (s.iqf == IQF_UC8) { TSDR_LAUNCH(ctx, s.name, (k_down_fused<true, M, SUMS, LD, IQF_UC8>), grid, block, s.lds, DOWN_ARGS); }
-  else { TSDR_LAUNCH(ctx, s.name, (k_down_fused<true, M, SUMS, LD>), grid, block, s.lds, DOWN_ARGS); }
-  return TSDR_OK;
-}
-template <int M>
-static int down_m(tsdr_ctx *ctx, const ImageStep &s, const DownParams &q, const StepPtrs &p) {
-  if (s.sums) return s.ld == 16 ? down_k<M, DS_PSUM, 16>(ctx, s, q, p) : down_k<M, DS_PSUM, 4>(ctx, s, q, p);
-  return s.ld == 16 ? down_k<M, DS_NONE, 16>(ctx, s, q, p) : down_k<M, DS_NONE, 4>(ctx, s, q, p);
-}
+// the FAST modes of k_down_fused (IQ input), once per input format; the EXACT one (IQ or real input) reads the format from its
+// parameters and has no sums and four loads in flight: an EXACT step carries sums = DS_NONE, ld = 4, iqf = IQF_RT
 static int launch_down(tsdr_ctx *ctx, const ImageStep &s, const DownParams &q, const StepPtrs &p) {
-  if (s.mode == DM_FAST_FX) return down_m<DM_FAST_FX>(ctx, s, q, p);
-  if (s.mode == DM_FAST_F32) return down_m<DM_FAST_F32>(ctx, s, q, p);
-  const dim3 grid = STEP_GRID, block(s.block);
-  if (s.cplx) { TSDR_LAUNCH(ctx, s.name, (k_down_fused<true, DM_EXACT, DS_NONE, 4>), grid, block, s.lds, DOWN_ARGS); }
-  else { TSDR_LAUNCH(ctx, s.name, (k_down_fused<false, DM_EXACT, DS_NONE, 4>), grid, block, s.lds, DOWN_ARGS); }
-  return TSDR_OK;
+  int rc = kNoMatch;
+  if (s.mode == DM_EXACT && s.sums == DS_NONE && s.ld == 4 && s.iqf == IQF_RT) {
+    with_consts([&](auto C) { rc = LAUNCHED((k_down_fused<C, DM_EXACT, DS_NONE, 4>), STEP_GRID, dim3(s.block), s.lds, DOWN_ARGS); }, AmongBool{s.cplx});
+  } else if (s.cplx == 1) {
+    with_consts([&](auto M, auto SUMS, auto LD, auto F) { rc = LAUNCHED((k_down_fused<true, M, SUMS, LD, F>), STEP_GRID, dim3(s.block), s.lds, DOWN_ARGS); },
+                Among<DM_FAST_FX, DM_FAST_F32>{s.mode}, Among<DS_NONE, DS_PSUM>{s.sums}, Among<4, 16>{s.ld}, Among<IQF_CF32, IQF_SC16, IQF_SC8, IQF_UC8>{s.iqf});
+  }
+  return rc == kNoMatch ? no_kernel(ctx, s) : rc;
 }
+#undef LAUNCHED
 #undef DOWN_ARGS
 #undef TILE_ARGS
 #undef FAST_ARGS
@@ -1245,7 +1218,7 @@ static int launch_step(tsdr_ctx *ctx, const ImageStep &s, const StepPtrs &p, flo
     }
     case IK_SHEAR: return launch_shear(ctx, s, p.in, p.in_stride, p.out, p.out_stride);
     case IK_RESIZE2D: return resize2d_d(ctx, p.out, s.rs[0], s.rs[1], s.rs[2], s.rs[3], p.down);
-    default: assert(!"a plan step names a kernel"); return TSDR_EINVAL;
+    default: return no_kernel(ctx, s);
   }
 }
 

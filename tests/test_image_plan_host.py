@@ -14,6 +14,14 @@ Two error texts of the planner cannot be reached by any input, in the old code o
                                                   for ratios >= 1, where there are at most 69 of either
   "raster: tile plan needs the f32-sample walk"  guards a tile wider than 47 samples without the f32-sample walk; the tile
                                                   search falls back to the 47-sample budget exactly when that walk is not planned
+and a third one guards the set of k_raster_fast instantiations that the planner may name and the launcher builds
+(image_plan.h:fast_instance):
+  "raster: the tile plan names a kernel that is not built"   the step's template arguments fail fast_instance, whose rules are
+                                                  the planner's own conditions; test_planner_and_table_name_the_same_kernels
+                                                  sweeps for a counterexample
+
+That set is held from three sides: `plan_dump --table` prints it, `plan_dump --reach` prints what a sweep over plan_images met,
+and the device code of resample.hip is compiled and its kernel symbols are read.  All three must be the same list.
 """
 import os
 import re
@@ -24,7 +32,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "image_plans_v1.txt")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-MAX_CASES = 600
+MAX_CASES = 640
 
 PROFILE_NAMES = """raster_down_iq raster_iq down_walk_iq raster_down_iq_exact raster_down_f32_exact raster_iq_exact raster_f32_exact
 raster_direct_iq raster_direct_f32 down_fused_iq down_fused_iq_sums down_fused_iq_exact down_fused_f32_exact raster_sheared_iq
@@ -32,7 +40,11 @@ raster_unsheared_iq resize2d""".split()
 ERROR_TEXTS = ["y_t and x_t must be positive", "frame larger than 2^31 samples/pixels", "imresize needs at least 2 input samples",
                "output size must be positive", "imresize needs at least a 2x2 raster",
                "raster: too many tiles for one launch (split the buffer)"]
-UNREACHABLE = ["raster: candidate table overflow", "raster: tile plan needs the f32-sample walk"]   # (module docstring)
+UNREACHABLE = ["raster: candidate table overflow", "raster: tile plan needs the f32-sample walk",
+               "raster: the tile plan names a kernel that is not built"]   # (module docstring)
+# k_raster_fast instantiations that fast_instance admits and the sweep of `plan_dump --reach` does not meet: {name: why it stays}.
+# At most 8; none so far.
+TABLE_NOT_REACHED = {}
 
 
 def golden_lines():
@@ -102,3 +114,53 @@ def test_the_record_reaches_every_route():
     for text in UNREACHABLE:
         assert text not in errs
 
+
+
+def _lines(exe, mode):
+    r = subprocess.run([exe, mode], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    return r.stdout.split()
+
+
+def test_planner_and_table_name_the_same_kernels(plan_dump):
+    table = _lines(plan_dump, "--table")
+    reach = _lines(plan_dump, "--reach")
+    assert table == sorted(set(table)) and reach == sorted(set(reach))
+    walks = {x for x in reach if x.startswith("k_raster_fast<")}
+    assert set(table) and all(x.startswith("k_raster_fast<") for x in table)
+    assert not walks - set(table), "the planner names kernels the launcher lacks"
+    assert len(TABLE_NOT_REACHED) <= 8 and set(TABLE_NOT_REACHED) <= set(table)
+    assert set(table) - walks == set(TABLE_NOT_REACHED), "the launcher builds kernels no plan of the sweep names"
+    # the record's own steps lie in the table too, the gpu-inst-* cases of tests/test_raster_instances_gpu.py among them
+    recorded = {s[1] for x in golden_lines() for s in parse(x)[2] if s[1].startswith("k_raster_fast<")}
+    assert recorded <= set(table)
+    # the tap kernel has no table: the sweep meets every one of its 34 instantiations (2 EXACT: IQ and real input; FAST: fixed-point
+    # or f64 taps x sums or not x 4 or 16 loads in flight x four input formats), so resample.hip:launch_down has nothing to drop
+    assert len([x for x in reach if x.startswith("k_down_fused<")]) == 34
+
+
+def test_the_code_object_holds_exactly_the_table(plan_dump, tmp_path):
+    """resample.hip compiled for the device alone, with the library's flags (about 40 s): its k_raster_fast symbols are the table"""
+    import importlib.util
+    import shutil
+    filt = shutil.which("c++filt") or shutil.which("llvm-cxxfilt")
+    if filt is None:
+        pytest.skip("no demangler (c++filt, llvm-cxxfilt) on this machine")
+    spec = importlib.util.spec_from_file_location("tsdr_build_flags", os.path.join(ROOT, "tempestsdr.jl_amd", "build.py"))
+    build = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(build)
+    elf = str(tmp_path / "resample.elf")
+    r = subprocess.run([HIPCC] + build.FLAGS + ["-w", "--cuda-device-only", "--no-gpu-bundle-output", "-c",
+                        os.path.join(ROOT, "tempestsdr.jl_amd", "csrc", "resample.hip"), "-o", elf], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    # kernel descriptors: one 64-byte object `<kernel symbol>.kd` per kernel, in the ELF's symbol table
+    data = open(elf, "rb").read()
+    syms = sorted({m.group(1).decode() for m in re.finditer(rb"(_Z[A-Za-z0-9_]+)\.kd\0", data)})
+    assert syms
+    r = subprocess.run([filt], input="\n".join(syms), capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    built = {re.sub(r"\(.*$", "", x).replace("void tsdr::", "").replace(" ", "") for x in r.stdout.splitlines()}
+    walks = {x for x in built if x.startswith("k_raster_fast<")}
+    table = set(_lines(plan_dump, "--table"))
+    assert walks == table, (sorted(walks - table)[:4], sorted(table - walks)[:4])
+    assert len([x for x in built if x.startswith("k_down_fused<")]) == 34

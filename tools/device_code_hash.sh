@@ -7,7 +7,11 @@
 set -e
 REF=${1:-HEAD}
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
-LLVM=${LLVM_BIN:-/opt/rocm/llvm/bin}
+# the LLVM tools beside hipcc: ROCm keeps them under llvm/bin or lib/llvm/bin; llvm-readelf is llvm-readobj in its GNU style
+LLVM=$LLVM_BIN
+for d in /opt/rocm/llvm/bin /opt/rocm/lib/llvm/bin; do [ -n "$LLVM" ] || { [ -x "$d/llvm-objcopy" ] && LLVM=$d; }; done
+[ -n "$LLVM" ] || { echo "no llvm-objcopy under /opt/rocm (set LLVM_BIN)" >&2; exit 2; }
+readelf() { if [ -x "$LLVM/llvm-readelf" ]; then "$LLVM/llvm-readelf" "$@"; else "$LLVM/llvm-readobj" --elf-output-style=GNU "$@"; fi; }
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS=$(cd "$ROOT" && python3 -c "
 import importlib.util as u
@@ -28,8 +32,8 @@ done | xargs -P "${JOBS:-8}" -L 1 bash -c '
 figures() {  # kernel symbols with their sizes, then each kernel's resource figures from the code object's metadata note
   # (both sorted by name: a host-side change may move the order in which kernels are emitted; the per-source id symbol
   # __hip_cuid_* differs whenever the source text does)
-  "$LLVM/llvm-readelf" -sW "$1" | awk '($4 == "FUNC" || $4 == "OBJECT") && $8 !~ /^__hip_cuid_/ { print $8, $3 }' | sort
-  "$LLVM/llvm-readelf" --notes "$1" | grep -E '^ +\.(name|sgpr_count|vgpr_count|agpr_count|sgpr_spill_count|vgpr_spill_count|group_segment_fixed_size|private_segment_fixed_size|kernarg_segment_size|max_flat_workgroup_size):' | sed 's/^ *//' |
+  readelf -sW "$1" | awk '($4 == "FUNC" || $4 == "OBJECT") && $8 !~ /^__hip_cuid_/ { print $8, $3 }' | sort
+  readelf --notes "$1" | grep -E '^ +\.(name|sgpr_count|vgpr_count|agpr_count|sgpr_spill_count|vgpr_spill_count|group_segment_fixed_size|private_segment_fixed_size|kernarg_segment_size|max_flat_workgroup_size):' | sed 's/^ *//' |
     awk '{ k = $1 } k in seen { print name, rec; delete seen; rec = "" } { seen[k] = 1; if (k == ".name:") name = $2; else rec = rec " " $1 $2 } END { if (rec != "") print name, rec }' | sort
 }
 bad=0

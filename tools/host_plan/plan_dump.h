@@ -215,6 +215,28 @@ inline std::vector<Case> cases() {
     std::snprintf(b, sizeof b, "sweep-%03d", i);
     add(c, b);
   }
+  // 7  the geometries of tests/test_raster_instances_gpu.py: one per class of k_raster_fast instantiation (image_plan.h:
+  //    fast_instance), two frames each, the smallest rasters that produce the class
+  {
+    // the raster-only walk (200 x 300 is smaller than the 600 x 800 image: nothing to downgrade) at each tile width: TP = 4 .. 128
+    // from 10 .. 0.1 samples per raster pixel; one of them less than 128 lines high (one wavefront per workgroup column)
+    const Wl ras[] = {{"pw1", 600000, 200, 300}, {"pw2", 240000, 200, 300}, {"pw4", 120000, 200, 300}, {"pw8", 66000, 200, 300},
+                      {"pw16", 30000, 200, 300}, {"pw32-vw1", 3000, 100, 300}, {"pw1-w64", 676000, 130, 520}};   // (w64: 130 strips, the 64-bit advance)
+    for (const Wl &w : ras) { Case c = geo(w.S, w.y, w.x, 2); c.raster = 1; add(c, std::string("gpu-inst-ras-") + w.n); }
+    // the f32-sample walk with the in-walk downgrade (640 x 832) at TP = 32, 64, 128 (2.5, 1.15, 0.5 samples per raster pixel),
+    // with and without a raster to write (below 2 samples per pixel the tap kernel would take the second: "fast_walk_only")
+    const Wl dn[] = {{"pw8", 1331200, 640, 832}, {"pw16", 612352, 640, 832}, {"pw32", 266240, 640, 832}};
+    for (const Wl &w : dn)
+      for (int ras1 = 1; ras1 >= 0; --ras1) {
+        Case c = geo(w.S, w.y, w.x, 2); c.raster = ras1; c.fast_walk_only = !ras1 && w.S < 2 * 640 * 832;
+        add(c, std::string("gpu-inst-rec4-") + w.n + (ras1 ? "-ras" : "-nor"));
+      }
+    for (int f = FMT_SC16; f <= FMT_UC8; ++f) { Case c = geo(266240, 640, 832, 2); c.raster = 1; c.fmt = f; add(c, std::string("gpu-inst-rec4-pw32-ras-") + fmt_name(f)); }
+    // the record walk with the downgrade ("raster_rec4" 0; its 47-sample lines hold 128 pixels up to 0.33 samples per pixel)
+    Case c = geo(53248, 640, 832, 2); c.raster_rec4 = 0; c.raster = 1; add(c, "gpu-inst-rec-pw32-ras");
+    c.raster = 0; c.fast_walk_only = 1; add(c, "gpu-inst-rec-pw32-nor");
+    c = geo(12000, 200, 300, 2); c.raster = 1; add(c, "gpu-inst-ras-pw32");   // the 128-pixel raster-only tile two wavefronts high
+  }
   return v;
 }
 

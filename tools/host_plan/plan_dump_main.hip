@@ -5,9 +5,13 @@
 //   plan_dump --full ID    the canonical parameter dump of one case
 //   plan_dump --one FMT EXACT S Y_T X_T FRAMES RASTER IMAGES CUS    the line of one IQ request given on the command line (FMT: 0 cf32,
 //                          1 sc16, 2 sc8, 3 uc8; tests/test_grid_cap_host.py: the direct raster kernel's grid against its work)
+//   plan_dump --table      every k_raster_fast instantiation image_plan.h:fast_instance admits (what resample.hip builds), one per line
+//   plan_dump --reach      the distinct kernel instantiations a built-in sweep over plan_images met, sorted (tests/test_image_plan_host.py:
+//                          for k_raster_fast the two lists are equal)
 // Build, host only:  hipcc --cuda-host-only -std=c++17 -ffp-contract=off -Iinclude tools/host_plan/plan_dump_main.hip -o plan_dump
 #include <cstdlib>
 #include <cstring>
+#include <set>
 
 #include "../../tempestsdr.jl_amd/csrc/image_plan.h"
 #include "plan_dump.h"
@@ -15,11 +19,16 @@
 using namespace tsdr;
 
 // kernel<template arguments> of a step, spelled as a demangler prints the instantiation
+static const char *b(int v) { return v ? "true" : "false"; }
+static std::string fast_text(int f32w, int down, int pw, int out, int vw, int rec4, int iqf) {
+  plan_dump::Txt t;
+  t.f("k_raster_fast<true,%s,%s,%d,%s,%d,%s,%d>", b(f32w), b(down), pw, b(out), vw, b(rec4), iqf);
+  return t.s;
+}
 static std::string kernel_text(const ImageStep &s) {
   plan_dump::Txt t;
-  auto b = [](int v) { return v ? "true" : "false"; };
   switch (s.kernel) {
-    case IK_FAST: t.f("k_raster_fast<true,%s,%s,%d,%s,%d,%s,%d>", b(s.f32w), b(s.down), s.pw, b(s.out), s.vw, b(s.rec4), s.iqf); break;
+    case IK_FAST: return fast_text(s.f32w, s.down, s.pw, s.out, s.vw, s.rec4, s.iqf);
     case IK_FAST4: t.f("k_raster_fast4<%d,%d>", s.iqf, s.pw); break;
     case IK_TILE: t.f("k_raster_tile<%s,%s>", b(s.cplx), b(s.down)); break;
     case IK_DIRECT: t.f("k_raster_direct<%s>", b(s.cplx)); break;
@@ -31,7 +40,7 @@ static std::string kernel_text(const ImageStep &s) {
   return t.s;
 }
 
-static plan_dump::Outcome run(const plan_dump::Case &c) {
+static ImagePlan plan_of(const plan_dump::Case &c) {
   PlanOpts o;
   o.raster_rec4 = c.raster_rec4; o.raster_v4 = c.raster_v4; o.raster_split = c.raster_split; o.fast_walk_only = c.fast_walk_only;
   o.down_spp_max_pct = c.down_spp_max_pct; o.down_xcd = c.down_xcd; o.cu_count = c.cu_count;
@@ -41,7 +50,11 @@ static plan_dump::Outcome run(const plan_dump::Case &c) {
   r.raster = c.raster != 0; r.images = c.images != 0; r.sums = c.sums != 0;
   r.raster_addr = c.raster ? (uintptr_t)0x7f0010000000ull + c.raster_addr_low : 0;
   r.raster_stride = (size_t)c.y_t * (size_t)c.x_t;
-  const ImagePlan pl = plan_images(o, r);
+  return plan_images(o, r);
+}
+
+static plan_dump::Outcome run(const plan_dump::Case &c) {
+  const ImagePlan pl = plan_of(c);
   plan_dump::Outcome out;
   out.status = pl.status; out.err = pl.err;
   out.raster = pl.raster; out.images = pl.images; out.fallback = pl.fallback; out.ws_raster = pl.ws_raster;
@@ -69,7 +82,42 @@ static plan_dump::Outcome run(const plan_dump::Case &c) {
   return out;
 }
 
+// --table: fast_instance over a box that holds every value a template argument can take (and some it cannot)
+static void print_table() {
+  std::set<std::string> names;
+  for (int f32w = 0; f32w < 2; ++f32w) for (int down = 0; down < 2; ++down) for (int pw = 0; pw <= 64; ++pw) for (int out = 0; out < 2; ++out)
+    for (int vw = 0; vw <= 4; ++vw) for (int rec4 = 0; rec4 < 2; ++rec4) for (int iqf = 0; iqf <= IQF_UC8; ++iqf)
+      if (fast_instance(f32w, down, pw, out, vw, rec4, iqf)) names.insert(fast_text(f32w, down, pw, out, vw, rec4, iqf));
+  for (const std::string &n : names) std::puts(n.c_str());
+}
+
+// --reach: raster sizes around every threshold of the planner (2, 64 / 128 lines, 128 / 256 pixels, 128 tiles, 2P = 2^24), sample
+// ratios across every tile width of the three staging budgets, five output sizes, and every value of the request (the four IQ
+// formats and real input, both precisions, raster / images / sums wanted) and of the options that plan_images reads
+static void print_reach() {
+  static const int ys[] = {2, 20, 100, 127, 128, 200, 640, 1125, 2300, 17000}, xs[] = {2, 30, 255, 256, 300, 832, 2576, 4500, 17000};
+  static const double ratios[] = {0.05, 0.115, 0.3, 0.45, 0.6, 0.7, 1.0, 1.15, 1.4, 2.0, 2.8, 4.0, 6.0, 10.0, 14.0, 20.0, 80.0};
+  static const int outs[][2] = {{600, 800}, {100, 150}, {64, 64}, {1125, 2576}, {1200, 1600}};
+  struct Opt { int rec4, v4, split, walk; };
+  static const Opt opts[] = {{-1, 0, 0, 0}, {0, 0, 0, 0}, {1, 0, 0, 0}, {-1, 0, 0, 1}, {0, 0, 0, 1}, {-1, 1, 0, 0}, {-1, 32, 0, 0}, {-1, 0, 1, 0}, {-1, 0, 2, 0}};
+  std::set<std::string> names;
+  for (int y : ys) for (int x : xs) for (double ratio : ratios) for (const auto &hw : outs) for (const Opt &op : opts)
+    for (int fmt = 0; fmt < 5; ++fmt) for (int bits = 0; bits < 16; ++bits) {   // (fmt 4: real samples)
+      plan_dump::Case c;
+      c.y_t = y; c.x_t = x; c.S = (unsigned long long)(ratio * (double)y * (double)x); c.h_out = hw[0]; c.w_out = hw[1];
+      c.raster_rec4 = op.rec4; c.raster_v4 = op.v4; c.raster_split = op.split; c.fast_walk_only = op.walk;
+      c.cplx = fmt < 4; c.fmt = c.cplx ? fmt : 0; c.scale = c.cplx ? plan_dump::fmt_scale(fmt) : 1.0f;
+      c.exact = bits & 1; c.raster = (bits >> 1) & 1; c.images = (bits >> 2) & 1; c.sums = (bits >> 3) & 1;
+      if ((!c.images && !c.raster) || (!c.cplx && !c.exact)) continue;
+      const ImagePlan pl = plan_of(c);
+      for (int i = 0; i < pl.nsteps; ++i) names.insert(kernel_text(pl.step[i]));
+    }
+  for (const std::string &n : names) std::puts(n.c_str());
+}
+
 int main(int argc, char **argv) {
+  if (argc == 2 && !std::strcmp(argv[1], "--table")) { print_table(); return 0; }
+  if (argc == 2 && !std::strcmp(argv[1], "--reach")) { print_reach(); return 0; }
   if (argc == 11 && !std::strcmp(argv[1], "--one")) {
     plan_dump::Case c;
     c.id = "one"; c.cplx = 1; c.fmt = std::atoi(argv[2]); c.scale = c.fmt ? 1.0f / 128.0f : 1.0f; c.exact = std::atoi(argv[3]);
@@ -79,7 +127,7 @@ int main(int argc, char **argv) {
     return 0;
   }
   const char *want = (argc == 3 && !std::strcmp(argv[1], "--full")) ? argv[2] : nullptr;
-  if (argc != 1 && !want) { std::fprintf(stderr, "usage: %s [--full ID | --one FMT EXACT S Y_T X_T FRAMES RASTER IMAGES CUS]\n", argv[0]); return 2; }
+  if (argc != 1 && !want) { std::fprintf(stderr, "usage: %s [--table | --reach | --full ID | --one FMT EXACT S Y_T X_T FRAMES RASTER IMAGES CUS]\n", argv[0]); return 2; }
   bool found = false;
   for (const plan_dump::Case &c : plan_dump::cases()) {
     if (want && c.id != want) continue;
