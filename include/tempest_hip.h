@@ -593,6 +593,8 @@ int tsdr_frames_pipeline_info(tsdr_ctx *ctx, int *trials_left, int *chosen, floa
 #include "tempest_hip_cfold.h"
 /* coherent stacking across buffers: the fold's picture kept complex, turned onto a complex state (given phase, or phase lock) and blended */
 #include "tempest_hip_cstack.h"
+/* carrier tracking: a frame phase probe, and coherent stacking along a phase track (a weight per frame and line) */
+#include "tempest_hip_ctrack.h"
 
 /* ---- host -> device staging ring ---------------------------------------
  * The consumer side of AtomicCircularBuffer (AtomicAbstractSDRs.jl:64-190): `depth` slots of nEch samples in

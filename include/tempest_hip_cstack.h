@@ -7,7 +7,8 @@
  * which averaging magnitudes cannot undo.  Here the complex state exists: the state keeps Z itself, every call turns its own Z onto
  * the state and blends the two as complex numbers, and the magnitude is taken once, of the blended state.  The turn is either the
  * caller's (GIVEN: the call's start phase phi carries the carrier across buffers, cstack_plan of the bindings) or measured (LOCK: the
- * inner product of Z and the state), which survives a dropped buffer or a retune.  The entry points below go beyond the reference
+ * inner product of Z and the state), which survives a dropped buffer or a carrier phase step (a retune that moves kappa by whole
+ * turns per frame also changes the phase ramp along each frame: tempest_hip_ctrack.h).  The entry points below go beyond the reference
  * and change nothing that exists.
  *
  *  1. INPUT.  As tempest_hip_cfold.h, 1.: iq, n, the format rule, the geometry y_t x x_t with P = y_t*x_t, t0, T, F = n_frames, the

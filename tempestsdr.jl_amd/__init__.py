@@ -21,3 +21,5 @@ from .display import display_u8, display_u8_d  # noqa: F401
 from .fold import fold, fold_d, fold_plan, fold_scan, fold_scan_d, refine_period  # noqa: F401
 from .cfold import cfold, cfold_d, cfold_scan, cfold_scan_d, refine_carrier  # noqa: F401
 from .cstack import cstack, cstack_d, cstack_plan  # noqa: F401
+from .ctrack import (constant_track, ctrack_probe, ctrack_probe_d, ctrack_stack, ctrack_stack_d, fit_track,  # noqa: F401
+                     refine_track)

@@ -279,6 +279,16 @@ _SIGS_CSTACK = {
 }
 CSTACK_GIVEN, CSTACK_LOCK, CSTACK_INFO = 0, 1, 8  # TSDR_CSTACK_*
 
+# include/tempest_hip_ctrack.h (included after tempest_hip_cstack.h): carrier tracking -- a frame phase probe, stacking along a phase track
+_CTRACK_STACK = _FOLD + [C.c_double, vp] + _GEOM + [C.c_float, C.c_int, vp, vp, vp]  # T, track, ..., alpha, mode, zstate, mag, info
+_CTRACK_PROBE = _FOLD + [C.c_double, vp] + _GEOM + [vp, vp]                           # T, track, ..., zref, out
+_SIGS_CTRACK = {
+    "tsdr_ctrack_stack_iq_d": (C.c_int, list(_CTRACK_STACK)),
+    "tsdr_ctrack_stack_iq": (C.c_int, list(_CTRACK_STACK)),
+    "tsdr_ctrack_probe_iq_d": (C.c_int, list(_CTRACK_PROBE)),
+    "tsdr_ctrack_probe_iq": (C.c_int, list(_CTRACK_PROBE)),
+}
+
 
 def exported_names():
     """Every symbol include/tempest_hip.h declares (kept in sync by tests/test_abi.py)."""
@@ -325,6 +335,11 @@ def exported_names_cstack():
     return sorted(_SIGS_CSTACK)
 
 
+def exported_names_ctrack():
+    """Every symbol include/tempest_hip_ctrack.h declares (kept in sync by tests/test_ctrack_host.py)."""
+    return sorted(_SIGS_CTRACK)
+
+
 def _share_torch_hip_runtime():
     """PyTorch-ROCm wheels bundle their own libamdhip64/libhsa-runtime64.  Two HIP runtimes in one
     process cannot both own the GPU (whichever initialises second sees no device), and the dynamic
@@ -352,7 +367,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(_SIGS.items()) + list(_SIGS_IQ.items()) + list(_SIGS_CPLX.items()) + list(_SIGS_HIRES.items()) + \
             list(_SIGS_REGISTER.items()) + list(_SIGS_DISPLAY.items()) + list(_SIGS_FOLD.items()) + list(_SIGS_CFOLD.items()) + \
-            list(_SIGS_CSTACK.items()):
+            list(_SIGS_CSTACK.items()) + list(_SIGS_CTRACK.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI is incomplete
         fn.restype = res
         fn.argtypes = args

@@ -693,6 +693,38 @@ class Context:
         """-> (F, next_t0, next_phi): fold_plan, and the carrier phase carried over the F frames and the straddling one"""
         return _cstack.cstack_plan(n, t0, T, kappa, phi, theta)
 
+    # -- carrier tracking: a frame phase probe, stacking along a phase track (include/tempest_hip_ctrack.h; ctrack.py) ----------------
+    def ctrack_stack(self, iq, t0, T, track, n_frames, y_t, x_t, alpha=0.0, mode="given", zstate=None, fmt="cf32", scale=1.0):
+        """-> (zstate, mag, info) of cstack along `track` ((F, 2) float64: frame f on line l turned by -(a_f + b_f (l + 1/2) / y_t) turns)"""
+        return _ctrack.ctrack_stack(self, iq, t0, T, track, n_frames, y_t, x_t, alpha, mode, zstate, fmt, scale)
+
+    def ctrack_stack_d(self, iq, fmt, scale, n, t0, T, track, n_frames, y_t, x_t, alpha, mode, zstate, mag=None, info=None):
+        """device-pointer form of ctrack_stack (track: 2 * n_frames float64 on the device): enqueues on the context's stream and returns"""
+        return _ctrack.ctrack_stack_d(self, iq, fmt, scale, n, t0, T, track, n_frames, y_t, x_t, alpha, mode, zstate, mag, info)
+
+    def ctrack_probe(self, iq, t0, T, track, n_frames, y_t, x_t, zref, fmt="cf32", scale=1.0):
+        """-> (rho complex128[F], E_f float64[F], gamma float64[F], E_s): every frame's inner product with the picture zref after the
+        track's turn (track None: the zero track)"""
+        return _ctrack.ctrack_probe(self, iq, t0, T, track, n_frames, y_t, x_t, zref, fmt, scale)
+
+    def ctrack_probe_d(self, iq, fmt, scale, n, t0, T, track, n_frames, y_t, x_t, zref, out):
+        """device-pointer form of ctrack_probe (out: 4 * n_frames + 1 float64 on the device): enqueues and returns"""
+        return _ctrack.ctrack_probe_d(self, iq, fmt, scale, n, t0, T, track, n_frames, y_t, x_t, zref, out)
+
+    @staticmethod
+    def constant_track(n_frames, kappa, phi=0.0, slope=0.0):
+        """-> the (F, 2) track a_f = f * kappa + phi, b_f = slope: cstack's weights when slope == 0"""
+        return _ctrack.constant_track(n_frames, kappa, phi, slope)
+
+    @staticmethod
+    def fit_track(rho, track, degree=2):
+        """-> (track, p): `track` corrected by the weighted polynomial through the probe's phases arg(rho_f) / 2 pi"""
+        return _ctrack.fit_track(rho, track, degree)
+
+    def refine_track(self, iq_d, fmt, scale, n, t0, T, n_frames, y_t, x_t, kappa, iterations=2, degree=2, zstate=None, mag=None):
+        """-> (track, polynomials, gammas): a buffer's phase track from a start kappa, by stack / probe / fit iterations"""
+        return _ctrack.refine_track(self, iq_d, fmt, scale, n, t0, T, n_frames, y_t, x_t, kappa, iterations, degree, zstate, mag)
+
 
 def frames_d(ctx, sync, iq, nEch, S, y_t, x_t, alpha, do_align, state, frames_out=None, raster_out=None, sync_idx=None):
     """Device-pointer form of Context.frames: every array argument is a device buffer (torch tensor
@@ -776,6 +808,8 @@ from . import fold as _fold  # noqa: E402  (the package exports a function of th
 from . import cfold as _cfold  # noqa: E402  (the package exports a function of that name)
 # coherent stacking across buffers (the entry points of include/tempest_hip_cstack.h): cstack.py
 from . import cstack as _cstack  # noqa: E402  (the package exports a function of that name)
+# carrier tracking (the entry points of include/tempest_hip_ctrack.h): ctrack.py
+from . import ctrack as _ctrack  # noqa: E402
 
 
 def frames_iq_d(ctx, sync, iq, fmt, scale, nEch, S, y_t, x_t, alpha, do_align, state, frames_out=None, raster_out=None, sync_idx=None,

@@ -20,6 +20,16 @@ __device__ inline void coh_add(float2 &a, float2 z, float2 w) {
   a.x = __fadd_rn(a.x, __fsub_rn(__fmul_rn(w.x, z.x), __fmul_rn(w.y, z.y)));
   a.y = __fadd_rn(a.y, __fadd_rn(__fmul_rn(w.x, z.y), __fmul_rn(w.y, z.x)));
 }
+// w * z alone, the term coh_add sums: two products and one sum per component, each rounded
+__device__ inline float2 coh_mul(float2 z, float2 w) {
+  return make_float2(__fsub_rn(__fmul_rn(w.x, z.x), __fmul_rn(w.y, z.y)), __fadd_rn(__fmul_rn(w.x, z.y), __fmul_rn(w.y, z.x)));
+}
+// the weight of frame f on raster line l of y_t along a track (include/tempest_hip_ctrack.h, TRACK): a, b in turns,
+// c_l = fl64((l + 1/2) / y_t), x = fma(b, c_l, a); b == 0 leaves x = a exactly
+__device__ inline float2 coh_line_weight(double a, double b, int l, int y_t) {
+  const double c = ((double)l + 0.5) / (double)y_t;
+  return coh_weight(fma(b, c, a));
+}
 // Z = acc / F: one fdiv per component
 __device__ inline float2 coh_mean(float2 a, float Ff) { return make_float2(__fdiv_rn(a.x, Ff), __fdiv_rn(a.y, Ff)); }
 

@@ -19,6 +19,9 @@
 // A Flavour is a struct of constants and static functions:
 //   Sample, Trial              the staged sample, the trial parameters a launch carries (FoldArgs::tr)
 //   has_weights, NS            whether frame f of trial k has a weight; f64 statistics per trial of the scan
+//   line_weights               the weight of frame f is a function of the raster line too (raster_ctrack.hip; one trial): the lane is
+//                              the line, so lanes 0 .. 63 evaluate line_weight(tr, f, l, y_t) of the tile's 64 lines into LDS where
+//                              `weight` would fill its KB entries, and a lane's walk reads its own line's entry
 //   stacks                     the fold keeps its picture complex (raster_cstack.hip): its epilogue is the scan's with one trial, and
 //                              stack(A, s, acc, Ff, at) per pixel -- the pixel's share of the NS statistics and its stores at state
 //                              index `at` -- in place of stat; the tile's NS sums land at part[tile][NS]
@@ -100,7 +103,9 @@ __global__ __launch_bounds__(NW * 64) void k_fold_engine(FoldArgs<typename Fl::T
   extern __shared__ Sample smp[];              // STAGED: [64][W | 1] samples
   __shared__ int kfirst[2][kFoldLines];        // STAGED: first staged sample of every line (relative to the frame's bi), by frame parity
   __shared__ float2 wts[2][KB];                // has_weights: the batch's weights of a frame, by frame parity
+  __shared__ float2 lwts[2][Fl::line_weights ? kFoldLines : 1];   // line_weights: the tile's 64 lines' weights of a frame instead
   __shared__ double red[KB][NS][NW];           // SCAN: the wavefronts' partial statistics
+  static_assert(!Fl::line_weights || (Fl::has_weights && KB == 1), "weights per line: one trial");
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int tp = (int)(blockIdx.x / (unsigned)A.tiles_l), tl = (int)(blockIdx.x - (unsigned)tp * (unsigned)A.tiles_l);
@@ -124,8 +129,11 @@ __global__ __launch_bounds__(NW * 64) void k_fold_engine(FoldArgs<typename Fl::T
 
   for (int f = 0; f < A.F; ++f) {
     const FramePos fp = frame_pos(A, T, f);
-    if constexpr (Fl::has_weights)
+    if constexpr (Fl::line_weights) {
+      if (tid < kFoldLines) lwts[f & 1][tid] = Fl::line_weight(A.tr, f, min(l0 + tid, A.y_t - 1), A.y_t);
+    } else if constexpr (Fl::has_weights) {
       if (tid < KB) wts[f & 1][tid] = Fl::weight(A.tr, f, trial0 + tid);
+    }
     if constexpr (STAGED) {
       if (tid < kFoldLines) {
         double d;
@@ -162,7 +170,8 @@ __global__ __launch_bounds__(NW * 64) void k_fold_engine(FoldArgs<typename Fl::T
 #pragma unroll
       for (int j = 0; j < KB; ++j) {
         w[j] = make_float2(0.f, 0.f);
-        if constexpr (Fl::has_weights) w[j] = wts[f & 1][j];
+        if constexpr (Fl::line_weights) w[j] = lwts[f & 1][lane];
+        else if constexpr (Fl::has_weights) w[j] = wts[f & 1][j];
       }
       const int rb = STAGED ? lane * Wp - kfirst[f & 1][lane] : 0;   // smp[rb + k]: sample k of this lane's line
       const double s0 = fold_s(fp, spp, mrow + (unsigned)pbeg);
@@ -298,6 +307,8 @@ struct FoldCall {
   int mode = 0;
   float *mag = nullptr;
   double *info = nullptr;
+  const double *track = nullptr;   // raster_ctrack.hip: (a_f, b_f) per frame in turns (the probe: may be null), and the probe's reference
+  const float *zref = nullptr;
   double t_max() const { return T + (double)(n_trials - 1) * dT; }   // the largest trial period
 };
 

@@ -36,6 +36,8 @@
 //   tsdr_display_u8              images WS_IN; out WS_OUT; ranges WS_AUX
 //   fold, cfold (fold_entry)     iq WS_IN; WS_OUT: the state (up if alpha != 0 and no scan, down) or a scan's scores
 //   cstack (stack_entry)         iq WS_IN; zstate WS_OUT (up if alpha != 0, down); WS_AUX: mag, then info
+//   ctrack stack                 iq WS_IN; zstate WS_OUT (up if alpha != 0, down); WS_AUX: mag, then info, then the track (up)
+//   ctrack probe                 iq WS_IN; out WS_OUT; WS_AUX: zref, then the track (both up)
 //   tsdr_resampler_lpf (f32)     the narrowed H WS_FFT_A
 // (WS_MISC is also demod.hip's scratch: no host form above runs a demodulator.)
 #pragma once

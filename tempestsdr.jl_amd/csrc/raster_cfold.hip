@@ -26,7 +26,7 @@ struct Coherent {
     double kappa0, dkappa;   // trial k = blockIdx.y * KB + j turns frame f by -f * (kappa0 + k * dkappa) turns
     int n_trials;
   };
-  static constexpr bool has_weights = true, stacks = false;
+  static constexpr bool has_weights = true, stacks = false, line_weights = false;
   static constexpr int NS = 1, kMaxTrials = TSDR_CFOLD_MAX_TRIALS, kStageMax = TSDR_CFOLD_STAGE_MAX, kSlot = WS_CFOLD;
   static constexpr const char *name = "cfold";
   static int tile_p(bool scan) { return scan ? kScanP : kFoldTileP; }

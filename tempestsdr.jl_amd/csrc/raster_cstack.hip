@@ -49,7 +49,7 @@ struct Stacked {
     float *mag;             // GIVEN: |S'| (may be null)
     float2 *zws;            // LOCK: Z, in state order
   };
-  static constexpr bool has_weights = true, stacks = true;
+  static constexpr bool has_weights = true, stacks = true, line_weights = false;
   static constexpr int NS = 4, kMaxTrials = 1, kStageMax = TSDR_CFOLD_STAGE_MAX, kSlot = WS_CSTACK;
   static constexpr const char *name = "cstack";
   static int tile_p(bool) { return kFoldTileP; }
@@ -65,7 +65,9 @@ struct Stacked {
   }
   __device__ static float2 blend(float2 a, float2 b, double d) { return coh_blend(a, b, d); }
   __device__ static void add(float2 &a, float2 z, float2 w) { coh_add(a, z, w); }
-  __device__ static void stack(const FoldArgs<Trial> &A, double *s, float2 acc, float Ff, size_t at) {
+  // Args: FoldArgs of a stacking flavour, whose Trial has mode, mag and zws (this one's, or raster_ctrack.hip's)
+  template <class Args>
+  __device__ static void stack(const Args &A, double *s, float2 acc, float Ff, size_t at) {
     const float2 Z = coh_mean(acc, Ff);
     float2 *zp = reinterpret_cast<float2 *>(A.state) + at;
     float2 S = make_float2(0.f, 0.f);
@@ -164,30 +166,55 @@ __global__ __launch_bounds__(kBlendThreads) void k_cstack_blend(const float2 *__
   }
 }
 
-int Stacked::launch(tsdr_ctx *ctx, const FoldCall &c, const FoldGeom &g, const FoldArgs<Trial> &A0) {
+// the workspace of a stacking call (WS_CSTACK, above): the fold's partial sums, q, Z
+struct StackWs {
+  double *part;
+  float2 *q, *zws;
+};
+bool stack_ws(tsdr_ctx *ctx, const FoldCall &c, const FoldGeom &g, StackWs &w) {
+  const size_t part_bytes = 32 * g.tiles, z_off = part_bytes + 16;
+  char *ws = (char *)ctx->scratch(WS_CSTACK, z_off + (c.mode == TSDR_CSTACK_LOCK ? 8 * (size_t)c.y_t * (size_t)c.x_t : 0));
+  if (!ws) return false;
+  w = StackWs{reinterpret_cast<double *>(ws), reinterpret_cast<float2 *>(ws + part_bytes), reinterpret_cast<float2 *>(ws + z_off)};
+  return true;
+}
+
+// what follows the fold of a stacking flavour: cstack_lock when the mode or info asks for it, cstack_blend in LOCK mode
+int stack_finish(tsdr_ctx *ctx, const FoldCall &c, const FoldGeom &g, const StackWs &w) {
   const size_t P = (size_t)c.y_t * (size_t)c.x_t;
   const bool lock = c.mode == TSDR_CSTACK_LOCK;
-  const size_t part_bytes = 32 * g.tiles, z_off = part_bytes + 16;
-  char *ws = (char *)ctx->scratch(WS_CSTACK, z_off + (lock ? 8 * P : 0));
-  if (!ws) return TSDR_ENOMEM;
-  FoldArgs<Trial> A = A0;
-  A.part = reinterpret_cast<double *>(ws);
-  A.tr.zws = reinterpret_cast<float2 *>(ws + z_off);
-  float2 *q = reinterpret_cast<float2 *>(ws + part_bytes);
-  const dim3 wg_tile(kFoldTileWaves * 64), wg_direct(kFoldDirectWaves * 64);
-  if (g.staged) TSDR_LAUNCH(ctx, "cstack_tile", (k_fold_engine<Stacked, kFoldTileP, kFoldTileWaves, 1, true, false>), g.grid, wg_tile, g.lds, A);
-  else TSDR_LAUNCH(ctx, "cstack_direct", (k_fold_engine<Stacked, kFoldDirectP, kFoldDirectWaves, 1, false, false>), g.grid, wg_direct, 0, A);
   if (lock || c.info)
-    TSDR_LAUNCH(ctx, "cstack_lock", k_cstack_lock, dim3(1), dim3(64), 0, (const double *)A.part, (unsigned)g.tiles, c.mode, c.info, q);
+    TSDR_LAUNCH(ctx, "cstack_lock", k_cstack_lock, dim3(1), dim3(64), 0, (const double *)w.part, (unsigned)g.tiles, c.mode, c.info, w.q);
   if (!lock) return TSDR_OK;
   float2 *zs = reinterpret_cast<float2 *>(c.state);
   if ((reinterpret_cast<uintptr_t>(zs) & 15u) == 0)
     TSDR_LAUNCH(ctx, "cstack_blend", k_cstack_blend<true>, dim3((unsigned)ceil_div(ceil_div(P, 2), kBlendThreads)), dim3(kBlendThreads), 0,
-                (const float2 *)A.tr.zws, (const float2 *)q, (unsigned)P, c.alpha, zs, c.mag);
+                (const float2 *)w.zws, (const float2 *)w.q, (unsigned)P, c.alpha, zs, c.mag);
   else
     TSDR_LAUNCH(ctx, "cstack_blend", k_cstack_blend<false>, dim3((unsigned)ceil_div(P, kBlendThreads)), dim3(kBlendThreads), 0,
-                (const float2 *)A.tr.zws, (const float2 *)q, (unsigned)P, c.alpha, zs, c.mag);
+                (const float2 *)w.zws, (const float2 *)w.q, (unsigned)P, c.alpha, zs, c.mag);
   return TSDR_OK;
+}
+
+}  // namespace
+}  // namespace tsdr
+
+// raster_ctrack.hip (stacking along a phase track: a weight per frame and line) includes this file for everything above -- the
+// epilogue, cstack_lock, cstack_blend, the workspace -- and leaves this flavour's launches and entry points to this translation unit
+#ifndef TSDR_CSTACK_NO_ENTRY_POINTS
+namespace tsdr {
+namespace {
+
+int Stacked::launch(tsdr_ctx *ctx, const FoldCall &c, const FoldGeom &g, const FoldArgs<Trial> &A0) {
+  StackWs w;
+  if (!stack_ws(ctx, c, g, w)) return TSDR_ENOMEM;
+  FoldArgs<Trial> A = A0;
+  A.part = w.part;
+  A.tr.zws = w.zws;
+  const dim3 wg_tile(kFoldTileWaves * 64), wg_direct(kFoldDirectWaves * 64);
+  if (g.staged) TSDR_LAUNCH(ctx, "cstack_tile", (k_fold_engine<Stacked, kFoldTileP, kFoldTileWaves, 1, true, false>), g.grid, wg_tile, g.lds, A);
+  else TSDR_LAUNCH(ctx, "cstack_direct", (k_fold_engine<Stacked, kFoldDirectP, kFoldDirectWaves, 1, false, false>), g.grid, wg_direct, 0, A);
+  return stack_finish(ctx, c, g, w);
 }
 
 // an entry point: the refusals, then the device form, or the host form around it (upload iq -- and zstate if alpha != 0 --, launch,
@@ -243,3 +270,4 @@ int tsdr_cstack_iq(tsdr_ctx *ctx, const void *iq, int iq_fmt, float scale, size_
 }
 
 }  // extern "C"
+#endif  // TSDR_CSTACK_NO_ENTRY_POINTS

@@ -16,7 +16,7 @@ static_assert((TSDR_FOLD_STAGE_MAX | 1) * kFoldLines * 4 + 4 * kFoldLines * 2 + 
 struct Envelope {
   using Sample = float;
   struct Trial { double T0, dT; };   // the launch's trial blockIdx.y folds at T0 + blockIdx.y * dT
-  static constexpr bool has_weights = false, stacks = false;
+  static constexpr bool has_weights = false, stacks = false, line_weights = false;
   static constexpr int NS = 2, kMaxTrials = TSDR_FOLD_MAX_TRIALS, kStageMax = TSDR_FOLD_STAGE_MAX, kSlot = WS_FOLD;
   static constexpr const char *name = "fold";
   static int tile_p(bool) { return kFoldTileP; }

@@ -3,7 +3,8 @@ blended into it, the magnitude taken once of the blended state -- through the en
 call of their symbols is here; api.Context.cstack / cstack_d / cstack_plan delegate to this module.  The loop a viewer runs on a weak
 target: refine_period and refine_carrier once; per buffer F, t0_next, phi_next = cstack_plan(n, t0, T, kappa, phi) and
 cstack_d(..., t0, T, kappa, phi, F, ..., alpha, mode, zstate, mag, info) with the carried t0 and phi.  mode "given" trusts the carried
-phi; "lock" measures the turn between the buffer's picture and the state and survives a dropped buffer or a retune."""
+phi; "lock" measures the turn between the buffer's picture and the state and survives a dropped buffer or a carrier phase step
+(a retune by whole turns per frame also changes the phase along each frame: ctrack.py)."""
 import ctypes as C
 import math
 

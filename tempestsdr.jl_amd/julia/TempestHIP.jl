@@ -740,5 +740,7 @@ include("TempestHIP_fold.jl")
 include("TempestHIP_cfold.jl")
 # coherent stacking across buffers, a complex fold state and a phase lock: hip_cstack!, hip_cstack_d!, cstack_plan (include/tempest_hip_cstack.h)
 include("TempestHIP_cstack.jl")
+# carrier tracking, a frame phase probe and stacking along a phase track: hip_ctrack_stack!, hip_ctrack_probe, fit_track, constant_track (include/tempest_hip_ctrack.h)
+include("TempestHIP_ctrack.jl")
 
 end # module

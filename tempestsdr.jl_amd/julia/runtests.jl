@@ -96,4 +96,19 @@ ref = load_all(refdir)
         @test all(mag .<= 1f-6)
         @test TempestHIP.cstack_plan(600, 0.0, T, 0.125, 0.5) == (14, 15 * T - 600, 0.375)
     end
+    # carrier tracking: a constant sample probed along a track that turns frame f by 0.003 f^2 turns (0.36 at the last frame) shows
+    # exactly those phases, the fit finds the quadratic (a_f + p(f) - p'(f)/2 = 0.003 f), and the stack along the zero track is the mean
+    let z0 = ComplexF32(0.3, -0.4), T = 40.5, F = 12, iq = fill(ComplexF32(0.3, -0.4), 600)
+        zref = fill(z0, 4, 4)
+        track = TempestHIP.constant_track(F, 0.0)
+        track[1, :] .= [0.003 * f^2 for f in 0:F-1]
+        ρ, E_f, γ, E_s = TempestHIP.hip_ctrack_probe(iq, 0.0, T, track, F, zref)
+        @test all(abs.(γ .- 1.0) .<= 1e-6) && abs(E_s - 16 * 0.25) <= 1e-5
+        @test all(abs.(angle.(ρ) ./ 2π .+ [0.003 * f^2 for f in 0:F-1]) .<= 1e-6)
+        fitted, coef = TempestHIP.fit_track(ρ, track)
+        @test abs(coef[3] + 0.003) <= 1e-6 && all(abs.(fitted[1, :] .- 0.003 .* (0:F-1)) .<= 1e-5)
+        zs = zeros(ComplexF32, 4, 4)
+        TempestHIP.hip_ctrack_stack!(zs, iq, 0.0, T, TempestHIP.constant_track(F, 0.0), F)
+        @test all(abs.(zs .- z0) .<= 1f-6)
+    end
 end
