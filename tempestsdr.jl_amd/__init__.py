@@ -23,3 +23,5 @@ from .cfold import cfold, cfold_d, cfold_scan, cfold_scan_d, refine_carrier  # n
 from .cstack import cstack, cstack_d, cstack_plan  # noqa: F401
 from .ctrack import (constant_track, ctrack_probe, ctrack_probe_d, ctrack_stack, ctrack_stack_d, fit_track,  # noqa: F401
                      refine_track)
+from .gram import (blind_track, coherent_period_scan, ctrack_gram, ctrack_gram_d, gram_carrier, gram_energy, gram_phases,  # noqa: F401
+                   gram_track, track_slopes)

@@ -289,6 +289,16 @@ _SIGS_CTRACK = {
     "tsdr_ctrack_probe_iq": (C.c_int, list(_CTRACK_PROBE)),
 }
 
+# include/tempest_hip_gram.h (included after tempest_hip_ctrack.h): the frame Gram matrix along a track.  gram.py names the two symbols
+# through GRAM_IQ_D / GRAM_IQ: every other module of the package stays free of the tsdr_ctrack prefix, which belongs to ctrack.py
+_CTRACK_GRAM = _FOLD + [C.c_double, vp] + _GEOM + [vp]                                # T, track, ..., gram
+GRAM_IQ_D, GRAM_IQ = "tsdr_ctrack_gram_iq_d", "tsdr_ctrack_gram_iq"
+_SIGS_GRAM = {
+    GRAM_IQ_D: (C.c_int, list(_CTRACK_GRAM)),
+    GRAM_IQ: (C.c_int, list(_CTRACK_GRAM)),
+}
+GRAM_MAX_FRAMES, GRAM_CHUNK, GRAM_MAX_TILES = 64, 1024, 65536  # TSDR_GRAM_*
+
 
 def exported_names():
     """Every symbol include/tempest_hip.h declares (kept in sync by tests/test_abi.py)."""
@@ -340,6 +350,11 @@ def exported_names_ctrack():
     return sorted(_SIGS_CTRACK)
 
 
+def exported_names_gram():
+    """Every symbol include/tempest_hip_gram.h declares (kept in sync by tests/test_gram_host.py)."""
+    return sorted(_SIGS_GRAM)
+
+
 def _share_torch_hip_runtime():
     """PyTorch-ROCm wheels bundle their own libamdhip64/libhsa-runtime64.  Two HIP runtimes in one
     process cannot both own the GPU (whichever initialises second sees no device), and the dynamic
@@ -367,7 +382,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(_SIGS.items()) + list(_SIGS_IQ.items()) + list(_SIGS_CPLX.items()) + list(_SIGS_HIRES.items()) + \
             list(_SIGS_REGISTER.items()) + list(_SIGS_DISPLAY.items()) + list(_SIGS_FOLD.items()) + list(_SIGS_CFOLD.items()) + \
-            list(_SIGS_CSTACK.items()) + list(_SIGS_CTRACK.items()):
+            list(_SIGS_CSTACK.items()) + list(_SIGS_CTRACK.items()) + list(_SIGS_GRAM.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI is incomplete
         fn.restype = res
         fn.argtypes = args

@@ -725,6 +725,48 @@ class Context:
         """-> (track, polynomials, gammas): a buffer's phase track from a start kappa, by stack / probe / fit iterations"""
         return _ctrack.refine_track(self, iq_d, fmt, scale, n, t0, T, n_frames, y_t, x_t, kappa, iterations, degree, zstate, mag)
 
+    # -- the frame Gram matrix: blind carrier phases and the kappa periodogram from one pass (include/tempest_hip_gram.h; gram.py) ----
+    def ctrack_gram(self, iq, t0, T, track, n_frames, y_t, x_t, fmt="cf32", scale=1.0):
+        """-> G complex128 (F, F): G[f][g] = sum_m v_f(m) conj(v_g(m)), the frames of `iq` turned along `track` ((F, 2) or None)"""
+        return _gram.ctrack_gram(self, iq, t0, T, track, n_frames, y_t, x_t, fmt, scale)
+
+    def ctrack_gram_d(self, iq, fmt, scale, n, t0, T, track, n_frames, y_t, x_t, gram):
+        """device-pointer form of ctrack_gram (gram: 2 * n_frames^2 float64 on the device; track may be None): enqueues and returns"""
+        return _gram.ctrack_gram_d(self, iq, fmt, scale, n, t0, T, track, n_frames, y_t, x_t, gram)
+
+    @staticmethod
+    def gram_energy(G, turns):
+        """-> the energy of the coherent fold for per-frame turns a_f, from G alone"""
+        return _gram.gram_energy(G, turns)
+
+    @staticmethod
+    def gram_carrier(G, oversample=16, steps=4):
+        """-> (kappa mod 1, energy): the maximum of the kappa periodogram of G"""
+        return _gram.gram_carrier(G, oversample, steps)
+
+    @staticmethod
+    def gram_phases(G, iters=50):
+        """-> (v, rho): every frame's carrier phase (unit modulus, v_0 = 1) and its inner product with the stack of all other frames"""
+        return _gram.gram_phases(G, iters)
+
+    @staticmethod
+    def gram_track(G, track=None, v=None):
+        """-> the track G was measured along with a_f += arg(v_f) / 2 pi (v: gram_phases(G)[0], computed when not given)"""
+        return _gram.gram_track(G, track, v)
+
+    @staticmethod
+    def track_slopes(track):
+        """-> the track with b_f from the differences of its a_f, and a_f moved from the frame's middle to its start"""
+        return _gram.track_slopes(track)
+
+    def blind_track(self, iq_d, fmt, scale, n, t0, T, n_frames, y_t, x_t, passes=2, zstate=None, mag=None):
+        """-> (track, |rho|): a buffer's phase track with no start kappa and no reference picture, then one stack along it"""
+        return _gram.blind_track(self, iq_d, fmt, scale, n, t0, T, n_frames, y_t, x_t, passes, zstate, mag)
+
+    def coherent_period_scan(self, iq_d, fmt, scale, n, t0, y_t, x_t, periods):
+        """-> (energies, kappas, best): the joint (T, kappa) search, one Gram launch per trial period"""
+        return _gram.coherent_period_scan(self, iq_d, fmt, scale, n, t0, y_t, x_t, periods)
+
 
 def frames_d(ctx, sync, iq, nEch, S, y_t, x_t, alpha, do_align, state, frames_out=None, raster_out=None, sync_idx=None):
     """Device-pointer form of Context.frames: every array argument is a device buffer (torch tensor
@@ -810,6 +852,8 @@ from . import cfold as _cfold  # noqa: E402  (the package exports a function of 
 from . import cstack as _cstack  # noqa: E402  (the package exports a function of that name)
 # carrier tracking (the entry points of include/tempest_hip_ctrack.h): ctrack.py
 from . import ctrack as _ctrack  # noqa: E402
+# the frame Gram matrix (the entry points of include/tempest_hip_gram.h): gram.py
+from . import gram as _gram  # noqa: E402
 
 
 def frames_iq_d(ctx, sync, iq, fmt, scale, nEch, S, y_t, x_t, alpha, do_align, state, frames_out=None, raster_out=None, sync_idx=None,

@@ -23,7 +23,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-std=c++
 #   TSDR_BUILD_DEFINES="TSDR_ROWSUM_CHUNK8 TSDR_FIR_NOFMA" python tempestsdr.jl_amd/build.py --force
 FLAGS += ["-D" + d for d in os.environ.get("TSDR_BUILD_DEFINES", "").split()]
 # a translation unit that includes another one's source (without its entry points) is stale when that source changes
-INCLUDED_SOURCES = {"raster_ctrack.hip": ["raster_cstack.hip"]}
+INCLUDED_SOURCES = {"raster_ctrack.hip": ["raster_cstack.hip"], "raster_gram.hip": ["raster_ctrack.hip", "raster_cstack.hip"]}
 
 
 def _stale(target, deps):
@@ -39,7 +39,7 @@ def build_hip(force=False, verbose=True):
     hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     hdrs += [os.path.join(ROOT, "include", h) for h in ("tempest_hip.h", "tempest_hip_iq.h", "tempest_hip_cplx.h", "tempest_hip_hires.h",
                                                        "tempest_hip_register.h", "tempest_hip_display.h", "tempest_hip_fold.h", "tempest_hip_cfold.h",
-                                                       "tempest_hip_cstack.h", "tempest_hip_ctrack.h")]
+                                                       "tempest_hip_cstack.h", "tempest_hip_ctrack.h", "tempest_hip_gram.h")]
     jobs = []
     for s in srcs:
         src = os.path.join(CSRC, s)

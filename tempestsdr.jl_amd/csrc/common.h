@@ -40,6 +40,7 @@ enum Slot {
   WS_CFOLD,       // raster_cfold.hip: per (trial, tile) the f64 partial energies of a carrier scan's complex pictures
   WS_CSTACK,      // raster_cstack.hip: per tile the four f64 partial sums of a call, its rotation q, and (LOCK) the complex picture Z
   WS_CTRACK,      // raster_ctrack.hip: per (frame, tile) the f64 partial sums of a phase probe (Re rho_f, Im rho_f, E_f, the tile's E_s)
+  WS_GRAM,        // raster_gram.hip: per (tile, accumulator in use) the f64 partial sums of a frame Gram matrix's 32 x 32 blocks
   WS_HIRES,       // tsdr_frames_hires_iq_d: the rasters of one chunk of frames (raster_accum.hip)
   WS_HIRES_IDX,   // ... and the buffer's sync indices when the caller passes none
   WS_HIRES_SHIFTS,  // ... and the raster-unit shifts its frames were averaged with (tsdr_frames_hires_shifts)

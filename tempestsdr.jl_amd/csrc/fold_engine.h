@@ -348,13 +348,25 @@ int fold_check(tsdr_ctx *ctx, const char *fn, const FoldCall &c, bool device, Iq
   return TSDR_OK;
 }
 
-// the device form: checked arguments, F > 0.  The staged/direct choice is made on a 128-pixel line span at the largest trial (the
-// headers' COST); W is the span of the kernel's own tile.
+// The staged/direct choice of a call, made on a 128-pixel line span at the largest trial (the headers' COST), and its tiles of 64 lines
+// x tile_p or 16 pixels: fold_launch's geometry, which a flavour's refusals may ask for before anything is enqueued.
+template <class Fl>
+inline bool fold_staged(const FoldCall &c) {
+  const double P = (double)c.y_t * (double)c.x_t;
+  return std::ceil((double)kFoldTileP * (c.t_max() / P)) + 3.0 <= (double)Fl::kStageMax;
+}
+template <class Fl>
+inline size_t fold_tiles(const FoldCall &c, bool staged) {
+  const int TP = staged ? Fl::tile_p(c.scan) : kFoldDirectP;
+  return ceil_div((size_t)c.y_t, kFoldLines) * ceil_div((size_t)c.x_t, (size_t)TP);
+}
+
+// the device form: checked arguments, F > 0.  W is the span of the kernel's own tile.
 template <class Fl>
 int fold_launch(tsdr_ctx *ctx, const FoldCall &c, const IqFmt &f) {
   const double P = (double)c.y_t * (double)c.x_t;
   FoldGeom g{};
-  g.staged = std::ceil((double)kFoldTileP * (c.t_max() / P)) + 3.0 <= (double)Fl::kStageMax;
+  g.staged = fold_staged<Fl>(c);
   const int TP = g.staged ? Fl::tile_p(c.scan) : kFoldDirectP;
   FoldArgs<typename Fl::Trial> A{};
   A.iq = reinterpret_cast<const float *>(c.iq);
@@ -368,7 +380,7 @@ int fold_launch(tsdr_ctx *ctx, const FoldCall &c, const IqFmt &f) {
   A.alpha = c.alpha;
   A.state = c.state;
   A.tr = Fl::trial(c);
-  g.tiles = (size_t)A.tiles_l * ceil_div((size_t)c.x_t, (size_t)TP);
+  g.tiles = fold_tiles<Fl>(c, g.staged);
   if (g.tiles >= (1ull << 31)) return set_err(ctx, TSDR_EINVAL, "%s: %zu tiles exceed the grid", Fl::name, g.tiles);
   g.grid = dim3((unsigned)g.tiles, (unsigned)ceil_div((size_t)c.n_trials, (size_t)Fl::batch(c.scan)));
   g.lds = g.staged ? (size_t)kFoldLines * (size_t)(A.W | 1) * sizeof(typename Fl::Sample) : 0;

@@ -38,6 +38,7 @@
 //   cstack (stack_entry)         iq WS_IN; zstate WS_OUT (up if alpha != 0, down); WS_AUX: mag, then info
 //   ctrack stack                 iq WS_IN; zstate WS_OUT (up if alpha != 0, down); WS_AUX: mag, then info, then the track (up)
 //   ctrack probe                 iq WS_IN; out WS_OUT; WS_AUX: zref, then the track (both up)
+//   ctrack gram                  iq WS_IN; gram WS_OUT; the track WS_AUX (up)
 //   tsdr_resampler_lpf (f32)     the narrowed H WS_FFT_A
 // (WS_MISC is also demod.hip's scratch: no host form above runs a demodulator.)
 #pragma once

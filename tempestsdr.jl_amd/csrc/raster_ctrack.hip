@@ -360,6 +360,9 @@ FoldCall track_probe_call(const void *iq, int iq_fmt, float scale, size_t n, dou
 }  // namespace
 }  // namespace tsdr
 
+// raster_gram.hip (the frame Gram matrix along a track) includes this file for everything above -- the track's weight, the refusals
+// of a period and of a track's values, the call record -- and leaves the entry points to this translation unit
+#ifndef TSDR_CTRACK_NO_ENTRY_POINTS
 using namespace tsdr;
 
 extern "C" {
@@ -389,3 +392,4 @@ int tsdr_ctrack_probe_iq(tsdr_ctx *ctx, const void *iq, int iq_fmt, float scale,
 }
 
 }  // extern "C"
+#endif  // TSDR_CTRACK_NO_ENTRY_POINTS

@@ -742,5 +742,7 @@ include("TempestHIP_cfold.jl")
 include("TempestHIP_cstack.jl")
 # carrier tracking, a frame phase probe and stacking along a phase track: hip_ctrack_stack!, hip_ctrack_probe, fit_track, constant_track (include/tempest_hip_ctrack.h)
 include("TempestHIP_ctrack.jl")
+# the frame Gram matrix, blind carrier phases and the κ periodogram from one pass: hip_ctrack_gram, hip_ctrack_gram_d!, gram_energy, gram_carrier, gram_phases, gram_track, track_slopes, blind_track (include/tempest_hip_gram.h)
+include("TempestHIP_gram.jl")
 
 end # module

@@ -111,4 +111,19 @@ ref = load_all(refdir)
         TempestHIP.hip_ctrack_stack!(zs, iq, 0.0, T, TempestHIP.constant_track(F, 0.0), F)
         @test all(abs.(zs .- z0) .<= 1f-6)
     end
+    # the frame Gram matrix: a constant sample turned by 0.003 f^2 turns gives G[f, g] = P |z0|^2 exp(-2πi (a_f - a_g)); the blind phases
+    # are the track's, negated; the energy at those turns is the whole energy P |z0|^2
+    let z0 = ComplexF32(0.3, -0.4), T = 40.5, F = 12, iq = fill(ComplexF32(0.3, -0.4), 600)
+        a = [0.003 * f^2 for f in 0:F-1]
+        track = TempestHIP.constant_track(F, 0.0)
+        track[1, :] .= a
+        G = TempestHIP.hip_ctrack_gram(iq, 0.0, T, track, F, 4, 4)
+        @test all(abs.(G .- 16 * 0.25 .* [cispi(-2 * (a[f] - a[g])) for f in 1:F, g in 1:F]) .<= 1e-4)
+        @test all(imag.(G[f, f]) == 0 for f in 1:F) && G == G'
+        v, ρ = TempestHIP.gram_phases(G)
+        @test all(abs.(v .- [cispi(-2 * x) for x in a]) .<= 1e-5)
+        @test abs(TempestHIP.gram_energy(G, -a) - 4.0) <= 1e-4
+        κ, e = TempestHIP.gram_carrier(TempestHIP.hip_ctrack_gram(iq, 0.0, T, nothing, F, 4, 4))
+        @test min(κ, 1 - κ) <= 1e-6 && abs(e - 4.0) <= 1e-4
+    end
 end
