@@ -104,8 +104,13 @@ def _stack_d(ctx, iq, fmt, scale, n, t0, T, kappa, phi, F, y, x, alpha, mode, zs
              C.c_float(alpha), mode, zs, mag, info)
 
 
+def _case_of(case):
+    """a case by its name in CASES, or the case itself: a dict with y, x, T, F, t0 (tests/fold_domain_cases.py's rows)"""
+    return CASES[case] if isinstance(case, str) else case
+
+
 def _case_d(ctx, name, d_iq, n, phi, alpha, mode, zs, mag, info, fmt=0, scale=1.0, kappa=KAPPA_TRUE):
-    c = CASES[name]
+    c = _case_of(name)
     _stack_d(ctx, d_iq, fmt, scale, n, c["t0"], c["T"], kappa, phi, c["F"], c["y"], c["x"], alpha, mode, zs, mag, info)
 
 

@@ -19,8 +19,8 @@ import cstack_ref as CS
 import ctrack_ref as R
 import dptr_util as D
 import test_ctrack_host as H
-from test_cstack_gpu import (ALL, CASES, IQ_PHASE, KAPPA_TRUE, KERNEL, MAG_PHASE, MODE_NAME, ZS_PHASE, _capture, _check_info, _fill, _null,
-                             _pkg, _profiled, _quantised, _report, _stack_d, _zref)
+from test_cstack_gpu import (ALL, CASES, IQ_PHASE, KAPPA_TRUE, KERNEL, MAG_PHASE, MODE_NAME, ZS_PHASE, _capture, _case_of, _check_info, _fill,
+                             _null, _pkg, _profiled, _quantised, _report, _stack_d, _zref)
 
 pytestmark = pytest.mark.gpu
 
@@ -74,12 +74,12 @@ def _probe_d(ctx, iq, fmt, scale, n, t0, T, track, F, y, x, zref, out):
 
 
 def _case_stack(ctx, name, d_iq, n, d_track, alpha, mode, zs, mag, info, fmt=0, scale=1.0):
-    c = CASES[name]
+    c = _case_of(name)
     _tstack_d(ctx, d_iq, fmt, scale, n, c["t0"], c["T"], d_track, c["F"], c["y"], c["x"], alpha, mode, zs, mag, info)
 
 
 def _case_probe(ctx, name, d_iq, n, d_track, zref, out, fmt=0, scale=1.0):
-    c = CASES[name]
+    c = _case_of(name)
     _probe_d(ctx, d_iq, fmt, scale, n, c["t0"], c["T"], d_track, c["F"], c["y"], c["x"], zref, out)
 
 

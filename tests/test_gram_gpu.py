@@ -39,6 +39,8 @@ ALL = list(CASES) + list(NEW)
 
 
 def _case(name):
+    if not isinstance(name, str):   # the case itself: a dict with y, x, T, F, t0 (tests/fold_domain_cases.py's rows)
+        return name
     if name in CASES:
         return dict(CASES[name], kernel=KERNEL[name], iq_phase=IQ_PHASE[name], n=_n(CASES[name]))
     c = NEW[name]
