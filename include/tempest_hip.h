@@ -597,6 +597,8 @@ int tsdr_frames_pipeline_info(tsdr_ctx *ctx, int *trials_left, int *chosen, floa
 #include "tempest_hip_ctrack.h"
 /* the frame Gram matrix: every pair of frames' inner product along a track from one pass -- blind carrier phases, the kappa periodogram */
 #include "tempest_hip_gram.h"
+/* the tuner: frequency shift by a 64-bit phase accumulator, real FIR low-pass and decimation of an IQ stream, chained across calls */
+#include "tempest_hip_tune.h"
 
 /* ---- host -> device staging ring ---------------------------------------
  * The consumer side of AtomicCircularBuffer (AtomicAbstractSDRs.jl:64-190): `depth` slots of nEch samples in

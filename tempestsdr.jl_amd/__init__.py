@@ -25,3 +25,4 @@ from .ctrack import (constant_track, ctrack_probe, ctrack_probe_d, ctrack_stack,
                      refine_track)
 from .gram import (blind_track, coherent_period_scan, ctrack_gram, ctrack_gram_d, gram_carrier, gram_energy, gram_phases,  # noqa: F401
                    gram_track, track_slopes)
+from .tune import Tuner, design_lowpass, freq_fix, phase_fix, tune, tune_d, tune_plan, tune_tile, tuned_t0  # noqa: F401

@@ -299,6 +299,17 @@ _SIGS_GRAM = {
 }
 GRAM_MAX_FRAMES, GRAM_CHUNK, GRAM_MAX_TILES = 64, 1024, 65536  # TSDR_GRAM_*
 
+# include/tempest_hip_tune.h (included after tempest_hip_gram.h): the tuner -- frequency shift, FIR low-pass, decimation (tune.py)
+c_u64 = C.c_uint64
+_TUNE = [vp, vp, C.c_int, C.c_float, c_sz, c_u64, c_u64, c_u64, vp, C.c_int, C.c_int, c_u64, vp, C.c_int, vp, c_sz, vp]
+#        ctx, iq, iq_fmt, scale, n, m0, nu_fix, phi_fix, taps, n_taps, decim, j0, hist, n_hist, out, out_cap, n_out
+_SIGS_TUNE = {
+    "tsdr_tune_iq_d": (C.c_int, list(_TUNE)),
+    "tsdr_tune_iq": (C.c_int, list(_TUNE)),
+    "tsdr_tune_tile": (C.c_int, [C.c_int, C.c_int]),   # n_taps, decim (no context)
+}
+TUNE_TAPS_MAX, TUNE_DECIM_MAX = 1024, 64  # TSDR_TUNE_*
+
 
 def exported_names():
     """Every symbol include/tempest_hip.h declares (kept in sync by tests/test_abi.py)."""
@@ -355,6 +366,11 @@ def exported_names_gram():
     return sorted(_SIGS_GRAM)
 
 
+def exported_names_tune():
+    """Every symbol include/tempest_hip_tune.h declares (kept in sync by tests/test_tune_host.py)."""
+    return sorted(_SIGS_TUNE)
+
+
 def _share_torch_hip_runtime():
     """PyTorch-ROCm wheels bundle their own libamdhip64/libhsa-runtime64.  Two HIP runtimes in one
     process cannot both own the GPU (whichever initialises second sees no device), and the dynamic
@@ -382,7 +398,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(_SIGS.items()) + list(_SIGS_IQ.items()) + list(_SIGS_CPLX.items()) + list(_SIGS_HIRES.items()) + \
             list(_SIGS_REGISTER.items()) + list(_SIGS_DISPLAY.items()) + list(_SIGS_FOLD.items()) + list(_SIGS_CFOLD.items()) + \
-            list(_SIGS_CSTACK.items()) + list(_SIGS_CTRACK.items()) + list(_SIGS_GRAM.items()):
+            list(_SIGS_CSTACK.items()) + list(_SIGS_CTRACK.items()) + list(_SIGS_GRAM.items()) + list(_SIGS_TUNE.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI is incomplete
         fn.restype = res
         fn.argtypes = args

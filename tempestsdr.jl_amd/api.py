@@ -767,6 +767,19 @@ class Context:
         """-> (energies, kappas, best): the joint (T, kappa) search, one Gram launch per trial period"""
         return _gram.coherent_period_scan(self, iq_d, fmt, scale, n, t0, y_t, x_t, periods)
 
+    # -- the tuner: frequency shift, FIR low-pass and decimation of an IQ stream (include/tempest_hip_tune.h; tune.py) ----
+    def tune(self, iq, nu_fix, taps, decim, m0=0, phi_fix=0, j0=None, hist=None, n_hist=0, fmt="cf32", scale=1.0):
+        """host arrays -> (y complex64[n_out], hist complex64[L - 1], next): `iq` shifted by nu_fix, low-passed by `taps`, decimated"""
+        return _tune.tune(self, iq, nu_fix, taps, decim, m0, phi_fix, j0, hist, n_hist, fmt, scale)
+
+    def tune_d(self, iq, fmt, scale, n, m0, nu_fix, phi_fix, taps, n_taps, decim, j0, hist, n_hist, out, out_cap):
+        """device-pointer form of tune (out: room for out_cap ComplexF32; hist: n_taps - 1 ComplexF32 or None): enqueues, returns n_out"""
+        return _tune.tune_d(self, iq, fmt, scale, n, m0, nu_fix, phi_fix, taps, n_taps, decim, j0, hist, n_hist, out, out_cap)
+
+    def tuner(self, nu_fix, taps, decim, phi_fix=0, m0=0):
+        """-> tune.Tuner: the device taps, the history and the plan of a stream, push_d per buffer"""
+        return _tune.Tuner(self, nu_fix, taps, decim, phi_fix, m0)
+
 
 def frames_d(ctx, sync, iq, nEch, S, y_t, x_t, alpha, do_align, state, frames_out=None, raster_out=None, sync_idx=None):
     """Device-pointer form of Context.frames: every array argument is a device buffer (torch tensor
@@ -854,6 +867,8 @@ from . import cstack as _cstack  # noqa: E402  (the package exports a function o
 from . import ctrack as _ctrack  # noqa: E402
 # the frame Gram matrix (the entry points of include/tempest_hip_gram.h): gram.py
 from . import gram as _gram  # noqa: E402
+# the tuner (the entry points of include/tempest_hip_tune.h): tune.py
+from . import tune as _tune  # noqa: E402
 
 
 def frames_iq_d(ctx, sync, iq, fmt, scale, nEch, S, y_t, x_t, alpha, do_align, state, frames_out=None, raster_out=None, sync_idx=None,

@@ -39,7 +39,7 @@ def build_hip(force=False, verbose=True):
     hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     hdrs += [os.path.join(ROOT, "include", h) for h in ("tempest_hip.h", "tempest_hip_iq.h", "tempest_hip_cplx.h", "tempest_hip_hires.h",
                                                        "tempest_hip_register.h", "tempest_hip_display.h", "tempest_hip_fold.h", "tempest_hip_cfold.h",
-                                                       "tempest_hip_cstack.h", "tempest_hip_ctrack.h", "tempest_hip_gram.h")]
+                                                       "tempest_hip_cstack.h", "tempest_hip_ctrack.h", "tempest_hip_gram.h", "tempest_hip_tune.h")]
     jobs = []
     for s in srcs:
         src = os.path.join(CSRC, s)

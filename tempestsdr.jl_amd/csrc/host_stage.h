@@ -39,6 +39,7 @@
 //   ctrack stack                 iq WS_IN; zstate WS_OUT (up if alpha != 0, down); WS_AUX: mag, then info, then the track (up)
 //   ctrack probe                 iq WS_IN; out WS_OUT; WS_AUX: zref, then the track (both up)
 //   ctrack gram                  iq WS_IN; gram WS_OUT; the track WS_AUX (up)
+//   tune (tune_entry)            iq WS_IN; out WS_OUT; WS_AUX: taps (up), then hist (up, down)
 //   tsdr_resampler_lpf (f32)     the narrowed H WS_FFT_A
 // (WS_MISC is also demod.hip's scratch: no host form above runs a demodulator.)
 #pragma once

@@ -744,5 +744,7 @@ include("TempestHIP_cstack.jl")
 include("TempestHIP_ctrack.jl")
 # the frame Gram matrix, blind carrier phases and the κ periodogram from one pass: hip_ctrack_gram, hip_ctrack_gram_d!, gram_energy, gram_carrier, gram_phases, gram_track, track_slopes, blind_track (include/tempest_hip_gram.h)
 include("TempestHIP_gram.jl")
+# the tuner, frequency shift + FIR low-pass + decimation of an IQ stream chained across calls: hip_tune!, hip_tune_d!, freq_fix, design_lowpass, tune_plan (include/tempest_hip_tune.h)
+include("TempestHIP_tune.jl")
 
 end # module

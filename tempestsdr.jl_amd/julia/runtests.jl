@@ -126,4 +126,21 @@ ref = load_all(refdir)
         κ, e = TempestHIP.gram_carrier(TempestHIP.hip_ctrack_gram(iq, 0.0, T, nothing, F, 4, 4))
         @test min(κ, 1 - κ) <= 1e-6 && abs(e - 4.0) <= 1e-4
     end
+    # the tuner: a tone at +0.125 Fs shifted by -0.125 Fs is the constant it started from, whatever unit-gain low-pass follows; two
+    # chained calls give the bits of one
+    let n = 4000, L = 31, D = 4, x = ComplexF32[0.5f0 * cispi(2 * 0.125 * m) for m in 0:n-1]
+        h = TempestHIP.design_lowpass(L, D)
+        ν = TempestHIP.freq_fix(-0.125, 1.0)
+        @test ν == UInt64(7) << 61 && abs(sum(Float64.(h)) - 1) <= 1e-6 && h == reverse(h)
+        cap, nxt = TempestHIP.tune_plan(0, n, L, D, 0, 0)
+        y, hist = zeros(ComplexF32, cap), zeros(ComplexF32, L - 1)
+        @test TempestHIP.hip_tune!(y, hist, x, 0, ν, UInt64(0), h, D, 0, 0) == cap == div(n - L, D) + 1
+        @test all(abs.(y .- 0.5f0) .<= 1f-5)
+        c1, n1 = TempestHIP.tune_plan(0, 1001, L, D, 0, 0)
+        y2, h2 = zeros(ComplexF32, cap), zeros(ComplexF32, L - 1)
+        @test TempestHIP.hip_tune!(y2, h2, x[1:1001], 0, ν, UInt64(0), h, D, 0, 0) == c1
+        rest = zeros(ComplexF32, cap - c1)
+        @test TempestHIP.hip_tune!(rest, h2, x[1002:end], n1.m0, ν, UInt64(0), h, D, n1.j0, n1.n_hist) == cap - c1
+        @test vcat(y2[1:c1], rest) == y && h2 == hist
+    end
 end
